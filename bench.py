@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """bench.py - alpha mattes/sec at 1024x1024 on N MI355X (BASELINE.json metric), one process per GPU.
 
-  python bench.py --gpus N --steps K --warmup W       (N > 1 without a launcher: re-executes itself under torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W       (N > 1 without a launcher: runs itself under torch.distributed.run in a child process)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+  python bench.py ... --dump-outputs DIR              (what the last timed step returned to its caller, as DIR/<name>.npy in float32)
+  python bench.py ... --full                          (also every companion measurement listed below)
 
 A "step" = one pass of the hot path (resize-free preprocessing -> VAE encode x2 -> U-Net -> VAE decode -> alpha) over a
 batch of B synthetic 1024x1024 image+trimap pairs per GPU that are already resident in HBM, through the same C-ABI entry
@@ -12,12 +14,16 @@ broadcasts the packed blob to the other ranks over RCCL.  Scaling is weak (B ima
 data-path collective other than the alpha gather).
 
 `value` is measured in the engine's DEFAULT precision ("fp16x3": split-fp16 MFMA operands + fp32 activations, the mode that
-meets the north star's 1e-3 alpha tolerance against the fp32 reference path; `parity` in the JSON line is measured in the
-same process).  The opt-in fast mode (plain fp16 operands, ~4e-3 from the reference) is timed next to it under `modes`.
+meets the north star's 1e-3 alpha tolerance against the fp32 reference path; with --full, `parity` in the JSON line is measured
+in the same process).  With --full, the opt-in fast mode (plain fp16 operands, ~4e-3 from the reference) is timed next to it
+under `modes`.
 
-Prints ONE JSON line on rank 0 (see the driver contract) including
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times the K steps and prints it; the
+fields below are null unless --full is given:
   "roofline"     : achieved vs peak for the dominant kernel (conv3x3 implicit-GEMM MFMA), HIP-event timed per launch
-  "cpu_baseline" : the fp32 CPU oracle (port of the reference's force_cpu path) timed on this host on a bounded sample.
+  "cpu_baseline" : the fp32 CPU oracle (port of the reference's force_cpu path) timed on this host on a bounded sample
+  "parity", "kernel_breakdown_ms", "launches_per_step", "single_image", "including_host_transfers", the companion steps with
+  engine options changed, and the other precision under "modes".
 """
 import argparse
 import json
@@ -33,6 +39,7 @@ from __graft_entry__ import load_package  # noqa: E402
 
 FLOPS_PER_IMAGE = {512: 5.96e12, 768: 14.59e12, 1024: 28.89e12}     # SURVEY.md 8d (dense, 2*MAC)
 MFMA_F16_PEAK_TFLOPS = 2500.0                                       # MI355X dense fp16 (MI355X_MICROARCH.md)
+DUMP_BYTES = 64_000_000                                             # --dump-outputs: at most this much array data in all
 
 
 def timed_steps(step, steps, world, dev):
@@ -44,13 +51,15 @@ def timed_steps(step, steps, world, dev):
         dist.barrier()
     sync()
     t0 = time.perf_counter()
+    out = None
     for _ in range(steps):
-        step()
+        out = step()
     sync()
     if world > 1:
         dist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    LAST_OUT[:] = [out]
     PER_RANK_S[:] = [elapsed]
     if world > 1:
         # every rank's own time (all_gather: the list's length is the number of ranks the collective REALLY spanned), then the maximum
@@ -63,6 +72,21 @@ def timed_steps(step, steps, world, dev):
 
 
 PER_RANK_S = []      # seconds of the last timed_steps() per rank (filled on every rank)
+LAST_OUT = []        # what the last step of the last timed_steps() returned to its caller
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> tensor.  Written as out_dir/<name>.npy in float32; when they hold more than DUMP_BYTES in all, each one is
+    replaced by the same fixed, seeded sample of its flattened elements (a share of DUMP_BYTES in proportion to its size)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BYTES:
+            keep = int(a.size * DUMP_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def main():
@@ -73,10 +97,15 @@ def main():
     ap.add_argument("--batch", type=int, default=4, help="images per GPU per step")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--precision", type=str, default=None, help="fp16x3 (default: meets the 1e-3 parity bar) or fp16 (fast)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every companion measurement (profiled step, roofline, B = 1 latency, host hand-over, "
+                         "steps with engine options changed, the other precision, CPU baseline and parity); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy in float32, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-mode", action="store_true", help="skip timing the non-default precision")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only warmup + timed steps + the one profiled step (all identical): the run rocprofv3 summaries are taken from")
+                    help="with --full: only warmup + timed steps + the one profiled step (all identical): the run rocprofv3 summaries are taken from")
     ap.add_argument("--cpu-sample-size", type=int, default=1024,
                     help="size of the ONE image the fp32 CPU oracle is timed on (default: the benchmark's own 1024 - about two minutes of host time)")
     ap.add_argument("--emu", action="store_true",
@@ -93,19 +122,26 @@ def main():
     ap.add_argument("--dense-attention", action="store_true",
                     help="walk every key tile in the trimap-biased self-attention instead of skipping the tiles whose bias underflows the softmax")
     args = ap.parse_args()
-    if args.timed_only:
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if (args.timed_only or args.dump_profile) and not args.full:
+        ap.error("--timed-only and --dump-profile describe the profiled step of a --full run: add --full")
+    if args.timed_only or not args.full:
         args.no_other_mode = args.no_cpu_baseline = True
+    if not args.full:
+        args.timed_only = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, RCCL rendezvous on 127.0.0.1)
+        # `python bench.py --gpus N` without a launcher: start the launcher (one rank per GPU, RCCL rendezvous on 127.0.0.1) in a child process
         if not args.emu and torch.cuda.device_count() < args.gpus:
             sys.exit(f"[bench] --gpus {args.gpus} requested but only {torch.cuda.device_count()} GPU(s) are visible")
         import socket
+        import subprocess
         with socket.socket() as s:
             s.bind(("127.0.0.1", 0))
             port = s.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                 "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]).returncode)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -176,6 +212,8 @@ def main():
             engine.apply_matte(img_d, tri_d, S, False, out=alpha, sync=dev.type != "cuda")    # stream-ordered with torch's current stream
             if world > 1:
                 dist.gather(alpha, gathered, dst=0)                              # RCCL on the same stream order: no host sync in between
+                return gathered
+            return [alpha]
         return step
 
     step = make_step(eng)
@@ -196,11 +234,15 @@ def main():
         step()
     elapsed = timed_steps(step, args.steps, world, dev)
     per_rank_s = list(PER_RANK_S)
-    ms_per_step = elapsed * 1e3 / max(args.steps, 1)
+    ms_per_step = elapsed * 1e3 / args.steps
     value = world * B * args.steps / elapsed
     if args.stream:
         value = len(stream_sizes) * args.steps / elapsed
         args.timed_only = True      # (the companion legs below describe the uniform 1024^2 batch)
+    if rank == 0 and args.dump_outputs:
+        # (before the --full legs below, which reuse the alpha buffer)
+        out = LAST_OUT[0]
+        dump_outputs(args.dump_outputs, {f"matted_rgba_{i:03d}": a for i, a in enumerate(out)} if args.stream else {"alpha": torch.cat(out)})
 
     if rank == 0:
         # ---- B = 1 latency (BASELINE configs[1] is quoted one image per call) ----
@@ -264,7 +306,7 @@ def main():
             eng.apply_matte(img_d, tri_d, S, False, out=alpha, sync=True)
             eng.profile(False)
             return eng.profile_results()
-        prof = profile_pass()
+        prof = profile_pass() if args.full else {}
         prof_dump = eng.profile_dump() if args.dump_profile else None
         prof_exec = prof
         skip_prev = eng.lib.get_option("trimap_skip")
@@ -296,7 +338,7 @@ def main():
                 pmc_stale = pmc_stale or pt.get("build_stamp") != build_stamp
         except Exception:
             pass
-        # matrix-pipe busy fraction of the same kernel from the committed SQ counter pass of `bench.py --timed-only`
+        # matrix-pipe busy fraction of the same kernel from the committed SQ counter pass of `bench.py --full --timed-only`
         # (profiles/pmc_sq.json, written by tools/pmc_sq.py: SQ_VALU_MFMA_BUSY_CYCLES / (4 SIMDs x SQ_BUSY_CU_CYCLES)); null when absent
         mfma_busy = None
         try:
@@ -329,7 +371,7 @@ def main():
                             f"{mfma_per_product} fp16-MFMA time(s) per algorithmic product"
                             + (" (x_hi*w_hi on fp16 + the two residual terms on fp8 K=64 MFMAs at twice the rate)" if f8_res else ""),
                     "mfma_executed_frac": round(mfma_per_product * ach / MFMA_F16_PEAK_TFLOPS, 4), "mfma_busy_frac_pmc": mfma_busy,
-                    "pmc_source": "profiles/pmc_traffic.json, profiles/pmc_sq.json (rocprofv3 --pmc passes of `bench.py --timed-only`, reduced by tools/pmc_*.py)",
+                    "pmc_source": "profiles/pmc_traffic.json, profiles/pmc_sq.json (rocprofv3 --pmc passes of `bench.py --full --timed-only`, reduced by tools/pmc_*.py)",
                     "pmc_stale": pmc_stale, "pmc_measured_in_this_run": False}
             if pmc_stale:      # counters of another build say nothing about this one
                 roof["traffic"] = None
@@ -337,7 +379,7 @@ def main():
         breakdown = {k: {"ms": round(v["ms"], 3), "launches": v["launches"],
                          "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1) if v["flops"] else None,
                          "gbps": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1) if v["bytes"] else None}
-                     for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
+                     for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])} if args.full else None
         # ---- the other precision, same inputs, same protocol (N = 1 only): reported, never `value` ----
         modes = {precision: {"images_per_s": round(value, 3), "ms_per_step": round(ms_per_step, 3)}}
         eng_o = None
@@ -423,7 +465,7 @@ def main():
                        "self_attention_keys": "all key tiles" if args.dense_attention else
                        "key tiles whose (1-m)*-10000 bias underflows the fp32 softmax are not loaded (exact; --dense-attention disables)"},
             "parity": parity, "modes": modes, "dense_attention": dense, "every_trimap_tile_multiplied": all_tiles, "no_input_shortcuts": no_short,
-            "launches_per_step": sum(v["launches"] for v in prof.values()), "single_image": b1, "including_host_transfers": incl,
+            "launches_per_step": sum(v["launches"] for v in prof.values()) if args.full else None, "single_image": b1, "including_host_transfers": incl,
             # dense-equivalent algorithmic rate (28.89 TFLOP per 1024^2 image); the self-attention skips the key tiles
             # whose bias underflows the softmax, so the executed attention work depends on the trimap (kernel_breakdown_ms has
             # executed rates per kernel)

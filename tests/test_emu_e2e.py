@@ -444,30 +444,59 @@ def test_emu_rectangular_inference_matches_oracle(pkg):
     eng.close()
 
 
-def test_bench_two_ranks_control_flow(pkg):
-    """`bench.py --gpus 2` has never met a second GPU in the build container: its launcher re-exec, rank / world bookkeeping, weight
-    broadcast, per-step gather, max-over-ranks timing and rank-0 JSON line are exercised here on the kernel emulator over gloo
-    (`--emu`: tiny architecture, 64x64, one step - a control-flow test, not a measurement)."""
+def test_bench_two_ranks_control_flow(pkg, tmp_path):
+    """`bench.py --gpus 2` has never met a second GPU in the build container: its launcher, rank / world bookkeeping, weight
+    broadcast, per-step gather, max-over-ranks timing, rank-0 JSON line and --dump-outputs are exercised here on the kernel emulator
+    over gloo (`--emu`: tiny architecture, 64x64, one step - a control-flow test, not a measurement)."""
     import json
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--emu", "--gpus", "2", "--size", "64", "--batch", "1", "--steps", "1", "--warmup", "0"],
-                       capture_output=True, text=True, timeout=1500, cwd=ROOT)
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--emu", "--gpus", "2", "--size", "64", "--batch", "1", "--steps", "1", "--warmup", "0",
+                        "--dump-outputs", str(tmp_path / "uniform")], capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]              # ONE JSON line, from rank 0
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0 and d["steps"] == 1
+    assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0 and d["steps"] == 1 and d["ms_per_step"] > 0
     assert d["config"]["global_batch"] == 2 and d["config"]["parallelism"] == "dp2"
     assert d["ranks_seen"] == 2 and len(d["per_rank_images_per_s"]) == 2      # the collective really spanned both ranks
-    assert d["cpu_baseline"] is None
-    # the configs[4] leg (--stream): FLOP-balanced buckets per rank, matted_rgba through the node body, one packed message per peer
+    assert d["cpu_baseline"] is None and d["kernel_breakdown_ms"] is None      # a plain run times the steps only
+    # what rank 0 received in the last step: both ranks' alphas (the gather), each from its own seeded inputs
+    a = np.load(tmp_path / "uniform" / "alpha.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 64, 64) and np.isfinite(a).all() and not np.array_equal(a[0], a[1])
+    # the configs[4] leg (--stream): FLOP-balanced buckets per rank, matted_rgba through the node body, one packed message per peer; --full adds
+    # the profiled uniform step
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--emu", "--gpus", "2", "--size", "64", "--batch", "2", "--steps", "1", "--warmup", "0",
-                        "--stream", "--stream-requests", "3"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
+                        "--stream", "--stream-requests", "3", "--full", "--dump-outputs", str(tmp_path / "stream")],
+                       capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0 and "stream" in d["metric"] and "configs[4]" in d["config"]["workload"] and d["ranks_seen"] == 2
+    assert d["kernel_breakdown_ms"] is not None and d["launches_per_step"] is not None      # the profiled step ran (the emulator times no kernels)
+    sizes = [(64, 128, 64)[i % 3] for i in range(6)]
+    for i, s in enumerate(sizes):
+        rgba = np.load(tmp_path / "stream" / f"matted_rgba_{i:03d}.npy")
+        assert rgba.dtype == np.float32 and rgba.shape == (s, s, 4), (i, rgba.shape)
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """Outputs larger than the --dump-outputs budget are written as the same seeded sample of every array on every run (so that two
+    builds can be compared output for output), within the budget in all; outputs within it are written whole."""
+    import numpy as np
+    import bench
+    arrays = {"a": torch.arange(3000, dtype=torch.float32).reshape(30, 100), "b": torch.linspace(0, 1, 1000, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert np.array_equal(np.load(tmp_path / "whole" / "a.npy"), arrays["a"].numpy())
+    assert np.load(tmp_path / "whole" / "b.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    for run in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    got = {k: np.load(tmp_path / "x" / f"{k}.npy") for k in arrays}
+    assert sum(v.nbytes for v in got.values()) <= 4000 and all(v.size > 0 for v in got.values())
+    assert all(np.array_equal(got[k], np.load(tmp_path / "y" / f"{k}.npy")) for k in arrays)
+    assert np.all(np.diff(got["a"]) > 0) and np.isin(got["a"], arrays["a"].numpy()).all()      # sampled elements, in their original order
 
 
 def test_checkpoint_variants_load_to_identical_engines(pkg, tmp_path):

@@ -54,7 +54,7 @@ for (B, h, Lq, Lk) in ((1, 10, 4096, 16384), (1, 10, 1000, 4096 + 37)):
 eng.lib.set_option("attn_nw", 0)
 print("4-wave pipeline bit-identical:", ok4)
 for name, opts in (("plain 8-wave kernel (attn_pipe=0)", ["attn_pipe=0"]), ("8-wave pipeline only (attn_pipe4=0)", ["attn_pipe4=0"]), ("default", [])):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--timed-only", "--steps", "4", "--warmup", "2"] + [x for o in opts for x in ("--opt", o)], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--timed-only", "--steps", "4", "--warmup", "2"] + [x for o in opts for x in ("--opt", o)], capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])
         print(f"{name}: {d['value']} img/s {d['ms_per_step']} ms/step", {k: x["ms"] for k, x in list(d["kernel_breakdown_ms"].items())[:4]}, flush=True)

@@ -69,7 +69,7 @@ eng.lib.set_option("attn_pp", 1)
 eng.close()
 if "--no-step" not in sys.argv:
     for name, opts in (("attn_pp=0 (pipelines)", ["attn_pp=0"]), ("attn_pp=2 (no priority)", ["attn_pp=2"]), ("default (attn_pp=1)", [])):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--timed-only", "--steps", "4", "--warmup", "2"] + [x for o in opts for x in ("--opt", o)], capture_output=True, text=True)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--timed-only", "--steps", "4", "--warmup", "2"] + [x for o in opts for x in ("--opt", o)], capture_output=True, text=True)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])
             print(f"{name}: {d['value']} img/s {d['ms_per_step']} ms/step", {k: x["ms"] for k, x in list(d["kernel_breakdown_ms"].items())[:5]}, flush=True)

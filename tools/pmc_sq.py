@@ -1,4 +1,4 @@
-"""Reduce a rocprofv3 --pmc SQ pass of `bench.py --timed-only` (counters: SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16
+"""Reduce a rocprofv3 --pmc SQ pass of `bench.py --full --timed-only` (counters: SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16
 [SQ_INSTS_VALU_MFMA_MOPS_F8] SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE) to one row per kernel and to the matrix-pipe
 busy fraction of the kernel families `bench.py` reports:
 
@@ -42,7 +42,7 @@ with open(sys.argv[5], "w", newline="") as fh:
 FAM = {"conv3x3": ("conv_mfma_kernel<9",), "gemm": ("conv_mfma_kernel<1", "gemm_p3_kernel"), "attn_d64": ("attn_d64_",), "attn_d512": ("attn_d512_kernel",)}
 out = {"batch_per_gpu": int(sys.argv[2]), "inference_size": int(sys.argv[3]), "precision": sys.argv[4],
        "note": "matrix-pipe busy fraction per kernel family = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x SQ_BUSY_CYCLES / 32), summed over every "
-               "dispatch of the family in a `bench.py --timed-only` run"}
+               "dispatch of the family in a `bench.py --full --timed-only` run"}
 for name, key in FAM.items():
     agg = collections.defaultdict(float)
     n = 0

@@ -1,7 +1,7 @@
 """Reduce rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py` to HBM bytes per launch of the conv3x3 kernel.
 
 usage: python tools/pmc_traffic.py <fetch_counter_collection.csv> <write_counter_collection.csv> <batch> <size> <precision> > profiles/pmc_traffic.json
-(the passes are taken from `bench.py --timed-only`, so every profiled step is the timed workload)
+(the passes are taken from `bench.py --full --timed-only`, so every profiled step is the timed workload)
 FETCH_SIZE / WRITE_SIZE are in KB; on gfx950 FETCH_SIZE reports half of the bytes of wide coalesced reads
 (/opt/skills/guides/MI355X_MICROARCH.md, HBM section) so it is doubled; WRITE_SIZE is taken as is (uncalibrated)."""
 import csv, json, sys, collections

@@ -1,4 +1,4 @@
-"""Reduce a rocprofv3 `--kernel-trace --stats --output-format csv` kernel_stats.csv of `bench.py --timed-only` to the per-family
+"""Reduce a rocprofv3 `--kernel-trace --stats --output-format csv` kernel_stats.csv of `bench.py --full --timed-only` to the per-family
 table the bench line is checked against: every profiled step is the timed workload (warmup + steps + the one HIP-event-profiled
 step), so total / steps / launches-per-step is the average launch duration of a family in the timed region.
 
