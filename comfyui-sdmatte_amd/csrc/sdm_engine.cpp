@@ -124,8 +124,11 @@ static OptEntry g_opts[] = {
   {"attn_pipe4", 1, 1, "the same pipeline for the 4-wave launches (two K / three V^T buffers)"},
   {"attn_pp", 1, 1, "split-precision d=64 attention with fp32 output as a ping-pong of the block's wave halves (attn_d64_pp_kernel, 256 query rows per block): 0 off, 1 on, 2 on without the static priority of the younger half, 3 on with per-segment priority flips"},
   {"attn_pp_min_blocks", 128, 128, "attn_pp: launches with fewer 256-row blocks than this keep the 4-wave pipelines (0 in tests: the ping-pong kernel at any size)"},
-  {"attn_ksplit", 0, 0, "key split of the d=64 split-precision attention: 0 by launch size (blocks that do not fill the chip's block slots a whole number of times), 1 off, 2 / 4 forced"},
+  {"attn_ksplit", 0, 0, "key split of the d=64 split-precision attention: 0 by launch size (blocks that do not fill the chip's block slots a whole number of times), 1 off, 2 / 4 forced, 3 forced on the ping-pong kernel (ignored elsewhere: those launches run unsplit)"},
   {"precise_mask", -1, -1, "stages in split precision (-1 = the config's own mask; per-stage attribution experiments; read at sdm_create)"},
+#ifdef SDM_EMU
+  {"emu_arena_extra", 0, 0, "emulator build only, self-test of the arena check: the launch pass of a stand-alone op allocates one block its sizing pass did not"},
+#endif
 };
 static OptEntry* opt_find(const char* name) {
   for (auto& o : g_opts) if (name && strcmp(o.name, name) == 0) return &o;
@@ -664,6 +667,14 @@ struct sdm_ctx {
   size_t peak = 0;
   std::map<size_t, size_t> freelist;  // off -> size
   size_t arena_top = 0;
+  // dry / launch pass agreement (arena_pass_begin / arena_pass_end): the sizing pass records the size of every talloc in order, the launch pass
+  // compares each of its own with it.  From the first that differs - or would end past arena_bytes - on, allocations get a buffer of their own
+  // outside the arena (`aside`, released at the end of the pass) and the pass fails with SDM_ERR_ARENA naming that first one.
+  std::vector<size_t> atrace;
+  size_t atrace_i = 0;
+  bool adiverged = false;
+  std::string adiv_msg;
+  std::vector<void*> aside;
   // io staging
   void* io_in = nullptr; size_t io_in_bytes = 0;
   void* io_out = nullptr; size_t io_out_bytes = 0;
@@ -952,9 +963,35 @@ static void build_model(sdm_ctx* e) {
 // ------------------------------------------------------------------------------------------------
 // arena
 // ------------------------------------------------------------------------------------------------
+static const size_t kAsideOff = (size_t)1 << 62;      // T::off (and soff / cm_off) of a buffer outside the arena: tfree leaves it alone
+
+static void arena_diverged(sdm_ctx* e, const char* fmt, size_t i, size_t a, size_t b) {
+  if (e->adiverged) return;
+  char buf[256];
+  snprintf(buf, sizeof(buf), fmt, i, a, b);
+  e->adiverged = true; e->adiv_msg = buf;
+}
+
+// launch pass after a divergence: a buffer of its own (the arena is only known to hold what the sizing pass placed in it).  Should even this
+// allocation fail, the null pointer faults the kernel that gets it instead of letting it write past the arena.
+static T talloc_aside(sdm_ctx* e, T t) {
+  void* p = nullptr;
+  if (dev_malloc(&p, t.bytes) != 0) p = nullptr;
+  e->aside.push_back(p);
+  t.off = kAsideOff; t.p = p;
+  return t;
+}
+
 static T talloc(sdm_ctx* e, int N, int H, int W, int C, int f32) {
   T t; t.N = N; t.H = H; t.W = W; t.C = C; t.f32 = f32;
   t.bytes = rupz((f32 == kFmtP3 ? p3_rows_pad((size_t)N * H * W) : (size_t)N * H * W) * C * fmt_bytes(f32), 256);      // (P3 planes are blocked: rows padded to 32)
+  if (e->dry) e->atrace.push_back(t.bytes);
+  else {
+    const size_t i = e->atrace_i++;
+    const size_t want = i < e->atrace.size() ? e->atrace[i] : 0;
+    if (want != t.bytes) arena_diverged(e, "allocation %zu: %zu bytes in the sizing pass, %zu in the launch pass", i, want, t.bytes);
+    if (e->adiverged) return talloc_aside(e, t);
+  }
   // first fit in the free list
   for (auto it = e->freelist.begin(); it != e->freelist.end(); ++it) {
     if (it->second >= t.bytes) {
@@ -965,6 +1002,10 @@ static T talloc(sdm_ctx* e, int N, int H, int W, int C, int f32) {
       t.p = e->dry ? nullptr : e->arena + t.off;
       return t;
     }
+  }
+  if (!e->dry && e->arena_top + t.bytes > e->arena_bytes) {      // the same sizes in the same order, yet past the end (frees that differ)
+    arena_diverged(e, "allocation %zu: ends at byte %zu of an arena of %zu", e->atrace_i - 1, e->arena_top + t.bytes, e->arena_bytes);
+    return talloc_aside(e, t);
   }
   t.off = e->arena_top;
   e->arena_top += t.bytes;
@@ -982,6 +1023,7 @@ static void tfree(sdm_ctx* e, T& t) {
   t.bytes = 0; t.p = nullptr;
 }
 static void tfree_raw(sdm_ctx* e, size_t off, size_t sz) {
+  if (off >= kAsideOff) return;                  // outside the arena: released by arena_pass_end
   auto nx = e->freelist.lower_bound(off);
   if (nx != e->freelist.begin()) {
     auto pv = std::prev(nx);
@@ -998,6 +1040,33 @@ static void tfree_raw(sdm_ctx* e, size_t off, size_t sz) {
 static int tstats(sdm_ctx* e, T& t) { (void)e; t.want_stats = true; return 0; }
 
 static void arena_reset(sdm_ctx* e) { e->freelist.clear(); e->arena_top = 0; }
+
+static void arena_release_aside(sdm_ctx* e) {
+  if (e->aside.empty()) return;
+  dev_sync(e->stream);                           // (kernels of the pass may still use them)
+  for (void* p : e->aside) if (p) dev_free(p);
+  e->aside.clear();
+}
+
+// every two-pass loop (forward, run_two_pass): pass 0 sizes the arena without memory, pass 1 launches in it
+static void arena_pass_begin(sdm_ctx* e, int pass) {
+  arena_release_aside(e);                        // (left behind by a launch pass that ended early)
+  e->dry = (pass == 0);
+  arena_reset(e);
+  if (pass == 0) { e->peak = 0; e->atrace.clear(); }
+  e->atrace_i = 0; e->adiverged = false; e->adiv_msg.clear();
+}
+
+// end of the launch pass (rc: its own status, which takes precedence): an allocation that differed from the sizing pass is an error
+static int arena_pass_end(sdm_ctx* e, int rc) {
+  e->dry = false;
+  arena_release_aside(e);
+  if (rc) return rc;
+  if (!e->adiverged && e->atrace_i != e->atrace.size())
+    arena_diverged(e, "allocation %zu: the sizing pass made %zu allocations, the launch pass %zu", e->atrace_i, e->atrace.size(), e->atrace_i);
+  if (e->adiverged) SDM_FAIL(e, SDM_ERR_ARENA, "activation arena: the launch pass diverged from the sizing pass at %s", e->adiv_msg.c_str());
+  return 0;
+}
 
 // ------------------------------------------------------------------------------------------------
 // profiling helpers
@@ -1312,7 +1381,7 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
     const bool nw8 = pp || (force_nw ? (force_nw == 8) : ((long)B * heads * sdm_cdiv(Lq, 256) >= 1024));
     const long blocks = (long)B * heads * 8 * sdm_cdiv(sdm_cdiv(Lq, nw8 ? 256 : 128), 8), slots = (long)device_cus() * (nw8 ? 1 : 2);
     const int o = opt("attn_ksplit");
-    if (o >= 2) nsplit = (o == 2 || o == 4) ? o : 1;
+    if (o >= 2) nsplit = (o == 2 || o == 4 || (o == 3 && pp)) ? o : 1;
     else if (o == 0) {
       auto rounds = [&](int s) { return (double)((blocks * s + slots - 1) / slots) / s; };
       for (int s = 2; s <= 4; ++s)      // (3: 80 one-per-CU blocks - the 16^2 level's cross-attentions - become 240 of a third of the length)
@@ -1391,6 +1460,7 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
         // attn_d64_pipe_kernel: same arithmetic, bit-identical results, -9 % kernel time); option attn_pipe = 0 selects the plain form.
         const bool pipe8 = opt("attn_pipe") != 0, pipe4 = opt("attn_pipe4") != 0;
         if (pp) { count_kernel("attn_d64_pp"); p.pp_flags = opt("attn_pp") == 1 ? 1 : (opt("attn_pp") == 3 ? 2 : 0); const bool pb = p.bias != nullptr;
+          count_kernel(p.tiles && pb ? "attn_pp<0,1,1>" : (pb ? "attn_pp<0,1,0>" : "attn_pp<0,0,0>"));      // (which specialisation: tests)
           if (p.tiles && pb) { auto kp = attn_d64_pp_kernel<0, 1, 1>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(512), ATTN64PP_SMEM, e->stream, p); }
           else if (pb) { auto kp = attn_d64_pp_kernel<0, 1, 0>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(512), ATTN64PP_SMEM, e->stream, p); }
           else { auto kp = attn_d64_pp_kernel<0, 0, 0>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(512), ATTN64PP_SMEM, e->stream, p); } }
@@ -1410,6 +1480,8 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
       }
       if (nsplit > 1) {
         count_kernel("attn_combine");
+        count_kernel(nsplit == 2 ? "attn_combine/n=2" : (nsplit == 3 ? "attn_combine/n=3" : "attn_combine/n=4"));      // (the split taken: tests)
+        if (ap.out_p3) count_kernel("attn_combine_p3");
         const long nthr = (long)B * Lq * heads * 16;
         if (ap.out_p3)
           SDM_LAUNCH(attn_combine_p3_kernel, dim3((unsigned)((nthr / 2 + 255) / 256)), dim3(256), 0, e->stream, (const float*)part_o.p, (const float*)part_ml.p,
@@ -2044,10 +2116,8 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
   }
   TRY(prepare_variants(e, B, is_trans, cond, cond_dim, cond_kind));
   for (int pass = 0; pass < 2; ++pass) {
-    e->dry = (pass == 0);
-    arena_reset(e);
-    if (pass == 0) e->peak = 0;
-    else if (e->peak > e->arena_bytes) {
+    arena_pass_begin(e, pass);
+    if (pass == 1 && e->peak > e->arena_bytes) {
       if (e->arena) { SDM_CHECK_DEV(e, dev_sync(e->stream)); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
       void* p = nullptr;
       if (dev_malloc(&p, e->peak) != 0) SDM_FAIL(e, SDM_ERR_NOMEM, "cannot allocate %zu bytes of activation arena", e->peak);
@@ -2071,7 +2141,7 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
     }
     T alpha;
     int rc = run_model(e, x16, plane, B, SH, SW, use_mask, &alpha);
-    if (rc) { e->dry = false; return rc; }
+    if (rc) return arena_pass_end(e, rc);
     if (!e->dry) {
       if (mode == 0) {
         SDM_CHECK_DEV(e, dev_memcpy_d2d(d_out, alpha.p, (size_t)B * SH * SW * 4, e->stream));
@@ -2084,6 +2154,7 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
       }
     }
     tfree(e, alpha); tfree(e, plane); tfree(e, x16);
+    if (pass == 1) TRY(arena_pass_end(e, 0));
   }
   e->dry = false;
 #ifndef SDM_EMU
@@ -2108,17 +2179,22 @@ template <typename F>
 static int run_two_pass(sdm_ctx* e, F body) {
   OptReadLock opt_lock;          // (never nested: forward_impl does not come through here)
   for (int pass = 0; pass < 2; ++pass) {
-    e->dry = (pass == 0);
-    arena_reset(e);
-    if (pass == 0) e->peak = 0;
-    else if (e->peak > e->arena_bytes) {
+    arena_pass_begin(e, pass);
+    if (pass == 1 && e->peak > e->arena_bytes) {
       if (e->arena) { dev_sync(e->stream); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
       void* p = nullptr;
       if (dev_malloc(&p, std::max(e->peak, (size_t)1 << 20)) != 0) { e->dry = false; SDM_FAIL(e, SDM_ERR_NOMEM, "arena alloc failed"); }
       e->arena = (unsigned char*)p; e->arena_bytes = std::max(e->peak, (size_t)1 << 20);
     }
+#ifdef SDM_EMU
+    if (pass == 1 && opt("emu_arena_extra")) {      // self-test of the check: one block the sizing pass did not make, ahead of the op's own
+      const size_t b0 = (e->atrace.empty() ? 0 : e->atrace[0]) + 256;
+      (void)talloc(e, 1, 1, 1, (int)(b0 / 4), 1);
+    }
+#endif
     int rc = body();
-    if (rc) { e->dry = false; return rc; }
+    if (rc) { if (e->dry) { e->dry = false; return rc; } return arena_pass_end(e, rc); }
+    if (pass == 1) TRY(arena_pass_end(e, 0));
   }
   e->dry = false;
   SDM_CHECK_DEV(e, dev_sync(e->stream));
@@ -2216,6 +2292,7 @@ void sdm_destroy(sdm_ctx* e) {
   if (e) dev_use(e->device);
   if (!e) return;
   dev_sync(e->stream);
+  arena_release_aside(e);
   if (e->warena) dev_free(e->warena);
   if (e->arena) dev_free(e->arena);
   if (e->stage) dev_free(e->stage);
@@ -3141,15 +3218,13 @@ int sdm_op_attention(sdm_ctx* e, const void* q, int ldq, const void* k, int ldk,
   if (!e || !q || !k || !v || !out) return SDM_ERR_INVALID;
   return run_two_pass(e, [&]() {
     T b2 = talloc(e, B, 1, 1, Lk, 1);
-    const float* bl2 = nullptr;
-    if (bias) {
-      bl2 = (const float*)b2.p;
-      if (!e->dry) {
-        // natural-log bias (reference domain) -> log2 domain used by the kernel
-        SDM_LAUNCH(scale_copy_kernel, dim3(sdm_cdiv(B * Lk, 256)), dim3(256), 0, e->stream, bias, (float*)b2.p, (long)B * Lk, SDM_LOG2E);
-      }
+    // (the sizing pass has no memory but must take the launch pass's branches - op_attention_raw builds a tile list for a bias: a non-null marker)
+    const float* bl2 = !bias ? nullptr : (e->dry ? (const float*)16 : (const float*)b2.p);
+    if (bias && !e->dry) {
+      // natural-log bias (reference domain) -> log2 domain used by the kernel
+      SDM_LAUNCH(scale_copy_kernel, dim3(sdm_cdiv(B * Lk, 256)), dim3(256), 0, e->stream, bias, (float*)b2.p, (long)B * Lk, SDM_LOG2E);
     }
-    int rc = op_attention_raw(e, (const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)v, ldv, bias ? bl2 : nullptr,
+    int rc = op_attention_raw(e, (const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)v, ldv, bl2,
                               B, heads, Lq, Lk, D, (half_t*)out, ldo);
     tfree(e, b2);
     return rc;
@@ -3161,29 +3236,45 @@ int sdm_op_attention(sdm_ctx* e, const void* q, int ldq, const void* k, int ldk,
  * + fp16 lo plane, or + e5m2 pair plane when the Q.K^T residual terms run on fp8 MFMAs - the default; the option attn_f8 = 0 selects the former),
  * with the logit scale d^-1/2 * log2(e) applied to Q as the engine's to_q weights do; fp32 output [B,Lq,heads*64].  Test hook. */
 int sdm_op_attention_split(sdm_ctx* e, const float* q, const float* k, const float* v, const float* bias, int B, int heads, int Lq, int Lk, float* out) {
+  return sdm_op_attention_split_ex(e, q, k, v, bias, nullptr, B, heads, Lq, Lk, 0, out, nullptr);
+}
+
+int sdm_op_attention_split_ex(sdm_ctx* e, const float* q, const float* k, const float* v, const float* bias, const int* tiles, int B, int heads, int Lq,
+                              int Lk, int out_p3, float* out, void* planes) {
   if (e) dev_use(e->device);
   if (!e || !q || !k || !v || !out) return SDM_ERR_INVALID;
+  if (out_p3 < 0 || out_p3 > 2 || (tiles && !bias)) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_attention_split_ex: out_p3 0..2; a tile list needs the bias");
   const int C = heads * 64;
   const int mode = (attn_f8_enabled() && !opt("attn_pv_split")) ? 3 : 2;
-  return run_two_pass(e, [&]() {
+  return run_two_pass(e, [&]() -> int {
     T b2 = talloc(e, B, 1, 1, Lk, 1);
     T qp = talloc(e, B, 1, Lq, C, mode), kp = talloc(e, B, 1, Lk, C, mode), vp = talloc(e, B, 1, Lk, C, mode);
-    const float* bl2 = nullptr;
+    // (the sizing pass has no memory but must take the launch pass's branches - op_attention_raw builds a tile list for a bias: a non-null marker)
+    const float* bl2 = !bias ? nullptr : (e->dry ? (const float*)16 : (const float*)b2.p);
     const long nq = (long)B * Lq * C, nk = (long)B * Lk * C;
     if (!e->dry) {
-      if (bias) {
-        bl2 = (const float*)b2.p;
-        SDM_LAUNCH(scale_copy_kernel, dim3(sdm_cdiv(B * Lk, 256)), dim3(256), 0, e->stream, bias, (float*)b2.p, (long)B * Lk, SDM_LOG2E);
-      }
+      if (bias) SDM_LAUNCH(scale_copy_kernel, dim3(sdm_cdiv(B * Lk, 256)), dim3(256), 0, e->stream, bias, (float*)b2.p, (long)B * Lk, SDM_LOG2E);
       SDM_LAUNCH(split_planes_kernel, dim3((unsigned)((nq / 4 + 255) / 256)), dim3(256), 0, e->stream, q, (half_t*)qp.p, (half_t*)qp.p + nq, nq, 0.125f * SDM_LOG2E, mode);
       SDM_LAUNCH(split_planes_kernel, dim3((unsigned)((nk / 4 + 255) / 256)), dim3(256), 0, e->stream, k, (half_t*)kp.p, (half_t*)kp.p + nk, nk, 1.0f, mode);
       SDM_LAUNCH(split_planes_kernel, dim3((unsigned)((nk / 4 + 255) / 256)), dim3(256), 0, e->stream, v, (half_t*)vp.p, (half_t*)vp.p + nk, nk, 1.0f, 2);
     }
-    AttnPrec ap; ap.prec = mode - 1; ap.q_lo = nq; ap.k_lo = nk; ap.v_lo = nk; ap.out_f32 = 1;
-    int rc = op_attention_raw(e, (const half_t*)qp.p, C, (const half_t*)kp.p, C, (const half_t*)vp.p, C, bias ? bl2 : nullptr, B, heads, Lq, Lk, 64,
-                              out, C, true, nullptr, ap);
+    // out_p3 = 1: the planes written by the kernels (the engine's default); 2: an fp32 result, then to_p3_kernel
+    T to, pl;
+    if (out_p3) to = talloc(e, B, 1, Lq, C, out_p3 == 1 ? kFmtP3 : 1);
+    AttnPrec ap; ap.prec = mode - 1; ap.q_lo = nq; ap.k_lo = nk; ap.v_lo = nk; ap.out_f32 = 1; ap.out_p3 = out_p3 == 1;
+    TRY(op_attention_raw(e, (const half_t*)qp.p, C, (const half_t*)kp.p, C, (const half_t*)vp.p, C, bl2, B, heads, Lq, Lk, 64,
+                         out_p3 ? to.p : (void*)out, C, true, tiles, ap));
+    if (out_p3 == 2) TRY(op_to_p3(e, to, &pl));
+    const T& p3 = out_p3 == 2 ? pl : to;
+    if (out_p3 && !e->dry) {
+      SDM_LAUNCH(from_p3_kernel, dim3((unsigned)std::min<long>(((long)B * Lq * C + 255) / 256, 1 << 20)), dim3(256), 0, e->stream, (const unsigned char*)p3.p, out,
+                 (long)B * Lq, C);
+      if (planes) SDM_CHECK_DEV(e, dev_memcpy_d2d(planes, p3.p, p3_rows_pad((size_t)B * Lq) * C * 3, e->stream));
+    }
+    if (out_p3 == 2) tfree(e, pl);
+    if (out_p3) tfree(e, to);
     tfree(e, vp); tfree(e, kp); tfree(e, qp); tfree(e, b2);
-    return rc;
+    return 0;
   });
 }
 

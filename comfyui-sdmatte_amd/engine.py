@@ -83,7 +83,7 @@ EXPORTS = [
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
-    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_resize_aa",
+    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_op_resize_aa",
     "sdm_op_mask_bias",
     "sdm_set_option", "sdm_get_option", "sdm_reset_options", "sdm_option_name", "sdm_option_help", "sdm_kernel_counts", "sdm_kernel_counts_reset",
 ]
@@ -141,6 +141,7 @@ class Bindings:
             "sdm_op_layernorm": (i32, [vp, vp, i32, C.c_long, i32, vp, vp, f32, vp]),
             "sdm_op_attention": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32]),
             "sdm_op_attention_split": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+            "sdm_op_attention_split_ex": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
             "sdm_op_resize_aa": (i32, [vp, vp, i32, i32, i32, vp, i32, i32]),
             "sdm_op_mask_bias": (i32, [vp, vp, i32, i32, i32, vp]),
             "sdm_set_option": (i32, [C.c_char_p, i32]),
@@ -518,15 +519,25 @@ class Engine:
                                               heads, Lq, Lk, D, _ptr(out), HD), "sdm_op_attention")
         return out
 
-    def op_attention_split(self, q, k, v, heads, bias=None):
+    def op_attention_split(self, q, k, v, heads, bias=None, out_p3=0, tiles=None, planes=False):
         """Split-precision attention cores (head dim 64): q [B,Lq,h*64], k / v [B,Lk,h*64] fp32; the C side splits them into the operand
-        planes the producing GEMM epilogues write in the engine (fp16 high parts + fp8 residual pairs for Q.K^T); fp32 output."""
+        planes the producing GEMM epilogues write in the engine (fp16 high parts + fp8 residual pairs for Q.K^T); fp32 output.
+        Through sdm_op_attention_split_ex when one of these is given: tiles int32 [B, ceil(Lk/64) + 1] = count, then the ascending active
+        64-key tiles of each image (needs the bias); out_p3 1 (True): the kernels write the P3 operand planes the engine's transformer blocks
+        consume, 2: the fp32 result through to_p3_kernel - both decoded to fp32; planes=True (out_p3 != 0): also the raw plane bytes ->
+        (out, uint8 [ceil(B*Lq/32)*32 * h*64 * 3])."""
         B, Lq, HD = q.shape
         Lk = k.shape[1]
         qf, kf, vf = q.float().contiguous(), k.float().contiguous(), v.float().contiguous()
         out = torch.empty(B, Lq, HD, dtype=torch.float32, device=q.device)
-        self._check(self.lib.sdm_op_attention_split(self.h, _ptr(qf), _ptr(kf), _ptr(vf), _ptr(bias), B, heads, Lq, Lk, _ptr(out)), "sdm_op_attention_split")
-        return out
+        if not out_p3 and tiles is None:
+            self._check(self.lib.sdm_op_attention_split(self.h, _ptr(qf), _ptr(kf), _ptr(vf), _ptr(bias), B, heads, Lq, Lk, _ptr(out)), "sdm_op_attention_split")
+            return out
+        tl = tiles.to(torch.int32).contiguous() if tiles is not None else None
+        raw = torch.zeros(((B * Lq + 31) // 32) * 32 * HD * 3, dtype=torch.uint8, device=q.device) if (planes and out_p3) else None
+        self._check(self.lib.sdm_op_attention_split_ex(self.h, _ptr(qf), _ptr(kf), _ptr(vf), _ptr(bias), _ptr(tl), B, heads, Lq, Lk, int(out_p3),
+                                                       _ptr(out), _ptr(raw)), "sdm_op_attention_split_ex")
+        return (out, raw) if raw is not None else out
 
     def op_resize_aa(self, planes, Hout, Wout):
         P, Hin, Win = planes.shape

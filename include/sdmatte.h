@@ -28,7 +28,9 @@ enum sdm_status {
   SDM_ERR_HIP = -2,       /* HIP runtime error */
   SDM_ERR_STATE = -3,     /* weights not loaded / finalised */
   SDM_ERR_NOMEM = -4,
-  SDM_ERR_NODEVICE = -5   /* no gfx950 GPU visible: the product never falls back to the CPU */
+  SDM_ERR_NODEVICE = -5,  /* no gfx950 GPU visible: the product never falls back to the CPU */
+  SDM_ERR_ARENA = -6      /* internal: the launch pass allocated activation memory differently from the pass that sized the arena (the result is
+                             still correct: the diverging allocations were served outside the arena) */
 };
 
 enum sdm_ptr_kind { SDM_PTR_HOST = 0, SDM_PTR_DEVICE = 1 };
@@ -255,6 +257,13 @@ int sdm_op_attention(sdm_ctx* ctx, const void* q, int ldq, const void* k, int ld
  * are split into the operand planes the engine's GEMM epilogues produce (fp16 high parts + e5m2 residual pairs for Q.K^T, fp16 V), the
  * logit scale goes into Q; fp32 output [B,Lq,heads*64].  Test hook for the kernel the engine runs. */
 int sdm_op_attention_split(sdm_ctx* ctx, const float* q, const float* k, const float* v, const float* bias, int B, int heads, int Lq, int Lk, float* out);
+/* The same with the engine's other inputs and outputs.  tiles (needs bias; NULL: built from the bias as above): the active key tiles per image in the
+ * engine's layout, int [B][ceil(Lk/64) + 1] on the device = count, then the ascending 64-key tile indices.  out_p3: 0 fp32 output as above; 1 the
+ * kernels write the P3 operand planes of the GEMM that consumes the result (as the engine's transformer blocks run them; Lq % 32 == 0); 2 the fp32
+ * result converted to P3 by to_p3_kernel (the reference of 1).  With out_p3 != 0 `out` receives the planes decoded to fp32 by from_p3_kernel and, if
+ * planes != NULL, the raw planes (ceil(B*Lq/32)*32 * heads*64 * 3 bytes: fp16 hi plane, then the e5m2 xl plane). */
+int sdm_op_attention_split_ex(sdm_ctx* ctx, const float* q, const float* k, const float* v, const float* bias, const int* tiles, int B, int heads, int Lq,
+                              int Lk, int out_p3, float* out, void* planes);
 /* Antialiased bilinear resize of fp32 planes [P, Hin, Win] -> [P, Hout, Wout] (torchvision Resize). */
 int sdm_op_resize_aa(sdm_ctx* ctx, const float* in, int P, int Hin, int Win, float* out, int Hout, int Wout);
 /* Level-k additive key bias (natural-log domain) from the [-1,1] trimap plane [B,S,S] -> [B,(S/8>>k)^2]. */

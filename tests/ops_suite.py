@@ -373,3 +373,210 @@ def check_gemm_p3(eng, dev, N, H, W, K, O, mode=0, res=False, ln=False, lo_cols=
         assert torch.allclose(st[..., 0], s1, rtol=1e-5, atol=1e-3), f"{what}: statistics (sum)"
         assert torch.allclose(st[..., 1], s2, rtol=1e-5, atol=1e-3), f"{what}: statistics (sum of squares)"
     return err
+
+
+# ---- split-precision d = 64 attention as the engine runs it: kernel choice, key split, tile lists, plane output ------------------------------------
+
+LOG2E = 1.4426950408889634
+
+
+def attn_launch_choice(B, heads, Lq, Lk, cus, pp_min_blocks=128, ksplit=0, nw=0):
+    """Python mirror of op_attention_raw's choice for the split-precision cores with fp32 / plane output (default options: attn_pp = 1, attn_pipe =
+    attn_pipe4 = 1, fp8 residual terms): -> (counter name of the kernel, nsplit).  nw: option attn_nw (4 / 8 force the pipelines)."""
+    cdiv = lambda a, b: -(-a // b)
+    pp = not nw and Lk % 64 == 0 and B * heads * cdiv(Lq, 256) >= pp_min_blocks
+    nw8 = pp or (nw == 8 if nw else B * heads * cdiv(Lq, 256) >= 1024)
+    blocks = B * heads * 8 * cdiv(cdiv(Lq, 256 if nw8 else 128), 8)
+    slots = cus * (1 if nw8 else 2)
+    ntiles = cdiv(Lk, 64)
+    nsplit = 1
+    if ksplit >= 2:
+        nsplit = ksplit if (ksplit in (2, 4) or (ksplit == 3 and pp)) else 1
+    elif ksplit == 0:
+        rounds = lambda s: cdiv(blocks * s, slots) / s
+        for s in (2, 3, 4):
+            if (s != 3 or pp) and ntiles // s >= 32 and rounds(s) < 0.85 * rounds(nsplit):
+                nsplit = s
+    kern = "attn_d64_pp" if pp else ("attn_d64_pipe<8>" if nw8 else "attn_d64_pipe<4>")
+    return kern, nsplit
+
+
+def attn_active_tiles(bias):
+    """The engine's active-key-tile lists (attn_active_tiles_kernel, the layout of its per-level lists) from a natural-log bias [B, Lk]: int32
+    [B, ceil(Lk/64) + 1] = count, then the ascending indices of the 64-key tiles holding a key within SDM_ATTN_SKIP_MARGIN (2000, log2 domain)
+    of the image's largest bias."""
+    B, Lk = bias.shape
+    nt = -(-Lk // 64)
+    b2 = bias.float() * torch.tensor(LOG2E, dtype=torch.float32)
+    lim = b2.max(dim=1).values - 2000.0
+    padded = torch.full((B, nt * 64), -1e30)
+    padded[:, :Lk] = b2
+    act = padded.view(B, nt, 64).max(dim=2).values >= lim[:, None]
+    out = torch.zeros(B, nt + 1, dtype=torch.int32)
+    for b in range(B):
+        idx = act[b].nonzero().flatten()
+        out[b, 0] = idx.numel()
+        out[b, 1:1 + idx.numel()] = idx.to(torch.int32)
+    return out
+
+
+def attn_sample_rows(Lq, n_random=0, seed=0):
+    """Query rows for a row-sampled reference (rows are independent: an exact check of those rows): the first and last row of every 256-row and
+    128-row query block, the whole ragged tail of the last 128-row block (up to 32 rows of it) and n_random seeded others.  n_random < 0: every row."""
+    if n_random < 0:
+        return torch.arange(Lq)
+    rows = set()
+    for blk in (256, 128):
+        for r0 in range(0, Lq, blk):
+            rows.update((r0, min(r0 + blk, Lq) - 1))
+    tail0 = (Lq // 128) * 128
+    if tail0 < Lq:
+        rows.update(range(tail0, min(Lq, tail0 + 32)))
+    if n_random:
+        rows.update(torch.randint(0, Lq, (n_random,), generator=_g(seed)).tolist())
+    return torch.tensor(sorted(rows))
+
+
+def attn_bias(kind, B, Lk, g, nsplit=1):
+    """Key biases (natural log) for the split-attention matrix; every kind puts whole 64-key tiles at -5000 / -10000 so that a tile list leaves them out.
+    blocks: trimap-like (check_attention(blocks=True)) - scattered runs at 0, a different set per image, the last of B > 1 images with no key above
+            -10000 (nothing may be skipped there);
+    allneg: every key at -10000 (the bias cancels: every tile active);
+    onepart: the active keys all inside the first part of an nsplit-way split (the others walk only skipped tiles or none);
+    lastpart: active keys only inside the last part (its rescale decides the result);
+    random: keys kept with probability 1/2, the others at -10000 (no tile is skipped)."""
+    nt = -(-Lk // 64)
+    per = -(-nt // nsplit)
+    if kind == "random":
+        keep = (torch.rand(B, Lk, generator=g) > 0.5).float()
+        keep[:, Lk // 3] = 1.0
+        return (1 - keep) * -10000.0
+    bias = torch.full((B, Lk), -10000.0)
+    if kind == "allneg":
+        return bias
+    bias[:, Lk // 2:] = -5000.0
+    if kind == "blocks":
+        for b in range(B - 1 if B > 1 else B):
+            for t0 in range(64 * (1 + b), Lk, 64 * 5):
+                bias[b, t0 + 7:min(t0 + 40, Lk)] = 0.0
+        if B > 1:
+            bias[B - 1] = -10000.0
+    elif kind == "onepart":
+        for b in range(B):
+            k0 = 64 * min(b, per - 1)
+            bias[b, k0 + 3:min(k0 + 50, Lk)] = 0.0
+    elif kind == "lastpart":
+        t_last = (nsplit - 1) * per if (nsplit - 1) * per < nt else nt - 1
+        for b in range(B):
+            bias[b, 64 * t_last + 5 + b:Lk - 1] = 0.0
+    else:
+        raise ValueError(kind)
+    return bias
+
+
+def attn_reference_rows(q, k, v, heads, bias, rows):
+    """fp64 attention of the un-rounded fp32 q [B,Lq,h*64], k / v [B,Lk,h*64] for the query rows `rows` -> [B, len(rows), h*64] (float64)."""
+    B, _, HD = q.shape
+    Lk = k.shape[1]
+    out = torch.empty(B, len(rows), HD, dtype=torch.float64)
+    for b in range(B):
+        qh = q[b, rows].double().view(len(rows), heads, 64).transpose(0, 1)
+        kh = k[b].double().view(Lk, heads, 64).transpose(0, 1)
+        vh = v[b].double().view(Lk, heads, 64).transpose(0, 1)
+        s = torch.matmul(qh, kh.transpose(1, 2)) * 0.125
+        if bias is not None:
+            s = s + bias[b].double()[None, None, :]
+        out[b] = torch.matmul(s.softmax(-1), vh).transpose(0, 1).reshape(len(rows), HD)
+    return out
+
+
+def check_attention_split_case(eng, dev, set_option, B, heads, Lq, Lk, bias_kind=None, nsplit=None, nw=0, out_p3=False, spike=False, tiles="own",
+                               n_random=-1, atol=None, cus=256, pp_min_blocks=0, seed=0, unsplit_bound=None, what="", stats=None):
+    """One cell of the split-attention matrix (sdm_op_attention_split_ex, the kernels of the default precision) against fp64 attention of the
+    un-rounded fp32 operands on the sampled rows (attn_sample_rows; n_random = -1: every row).  nsplit: option attn_ksplit (None: the engine's
+    automatic choice, mirrored by attn_launch_choice with `cus` compute units); nw: option attn_nw (0 = the ping-pong kernel, 4 / 8 = the pipelines);
+    tiles: "own" the list the operator builds from the bias, "caller" the same list built here (the engine's forward passes its per-level lists).
+    The launch counters must show the kernel, its specialisation and the split.  Besides the fp64 error (returned; < atol):
+      - bias cases: the tile-list walk is bit-identical to the dense walk (option attn_dense = 1: the <0,1,0> form of the ping-pong kernel);
+      - nsplit > 1: within unsplit_bound of the same kernel unsplit (None: 2e-6 where every active key lies in one part, else 5e-4), which
+        meets atol as well;
+      - out_p3: the planes the kernels (or attn_combine_p3_kernel) write are byte-identical to the fp32 result of the same launch put through
+        to_p3_kernel (the fp64 error is then that of the decoded planes)."""
+    g = _g(seed)
+    q = torch.randn(B, Lq, heads * 64, generator=g)
+    k = torch.randn(B, Lk, heads * 64, generator=g)
+    v = torch.randn(B, Lk, heads * 64, generator=g)
+    if spike:       # a large running-max jump on the last key tile (query rows 0 of every image): the combine's rescale across parts matters
+        k[:, Lk - 3] = q[:, 0] * 4.0
+    ns_opt = 0 if nsplit is None else nsplit
+    bias = attn_bias(bias_kind, B, Lk, g, nsplit=max(ns_opt, 1)) if bias_kind else None
+    kern, ns = attn_launch_choice(B, heads, Lq, Lk, cus, pp_min_blocks=pp_min_blocks, ksplit=ns_opt, nw=nw)
+    if nsplit is not None:
+        assert ns == nsplit, f"option attn_ksplit={nsplit} is not taken by {kern} ({what})"
+    set_option(eng, "attn_pp_min_blocks", pp_min_blocks)
+    set_option(eng, "attn_nw", nw)
+    set_option(eng, "attn_ksplit", ns_opt)
+    set_option(eng, "attn_dense", 0)
+    tl = attn_active_tiles(bias).to(dev) if (bias is not None and tiles == "caller") else None
+    qd, kd, vd, bd = q.to(dev), k.to(dev), v.to(dev), bias.to(dev) if bias is not None else None
+    mode = 1 if out_p3 else 0
+    tag = f"{what} B={B} h={heads} Lq={Lq} Lk={Lk} bias={bias_kind} tiles={tiles} nw={nw} nsplit={ns} p3={out_p3} spike={spike}"
+
+    def run(p3=mode, tiles=tl):
+        r = eng.op_attention_split(qd, kd, vd, heads, bias=bd, tiles=tiles, out_p3=p3, planes=bool(p3))
+        return (r[0].cpu(), r[1].cpu()) if p3 else r.cpu()
+
+    eng.lib.kernel_counts(reset=True)
+    got = run()
+    counts = eng.lib.kernel_counts()
+    if out_p3:
+        got, raw = got
+    assert counts.get(kern, 0) == 1 and sum(c for n, c in counts.items() if n.startswith("attn_d64")) == 1, (tag, counts)
+    if stats is not None:
+        stats["counts"] = {n: c for n, c in counts.items() if n.startswith("attn")}
+    if kern == "attn_d64_pp":
+        spec = "attn_pp<0,1,1>" if bias is not None else "attn_pp<0,0,0>"
+        assert counts.get(spec, 0) == 1, (tag, counts)
+    if ns > 1:
+        assert counts.get("attn_combine", 0) == 1 and counts.get(f"attn_combine/n={ns}", 0) == 1, (tag, counts)
+        assert counts.get("attn_combine_p3", 0) == (1 if out_p3 else 0), (tag, counts)
+    else:
+        assert counts.get("attn_combine", 0) == 0, (tag, counts)
+    if out_p3:
+        # the same launch with an fp32 result, then to_p3_kernel: both end in the same p3_store8 rounding
+        ref_dec, ref_raw = run(p3=2)
+        ndiff = (raw != ref_raw).sum().item()
+        assert ndiff == 0 and torch.equal(got, ref_dec), f"{tag}: planes written by the kernels != to_p3_kernel of the fp32 result ({ndiff} bytes differ)"
+    rows = attn_sample_rows(Lq, n_random, seed)
+    ref = attn_reference_rows(q, k, v, heads, bias, rows)
+    err = (got[:, rows].double() - ref).abs().max().item()
+    if bias is not None:
+        set_option(eng, "attn_dense", 1)
+        eng.lib.kernel_counts(reset=True)
+        dense = run(p3=0)
+        if kern == "attn_d64_pp":
+            assert eng.lib.kernel_counts().get("attn_pp<0,1,0>", 0) == 1, tag
+        set_option(eng, "attn_dense", 0)
+        f32 = run(p3=0) if out_p3 else got
+        assert torch.equal(dense, f32), f"{tag}: tile-list walk != dense walk, max|d| = {(dense - f32).abs().max().item():.3g}"
+        if tiles == "caller":       # the list built here is the one the operator builds (the layout of the engine's per-level lists)
+            assert torch.equal(run(p3=0, tiles=None), f32), tag
+    if ns > 1:
+        f32 = dense if bias is not None else (run(p3=0) if out_p3 else got)
+        set_option(eng, "attn_ksplit", 1)
+        whole = run(p3=0)
+        set_option(eng, "attn_ksplit", ns_opt)
+        du = (whole - f32).abs().max().item()
+        err_whole = (whole[:, rows].double() - ref).abs().max().item()
+        if stats is not None:
+            stats.update(unsplit=du, err_unsplit=err_whole)
+        if unsplit_bound is None:
+            # every active key inside one part: the other parts weigh exactly 0 and the walk of that part is the unsplit walk; otherwise the parts
+            # round their probabilities to the fp16 P.V operands against their own running maxima - an error of the size of the fp64 one
+            # (1.6e-4 at most over the emulator matrix, where the fp64 errors are 1.5e-4 .. 1e-3)
+            unsplit_bound = 2e-6 if bias_kind in ("onepart", "lastpart") else 5e-4
+        assert err_whole < (atol if atol is not None else 1.0), f"{tag}: unsplit max|d| vs fp64 = {err_whole:.4g}"
+        assert du <= unsplit_bound, f"{tag}: split vs unsplit max|d| = {du:.3g} > {unsplit_bound:.3g}"
+    if atol is not None:
+        assert err < atol, f"{tag}: max|d| vs fp64 = {err:.4g} >= {atol:.4g}"
+    return err

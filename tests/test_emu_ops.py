@@ -322,6 +322,89 @@ def test_attention_d64_key_split(emu_engine, engine_option):
     assert (outs[1] - outs[4]).abs().max().item() < 2e-6
 
 
+# The split-attention matrix at emulator sizes (ops_suite.check_attention_split_case): every kernel the default precision runs for a transformer
+# block's attention - attn_d64_pp in its three specialisations (<0,1,1> bias + tile list, <0,1,0> the same bias walked densely, <0,0,0> no bias),
+# attn_d64_pipe<8>, attn_d64_pipe<4> - x key split 1 / 2 / 3 (ping-pong only) / 4 x fp32 / P3 output, each case aimed at one index computation:
+# ragged tile division (ntiles % nsplit), parts with no tile at all (ntiles < nsplit), the active keys inside one part, every key at -10000,
+# different tile lists per image, a late spike key in the last part (the combine's rescale), Lq off the 256-row block, heads > 1 (head offsets).
+# Bounds (last column): about 3x the error each case measured on the emulator against the fp64 attention of the un-rounded fp32 operands; the
+# invariants (tile list == dense walk, kernel planes == to_p3_kernel of the fp32 result: bit for bit) hold exactly.
+ATTN_MATRIX_EMU = [
+    # id,                          nw, nsplit, B, h, Lq,  Lk,   bias,       p3,    spike, tiles,    atol (measured here: 1/3 of it)
+    ("pp-ns1-blocks-B2",            0, 1,      2, 2, 200, 640,  "blocks",   False, False, "own",    0.0023),
+    ("pp-ns1-nobias-p3",            0, 1,      1, 2, 288, 256,  None,       True,  False, "own", 0.0007),
+    ("pp-ns2-blocks-B2-p3",         0, 2,      2, 2, 288, 640,  "blocks",   True,  False, "caller", 0.002),
+    ("pp-ns2-nobias-spike",         0, 2,      1, 1, 300, 1024, None,       False, True,  "own", 0.0023),
+    ("pp-ns3-ragged-blocks",        0, 3,      2, 1, 200, 640,  "blocks",   False, False, "caller", 0.0015),
+    ("pp-ns3-allneg-p3",            0, 3,      1, 2, 160, 384,  "allneg",   True,  False, "own", 0.0028),
+    ("pp-ns3-empty-part-nobias-p3", 0, 3,      1, 1, 64,  128,  None,       True,  False, "own", 0.0007),
+    ("pp-ns4-ragged-lastpart-p3",   0, 4,      1, 2, 96,  640,  "lastpart", True,  True,  "caller", 0.0031),
+    ("pp-ns4-empty-part-onepart",   0, 4,      2, 1, 130, 192,  "onepart",  False, False, "own", 0.0013),
+    ("pp-ns4-nobias",               0, 4,      1, 2, 200, 512,  None,       False, False, "own", 0.0011),
+    ("pipe8-ns1-blocks-B2",         8, 1,      2, 1, 200, 640,  "blocks",   False, False, "own", 0.0026),
+    ("pipe8-ns2-nobias-p3",         8, 2,      1, 2, 288, 500,  None,       True,  False, "own", 0.0005),
+    ("pipe8-ns4-lastpart-p3",       8, 4,      1, 1, 96,  640,  "lastpart", True,  True,  "caller", 0.0021),
+    ("pipe4-ns1-nobias-p3",         4, 1,      1, 2, 160, 300,  None,       True,  False, "own", 0.0006),
+    ("pipe4-ns2-blocks-B2",         4, 2,      2, 2, 200, 640,  "blocks",   False, False, "own", 0.0016),
+    ("pipe4-ns4-empty-part",        4, 4,      2, 1, 130, 192,  "onepart",  False, False, "own", 0.0011),
+]
+
+
+@pytest.mark.parametrize("case", ATTN_MATRIX_EMU, ids=[c[0] for c in ATTN_MATRIX_EMU])
+def test_attention_split_matrix(emu_engine, engine_option, case):
+    name, nw, ns, B, h, Lq, Lk, bias, p3, spike, tiles, atol = case
+    st = {}
+    err = S.check_attention_split_case(emu_engine, DEV, engine_option, B, h, Lq, Lk, bias_kind=bias, nsplit=ns, nw=nw, out_p3=p3, spike=spike,
+                                       tiles=tiles, seed=len(name), what=name, stats=st, atol=atol)
+    print(f"[attn matrix] {name}: max|d| vs fp64 = {err:.3g} {st}")
+
+
+def _fresh_engine(emu_engine):
+    from comfyui_sdmatte_amd.engine import Engine
+    from comfyui_sdmatte_amd.config import SDMatteConfig
+    return Engine(SDMatteConfig.tiny(), 0, True, _lib=emu_engine.lib)
+
+
+def test_attention_split_bias_sizes_its_arena(emu_engine):
+    """Regression: sdm_op_attention_split with a key bias on a FRESH engine (its own small arena; the module's engine has grown its arena on larger ops
+    and would hide an overrun).  The sizing pass used to see no bias, so it did not count the tile list op_attention_raw builds for one: the launch
+    pass wrote past the arena (heap damage on the emulator, silent on a GPU).  The arena check now turns such a divergence into SDM_ERR_ARENA; with
+    the sizing pass seeing the bias the call passes.  Lk = 6144 and the automatic key split (2 on the 4-wave pipeline here)."""
+    eng = _fresh_engine(emu_engine)
+    try:
+        emu_engine.lib.kernel_counts(reset=True)
+        err = S.check_attention(eng, DEV, 1, 1, 200, 6144, 64, use_bias=True, split=True, atol=1.3e-4)      # measured 4.2e-5
+        counts = emu_engine.lib.kernel_counts()
+        assert counts.get("attn_d64_pipe<4>", 0) == 1 and counts.get("attn_combine/n=2", 0) == 1, counts
+        assert err > 0
+    finally:
+        eng.close()
+
+
+def test_arena_check_self_test(emu_engine, engine_option):
+    """The check itself (option emu_arena_extra, emulator build only): the launch pass makes one allocation its sizing pass did not make, ahead of the
+    op's own.  The op must return SDM_ERR_ARENA naming allocation 0, serve everything from that point on outside the arena - the result equal to
+    a clean call - and leave the engine (and the process heap) intact for the next call."""
+    import torch
+    from comfyui_sdmatte_amd.engine import _ptr
+    eng = _fresh_engine(emu_engine)
+    try:
+        g = torch.Generator().manual_seed(5)
+        q, k, v = torch.randn(1, 70, 128, generator=g), torch.randn(1, 640, 128, generator=g), torch.randn(1, 640, 128, generator=g)
+        bias = torch.where(torch.rand(1, 640, generator=g) < 0.5, torch.tensor(-10000.0), torch.tensor(0.0))
+        good = eng.op_attention_split(q, k, v, 2, bias)
+        engine_option(eng, "emu_arena_extra", 1)
+        out = torch.full_like(good, float("nan"))
+        rc = eng.lib.sdm_op_attention_split(eng.h, _ptr(q), _ptr(k), _ptr(v), _ptr(bias), 1, 2, 70, 640, _ptr(out))
+        msg = eng.lib.sdm_last_error(eng.h).decode()
+        assert rc == -6 and "diverged from the sizing pass at allocation 0:" in msg, (rc, msg)
+        assert torch.equal(out, good)
+        engine_option(eng, "emu_arena_extra", 0)
+        assert torch.equal(eng.op_attention_split(q, k, v, 2, bias), good)
+    finally:
+        eng.close()
+
+
 def test_attention_d512(emu_engine):
     S.check_attention(emu_engine, DEV, 1, 1, 40, 64, 512, use_bias=False, atol=5e-3)
     S.check_attention(emu_engine, DEV, 1, 1, 33, 50, 512, use_bias=False, atol=5e-3, seed=2)   # ragged last key tile (clamped DMA rows + mask)

@@ -376,3 +376,60 @@ def test_gemm_p3_plane_fed_gemm(eng, engine_option, tile):
 def test_gemm_p3_operand_ranges(eng, xs, ws):
     e = S.check_gemm_p3(eng, DEV, 1, 16, 32, 640, 256, mode=0, seed=11, xscale=xs, wscale=ws, rel=True)
     assert e < 1e-4, (xs, ws, e)
+
+
+# The split-attention matrix of tests/test_emu_ops.py (ops_suite.check_attention_split_case) at medium sizes: the same cells and edges - ragged tile
+# division (65 tiles), parts without tiles (2 / 3 tiles), active keys inside one part, every key at -10000, per-image tile lists, a late spike in the
+# last part, Lq off the 256-row block (P3: a multiple of 32), heads > 1.  Bounds: about 3x the error measured on an MI355X at these sizes (the larger
+# key counts average the fp16 rounding of P.V down: most cells sit well below their emulator bound), max of the split and the unsplit launch.
+ATTN_MATRIX_GPU = [
+    # id,                          nw, nsplit, B, h, Lq,   Lk,   bias,       p3,    spike, tiles,    atol
+    ("pp-ns1-blocks-B2",            0, 1,      2, 2, 2000, 4160, "blocks",   False, False, "own",    0.00032),
+    ("pp-ns1-nobias-p3",            0, 1,      1, 5, 2080, 2048, None,       True,  False, "own",    0.00014),
+    ("pp-ns2-blocks-B2-p3",         0, 2,      2, 2, 2080, 4160, "blocks",   True,  False, "caller", 0.0003),
+    ("pp-ns2-nobias-spike",         0, 2,      1, 1, 3000, 8192, None,       False, True,  "own",    0.002),
+    ("pp-ns3-ragged-blocks",        0, 3,      2, 5, 2000, 4160, "blocks",   False, False, "caller", 0.00037),
+    ("pp-ns3-allneg-p3",            0, 3,      1, 2, 1120, 3072, "allneg",   True,  False, "own",    0.00032),
+    ("pp-ns3-empty-part-nobias-p3", 0, 3,      1, 2, 544,  128,  None,       True,  False, "own",    0.0008),
+    ("pp-ns4-ragged-lastpart-p3",   0, 4,      1, 2, 1056, 4160, "lastpart", True,  True,  "caller", 0.0028),
+    ("pp-ns4-empty-part-onepart",   0, 4,      2, 1, 1300, 192,  "onepart",  False, False, "own",    0.0011),
+    ("pp-ns4-nobias",               0, 4,      1, 2, 2000, 4096, None,       False, False, "own",    0.0001),
+    ("pipe8-ns1-blocks-B2",         8, 1,      2, 1, 2000, 4160, "blocks",   False, False, "own",    0.0003),
+    ("pipe8-ns2-nobias-p3",         8, 2,      1, 2, 2080, 4100, None,       True,  False, "own",    0.0001),
+    ("pipe8-ns4-lastpart-p3",       8, 4,      1, 1, 1056, 4160, "lastpart", True,  True,  "caller", 0.0025),
+    ("pipe4-ns1-nobias-p3",         4, 1,      1, 2, 1120, 3000, None,       True,  False, "own",    0.00014),
+    ("pipe4-ns2-blocks-B2",         4, 2,      2, 2, 2000, 4160, "blocks",   False, False, "own",    0.00032),
+    ("pipe4-ns4-empty-part",        4, 4,      2, 1, 1300, 192,  "onepart",  False, False, "own",    0.001),
+]
+
+
+@pytest.mark.parametrize("case", ATTN_MATRIX_GPU, ids=[c[0] for c in ATTN_MATRIX_GPU])
+def test_attention_split_matrix(eng, engine_option, case):
+    name, nw, ns, B, h, Lq, Lk, bias, p3, spike, tiles, atol = case
+    st = {}
+    err = S.check_attention_split_case(eng, DEV, engine_option, B, h, Lq, Lk, bias_kind=bias, nsplit=ns, nw=nw, out_p3=p3, spike=spike, tiles=tiles,
+                                       n_random=32, seed=len(name), what=name, stats=st, atol=atol)
+    print(f"[attn matrix] {name}: max|d| vs fp64 = {err:.3g} (bound {atol:g}) {st}")
+
+
+# The engine's own attention launches with the AUTOMATIC kernel / key-split choice (default options, attn_pp_min_blocks = 128) and the output the
+# transformer blocks consume (P3 planes), the kernel and nsplit expected from ops_suite.attn_launch_choice - the rule of op_attention_raw - for this
+# device's compute units (on 256 CUs: nsplit 4, 3, 3, 2).  Row-sampled fp64 references; bounds about 3x the error measured on an MI355X.
+ATTN_ENGINE_SHAPES = [
+    # id,                        B, h,  Lq,    Lk,    bias,     atol
+    ("level0-1024-B1-self",      1, 5,  16384, 16384, "blocks", 0.00022),
+    ("level1-1024-B1-cross",     1, 10, 4096,  16384, None,     6e-05),
+    ("level0-768-B4-self",       4, 5,  9216,  9216,  "blocks", 0.00032),
+    ("level1-1024-B4-self",      4, 10, 4096,  4096,  "blocks", 0.00043),
+]
+
+
+@pytest.mark.parametrize("case", ATTN_ENGINE_SHAPES, ids=[c[0] for c in ATTN_ENGINE_SHAPES])
+def test_attention_split_engine_shapes_auto_split(eng, engine_option, case):
+    name, B, h, Lq, Lk, bias, atol = case
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    kern, ns = S.attn_launch_choice(B, h, Lq, Lk, cus)
+    st = {}
+    err = S.check_attention_split_case(eng, DEV, engine_option, B, h, Lq, Lk, bias_kind=bias, nsplit=None, out_p3=True, tiles="caller", n_random=32,
+                                       cus=cus, pp_min_blocks=128, seed=len(name), what=name, stats=st, atol=atol)
+    print(f"[attn engine shapes] {name}: {kern} nsplit={ns} ({cus} CUs) max|d| vs fp64 = {err:.3g} (bound {atol:g}) {st}")
