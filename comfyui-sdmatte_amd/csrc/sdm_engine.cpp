@@ -99,7 +99,6 @@ static OptEntry g_opts[] = {
   {"gemm_p3_tile", 0, 0, "row tile of the plane-fed GEMM: 0 by shape, 256 / 128 / 64 forced"},
   {"gemm_p3_attn", 1, 1, "d=64 attention cores write the operand planes of to_out themselves (0: fp32 result + one conversion pass)"},
   {"gemm_p3_persist", 1, 1, "plane-fed GEMM: persistent blocks that prefetch the next tile's first chunk underneath the epilogue (0: one block per tile, n > 1: a grid of n blocks - tests)"},
-  {"gemm_p3_stages", 0, 0, "LDS stages of the plane-fed GEMM: 0 default, n = lab forms (fp32 / GEGLU epilogues)"},
   {"gemm_p3_ablate", 0, 0, "bench only: 1 no MFMAs, 2 no DMAs behind the prologue, 4 no epilogue (sdm_bench_gemm_p3)"},
   {"conv_epi", 4, 4, "F8 kernels' epilogue: 4 register-direct stores + residual as accumulator init, 3 residual init only, 0 LDS-staged"},
   {"conv_xtile", 1, 1, "F8 3x3: cross-tile prefetch by the producer waves"},
@@ -320,6 +319,14 @@ static int conv_f8_tiles_per_block(long tiles) {
 #endif
 }
 
+// Persistent grid of the F8 kernels (3x3 and 1x1): a block runs tpb of the vgrid tiles back to back.  Sets p.vgrid / p.tpb, returns the blocks to launch.
+static unsigned f8_persistent_grid(ConvParams& p, unsigned vgrid) {
+  p.vgrid = (int)vgrid;
+  p.tpb = conv_f8_tiles_per_block((long)vgrid);
+  const unsigned pg = (vgrid + p.tpb - 1) / p.tpb;
+  return (pg + 7) & ~7u;              // block id % 8 = XCD: the stride between a block's tiles stays a multiple of 8
+}
+
 // 256 px x 128 co, 3x3 stride 1, weights through the LDS-DMA stage ring (k_conv.h, DMAB): fp16 / fp32 activations, optional fused
 // GroupNorm, optional split precision
 static void launch_conv_dma(const ConvParams& p_in, void* stream) {
@@ -348,15 +355,12 @@ static void launch_conv_dma(const ConvParams& p_in, void* stream) {
     SDM_LAUNCH(k, grid, dim3(CD::LAUNCH_THREADS), (size_t)CD::SMEM + gn_extra, stream, p);                   \
   } while (0)
   if (split && p.f8) {          // fp8-residual producer / consumer kernel (32-channel chunks; no GroupNorm table in LDS)
+    using CD = ConvCfg<9, 1, 8, 32, 128, 32, 2, 2, 0, 1, 1, 1, 1>;
+    const unsigned pg = f8_persistent_grid(p, grid.x);
 #define SDM_F8_CASE(GNF)                                                                                     \
   do {                                                                                                       \
-    using CD = ConvCfg<9, 1, 8, 32, 128, 32, 2, 2, 0, 1, 1, 1, 1>;                                           \
     auto k = conv_mfma_kernel<9, 1, 8, 32, 128, 32, 2, 2, 1, 0, GNF, 1, 1, 1, 1>;                            \
     SDM_SET_SMEM(k, 160 * 1024);                                                                             \
-    p.vgrid = (int)grid.x;                                                                                   \
-    p.tpb = conv_f8_tiles_per_block((long)grid.x);                                                           \
-    unsigned pg = (grid.x + p.tpb - 1) / p.tpb;                                                              \
-    pg = (pg + 7) & ~7u;              /* block id % 8 = XCD: the stride between a block's tiles stays a multiple of 8 */ \
     SDM_LAUNCH(k, dim3(pg, 1, 1), dim3(CD::LAUNCH_THREADS), (size_t)CD::SMEM_F8, stream, p);                 /* LDS map: ConvCfg (k_conv.h) */ \
   } while (0)
     count_kernel(gn ? "conv3x3_f8<gn>" : "conv3x3_f8");
@@ -378,11 +382,7 @@ static void launch_gemm_f8(const ConvParams& p_in, void* stream) {
   p.tiles_n = sdm_cdiv(p.Cout_pad, 128);
   const long total_m = (long)p.tiles_m * (p.rows_per_img ? p.N : 1);
   p.xcd_chunk = (int)((total_m + 7) / 8);
-  const unsigned vg = (unsigned)(8L * p.xcd_chunk * p.tiles_n);
-  p.vgrid = (int)vg;
-  p.tpb = conv_f8_tiles_per_block((long)vg);
-  unsigned pg = (vg + p.tpb - 1) / p.tpb;
-  pg = (pg + 7) & ~7u;
+  const unsigned pg = f8_persistent_grid(p, (unsigned)(8L * p.xcd_chunk * p.tiles_n));
   count_kernel("gemm_f8");
   auto k = conv_mfma_kernel<1, 1, 8, 32, 128, 32, 2, 2, 1, 0, 0, 1, 1, 1, 1>;
   SDM_SET_SMEM(k, 160 * 1024);
@@ -390,9 +390,9 @@ static void launch_gemm_f8(const ConvParams& p_in, void* stream) {
 }
 
 // ---- plane-fed GEMM (k_gemm.h): tile = (64 * MT) rows x 128 channels, 4 waves; NS LDS stages (2 stages of the 256-row tile: two blocks per CU) ----
-template <int MT, int EPI, int NS>
+template <int MT, int EPI>
 static void launch_gemm_p3_t(GemmP3Params p, void* stream) {
-  constexpr int BM = 64 * MT, SMEM = NS * (BM * 96 + 128 * 128);
+  constexpr int BM = 64 * MT, NS = 2, SMEM = NS * (BM * 96 + 128 * 128);
   const long rows = p.rows_per_img ? (long)p.rows_per_img : p.M;
   p.tiles_per_img = (int)((rows + BM - 1) / BM);
   p.tiles_m = p.tiles_per_img * (p.rows_per_img ? (int)(p.M / p.rows_per_img) : 1);
@@ -406,7 +406,7 @@ static void launch_gemm_p3_t(GemmP3Params p, void* stream) {
     const unsigned slots = pp > 1 ? (unsigned)pp : ((unsigned)(device_cus() * ((SMEM <= 80 * 1024) ? 2 : 1)) & ~7u);      // (pp > 1: forced grid, tests)
     if (slots >= 1 && grid > slots) grid = slots;
   }
-  auto k = gemm_p3_kernel<MT, 2, EPI, NS>;
+  auto k = gemm_p3_kernel<MT, 2, EPI>;
   SDM_SET_SMEM(k, SMEM);
 #ifndef SDM_EMU
   if (opt("gemm_p3_ablate") & 256) {      // lab: resident blocks per CU as the runtime sees them
@@ -417,21 +417,11 @@ static void launch_gemm_p3_t(GemmP3Params p, void* stream) {
 #endif
   SDM_LAUNCH(k, dim3(grid, 1, 1), dim3(256), (size_t)SMEM, stream, p);
 }
-// LDS stages per row tile: the option gemm_p3_stages = 0 takes the default of the tile, n >= 2 asks for n (lab forms exist for the fp32 and GEGLU epilogues)
 template <int EPI>
 static void launch_gemm_p3_e(const GemmP3Params& p, int bm, void* stream) {
-  const int ns = opt("gemm_p3_stages");
-  if (EPI == 0 || EPI == 1) {
-    if (bm == 256 && ns == 3) return launch_gemm_p3_t<4, EPI, 3>(p, stream);
-    if (bm == 256 && ns == 4) return launch_gemm_p3_t<4, EPI, 4>(p, stream);
-    if (bm == 128 && ns == 4) return launch_gemm_p3_t<2, EPI, 4>(p, stream);
-    if (bm == 128 && ns == 5) return launch_gemm_p3_t<2, EPI, 5>(p, stream);
-    if (bm == 64 && ns == 4) return launch_gemm_p3_t<1, EPI, 4>(p, stream);
-    if (bm == 64 && ns == 7) return launch_gemm_p3_t<1, EPI, 7>(p, stream);
-  }
-  if (bm == 256) launch_gemm_p3_t<4, EPI, 2>(p, stream);
-  else if (bm == 128) launch_gemm_p3_t<2, EPI, 2>(p, stream);
-  else launch_gemm_p3_t<1, EPI, 2>(p, stream);
+  if (bm == 256) launch_gemm_p3_t<4, EPI>(p, stream);
+  else if (bm == 128) launch_gemm_p3_t<2, EPI>(p, stream);
+  else launch_gemm_p3_t<1, EPI>(p, stream);
 }
 // row tile: the largest of 256 / 128 / 64 that still gives every CU a block (the option gemm_p3_tile forces one)
 static int gemm_p3_pick_bm(long M, int N, int rows_per_img) {
@@ -1103,17 +1093,26 @@ struct ConvArgs {
   const float* gn_scale = nullptr; const float* gn_shift = nullptr; int gn_silu = 0;   // fused GroupNorm apply (tile cfg 0 only)
 };
 
+// The shape part of ConvParams - all that conv_pick_cfg and conv_cfg_ok read.  op_conv and the fuse test of gn_conv both fill it here, so the tile
+// gn_conv asks about is the tile op_conv would pick.
+static void conv_shape_params(ConvParams& p, const ConvL& L, const T& in0, const T* in1, const T& out, int stride) {
+  p.C0 = in0.C; p.C1 = in1 ? in1->C : 0; p.in_f32 = in0.f32;
+  p.N = in0.N; p.Hin = in0.H; p.Win = in0.W;
+  p.Hout = out.H; p.Wout = out.W;
+  p.M = out.rows();
+  p.Cout_pad = L.Cout_pad;
+  p.f8_hint = (L.f8 && L.w_dma && p.in_f32 && L.ntaps == 9 && stride == 1) ? 1 : 0;
+}
+
 static int op_conv(sdm_ctx* e, const ConvL& L, const ConvArgs& a) {
   ConvParams p;
   memset(&p, 0, sizeof(p));
-  p.in0 = a.in0->p; p.C0 = a.in0->C; p.in_f32 = a.in0->f32;
-  if (a.in1) { p.in1 = a.in1->p; p.C1 = a.in1->C; }
-  p.N = a.in0->N; p.Hin = a.in0->H; p.Win = a.in0->W; p.up = a.up;
-  p.Hout = a.out->H; p.Wout = a.out->W;
+  conv_shape_params(p, L, *a.in0, a.in1, *a.out, a.stride);
+  p.in0 = a.in0->p;
+  if (a.in1) p.in1 = a.in1->p;
+  p.up = a.up;
   p.pad_t = p.pad_l = (a.pad_mode == 0) ? 1 : 0;
-  p.M = a.out->rows();
   p.w = L.w; p.bias = a.bias_override ? a.bias_override : L.b; p.bias_sel = a.bias_sel;
-  p.Cout_pad = L.Cout_pad;
   p.out = a.out->p; p.out_f32 = a.out->f32; p.Cout_store = a.out->C;
   p.out_lo_off = (size_t)a.out->rows() * a.out->C;
   p.lo_cols = a.lo_cols >= 0 ? a.lo_cols : (1 << 30);
@@ -1142,7 +1141,6 @@ static int op_conv(sdm_ctx* e, const ConvL& L, const ConvArgs& a) {
   }
   if (p.C0 + p.C1 != L.Cin_pad) SDM_FAIL(e, SDM_ERR_INVALID, "conv %s: input channels %d+%d != %d", L.name.c_str(), p.C0, p.C1, L.Cin_pad);
   if (a.in1 && a.in1->f32 != a.in0->f32) SDM_FAIL(e, SDM_ERR_INVALID, "conv %s: concat sources differ in dtype", L.name.c_str());
-  p.f8_hint = (L.f8 && L.w_dma && p.in_f32 && L.ntaps == 9 && a.stride == 1) ? 1 : 0;
   int cfg = a.force_cfg >= 0 ? a.force_cfg : conv_pick_cfg(L.ntaps, a.stride, p);
   if (cfg < 0 || cfg >= conv_num_cfgs(L.ntaps, a.stride) || !conv_cfg_ok(conv_cfg_table(L.ntaps, a.stride)[cfg], p))
     SDM_FAIL(e, SDM_ERR_INVALID, "conv %s: no tile configuration for Cin=%d+%d (cfg %d)", L.name.c_str(), p.C0, p.C1, cfg);
@@ -1252,6 +1250,19 @@ static int op_conv(sdm_ctx* e, const ConvL& L, const ConvArgs& a) {
   return 0;
 }
 
+// Launch geometry of gn_stats_kernel and gn_apply_kernel (k_norm.h): a thread owns 8 channels, `slots` pixels run side by side in a block, a block walks
+// ppb pixels of one image (a multiple of slots), nb blocks per image.
+struct GnGeometry { int threads, ppb, nb, slots; };
+static GnGeometry gn_geometry(int C, int N, int HW) {
+  GnGeometry g;
+  const int CV = C / 8;
+  g.slots = std::max(1, 256 / CV);
+  g.threads = rup(CV * g.slots, 64);
+  g.ppb = rup(std::max(g.slots * 8, sdm_cdiv(HW, 2048 / std::max(1, N))), g.slots);
+  g.nb = sdm_cdiv(HW, g.ppb);
+  return g;
+}
+
 // GroupNorm statistics -> per-(image, channel) scale = rstd*gamma and shift = beta - mean*rstd*gamma.
 // scratch layout: [N][max(groups,C)][2] doubles (sums) | scale [N][C] floats | shift [N][C] floats.  The caller frees `scratch`.
 static int gn_scale_shift(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1, int in_f32, int N, int HW, int groups, const float* gamma,
@@ -1274,15 +1285,10 @@ static int gn_scale_shift(sdm_ctx* e, const void* in0, const void* in1, int C0, 
     prof_end(e);
   } else {
     GnSrc s; s.in0 = in0; s.in1 = in1; s.C0 = C0; s.C1 = C1; s.in_f32 = in_f32; s.HW = HW;
-    const int CV = C / 8;
-    const int slots = std::max(1, 256 / CV);
-    const int threads = rup(CV * slots, 64);
-    int ppb = std::max(slots * 8, sdm_cdiv(HW, 2048 / std::max(1, N)));
-    ppb = rup(ppb, slots);
-    const int nb = sdm_cdiv(HW, ppb);
+    const GnGeometry g = gn_geometry(C, N, HW);
     SDM_CHECK_DEV(e, dev_memset(sums, 0, (size_t)N * groups * 16, e->stream));
     prof_begin(e, "gn_stats", 0, (double)N * HW * C * (in_f32 ? 4 : 2));
-    SDM_LAUNCH(gn_stats_kernel, dim3(nb, N), dim3(threads), (size_t)2 * C * 4, e->stream, s, sums, groups, ppb);
+    SDM_LAUNCH(gn_stats_kernel, dim3(g.nb, N), dim3(g.threads), (size_t)2 * C * 4, e->stream, s, sums, groups, g.ppb);
     prof_end(e);
     SDM_LAUNCH(gn_finalize_kernel, dim3(sdm_cdiv(N * C, 256)), dim3(256), 0, e->stream, (const double*)sums, gamma, beta, scale, shift, N, C,
                groups, (long)HW * (C / groups), eps);
@@ -1298,18 +1304,13 @@ static int op_groupnorm_raw(sdm_ctx* e, const void* in0, const void* in1, int C0
   TRY(gn_scale_shift(e, in0, in1, C0, C1, in_f32, N, HW, groups, gamma, beta, eps, st0, rows0, st1, rows1, have_stats, &scratch, &scale, &shift));
   if (!e->dry) {
     GnSrc s; s.in0 = in0; s.in1 = in1; s.C0 = C0; s.C1 = C1; s.in_f32 = in_f32; s.HW = HW;
-    const int CV = C / 8;
-    const int slots = std::max(1, 256 / CV);
-    const int threads = rup(CV * slots, 64);
-    int ppb = std::max(slots * 8, sdm_cdiv(HW, 2048 / std::max(1, N)));
-    ppb = rup(ppb, slots);
-    const int nb = sdm_cdiv(HW, ppb);
+    const GnGeometry g = gn_geometry(C, N, HW);
     prof_begin(e, "gn_apply", 0, (double)N * HW * C * (in_f32 ? 4 : 2) + (double)N * HW * C * (double)fmt_bytes(out_f32));
     if (out_f32 == kFmtP3)
       SDM_LAUNCH(gn_apply_p3_kernel, dim3((unsigned)(((long)N * HW + 15) / 16)), dim3(256), 0, e->stream, s, (const float*)scale, (const float*)shift, (unsigned char*)out,
                  silu, (long)N * HW);
     else
-    SDM_LAUNCH(gn_apply_kernel, dim3(nb, N), dim3(threads), 0, e->stream, s, (const float*)scale, (const float*)shift, out, out_f32, silu, ppb);
+    SDM_LAUNCH(gn_apply_kernel, dim3(g.nb, N), dim3(g.threads), 0, e->stream, s, (const float*)scale, (const float*)shift, out, out_f32, silu, g.ppb);
     prof_end(e);
   }
   tfree(e, scratch);
@@ -1349,7 +1350,109 @@ static int op_ln(sdm_ctx* e, const NormL& n, const T& x, float eps, T* out, int 
 // Precise variant (d = 64): q / k / v point at the HIGH planes of split fp16 pairs, the low planes follow at element offsets
 // q_lo / k_lo / v_lo (written by the producing GEMM with out_f32 == 2); `out` is fp16 or fp32 (out_f32).
 // prec: 0 fp16 operands; 1 q / k / v as fp16 planes hi | lo; 2 q / k as fp16 plane + e5m2 pair plane (ConvParams::out_f32 == 3), v hi only
-struct AttnPrec { int prec = 0; long q_lo = 0, k_lo = 0, v_lo = 0; int out_f32 = 0; int out_p3 = 0; };      // out_p3 (with out_f32 = 1): `out` is a P3 tensor (k_gemm.h)
+// has_bias / has_tiles: whether a key bias / a caller's tile list comes with the call.  Stated by the caller, never read off bias_l2 / tiles: those
+// pointers exist only outside the dry pass, and the launch plan must be the same in both passes.
+struct AttnPrec { int prec = 0; long q_lo = 0, k_lo = 0, v_lo = 0; int out_f32 = 0; int out_p3 = 0; bool has_bias = false, has_tiles = false; };      // out_p3 (with out_f32 = 1): `out` is a P3 tensor (k_gemm.h)
+
+// Everything op_attention_raw decides about a launch, decided once: the sizing pass allocates from it, the launch pass launches from it.
+enum AttnKernel { kAttnPP, kAttnPPBias, kAttnPPTiles, kAttnPipe8, kAttnPipe4, kAttnP3W8, kAttnP3W4, kAttnP1W8, kAttnP1W4, kAttnP2W8, kAttnP2W4,
+                  kAttnF16W8, kAttnF16W4, kAttnD512 };
+struct AttnPlan {
+  AttnKernel kernel;              // row of kAttnKernels: launch counter (d = 64 launches are counted), block size, dynamic LDS
+  const char* spec_counter;       // ping-pong kernel: the specialisation taken (tests); otherwise null
+  const char* combine_counter;    // nsplit > 1: the split taken (tests); otherwise null
+  int qrows;                      // query rows per block
+  unsigned nblk;                  // grid.x: 1-D, XCD-aware mapping in the kernel
+  int nsplit;                     // key split (k_attn.h AttnParams::nsplit) = grid.y; 1: unsplit
+  bool walk_tiles, own_list;      // the kernel walks a list of active key tiles; the operator builds that list itself
+  bool pv_split;                  // residual terms of P.V too: V^T_lo is needed as well
+  int pp_flags;
+};
+struct AttnKernelInfo { const char* counter; int threads; size_t smem; void (*launch)(const AttnKernelInfo&, const AttnPlan&, const AttnParams&, void*); };
+template <auto K, int LDS_LIMIT = 160 * 1024>      // LDS_LIMIT: the dynamic-LDS limit the kernel is given (0: the default limit holds its LDS)
+static void attn_launch_t(const AttnKernelInfo& ki, const AttnPlan& pl, const AttnParams& p, void* stream) {
+  if constexpr (LDS_LIMIT > 0) SDM_SET_SMEM(K, LDS_LIMIT);
+  SDM_LAUNCH(K, dim3(pl.nblk, (unsigned)pl.nsplit, 1), dim3(ki.threads), ki.smem, stream, p);
+}
+static const AttnKernelInfo kAttnKernels[] = {      // indexed by AttnKernel
+  {"attn_d64_pp", 512, ATTN64PP_SMEM, attn_launch_t<attn_d64_pp_kernel<0, 0, 0>>},
+  {"attn_d64_pp", 512, ATTN64PP_SMEM, attn_launch_t<attn_d64_pp_kernel<0, 1, 0>>},
+  {"attn_d64_pp", 512, ATTN64PP_SMEM, attn_launch_t<attn_d64_pp_kernel<0, 1, 1>>},
+  {"attn_d64_pipe<8>", 512, ATTN64PIPE_SMEM, attn_launch_t<attn_d64_pipe_kernel<8>>},
+  {"attn_d64_pipe<4>", 256, ATTN64PIPE4_SMEM, attn_launch_t<attn_d64_pipe_kernel<4>>},
+  {"attn_d64<prec3,8>", 512, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 3, 8>>},
+  {"attn_d64<prec3,4>", 256, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 3, 4>>},
+  {"attn_d64<prec1,8>", 512, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 1, 8>>},
+  {"attn_d64<prec1,4>", 256, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 1, 4>>},
+  {"attn_d64<prec2,8>", 512, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 2, 8>>},
+  {"attn_d64<prec2,4>", 256, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 2, 4>>},
+  {"attn_d64<fp16,8>", 512, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 0, 8>>},
+  {"attn_d64<fp16,4>", 256, ATTN64_SMEM, attn_launch_t<attn_d64_kernel<1, 0, 4>, 0>},
+  {"attn_d512", 512, ATTN512P_SMEM, attn_launch_t<attn_d512_kernel<0>, ATTN512P_SMEM>},
+};
+// Pure: shapes, flags, the options and the CU count in, the plan out.
+static AttnPlan attn_plan(int B, int heads, int Lq, int Lk, int D, int prec, int out_f32, bool has_bias, bool has_tiles, int cus) {
+  AttnPlan pl;
+  memset(&pl, 0, sizeof(pl));
+  pl.nsplit = 1;
+  bool nw8 = true, pp = false;      // (d = 512: one 8-wave kernel, 128 query rows per block)
+  if (D != 64) {
+    pl.kernel = kAttnD512; pl.qrows = 128;
+  } else {
+    // key tiles whose bias underflows the softmax are skipped (exact, AttnParams::tiles); the engine passes one list per U-Net
+    // level, the stand-alone operator entry builds it here.  The option attn_dense = 1 walks every tile (A/B hook).
+    pl.walk_tiles = has_bias && opt("attn_dense") == 0;
+    pl.own_list = pl.walk_tiles && !has_tiles;
+    // split-precision variant: Q.K^T on split operands, P.V on plain fp16 (k_attn.h, PREC = 2) unless the option attn_pv_split asks for
+    // the residual terms of P.V too (PREC = 1)
+    pl.pv_split = prec == 1 && opt("attn_pv_split") != 0;
+    // 8-wave blocks (256 queries share every K / V^T tile: half the L2 / Infinity-Cache traffic and LDS staging per MFMA) only
+    // where they measured faster: the split-precision variant with >= 4 such blocks per CU (B=4 h=5 L=16384: 4.01 vs 4.25 ms;
+    // h=10 Lq=4096: 2.39 vs 2.24 ms, i.e. slower; the fp16 variant is neutral to -10 %) - profiles/r02_ablate_attn_nw8.txt
+    const int force_nw = opt("attn_nw");                          // A/B / test option: 4 or 8
+    const long blocks256 = (long)B * heads * sdm_cdiv(Lq, 256);
+    // ping-pong kernel: always 256-row blocks, one per CU; launches of fewer than 128 such blocks (the 16^2 level: 80) keep the 4-wave pipelines, whose 128-row
+    // blocks spread over twice as many CUs (measured 0.63 vs 0.79 ms at B = 4, profiles/r06_attn_pp_lab.txt)
+    pp = prec == 2 && out_f32 && opt("attn_pp") != 0 && !force_nw && Lk % 64 == 0 &&      // (LDS-DMA tiles: no masked tail rows)
+         blocks256 >= opt("attn_pp_min_blocks");
+    nw8 = pp || (force_nw ? (force_nw == 8) : (prec && blocks256 >= 1024));
+    pl.qrows = nw8 ? 256 : 128;
+    if (prec == 2) {
+      // 8-wave blocks with fp32 output (the engine's level-0 attentions): the two-tile software pipeline of the kernel (k_attn.h,
+      // attn_d64_pipe_kernel: same arithmetic, bit-identical results, -9 % kernel time); option attn_pipe = 0 selects the plain form.
+      const bool pipe = out_f32 && opt(nw8 ? "attn_pipe" : "attn_pipe4") != 0;
+      if (pp) pl.kernel = pl.walk_tiles ? kAttnPPTiles : (has_bias ? kAttnPPBias : kAttnPP);
+      else if (pipe) pl.kernel = nw8 ? kAttnPipe8 : kAttnPipe4;
+      else pl.kernel = nw8 ? kAttnP3W8 : kAttnP3W4;
+    } else if (prec) {
+      pl.kernel = pl.pv_split ? (nw8 ? kAttnP1W8 : kAttnP1W4) : (nw8 ? kAttnP2W8 : kAttnP2W4);
+    } else {
+      pl.kernel = nw8 ? kAttnF16W8 : kAttnF16W4;
+    }
+    if (pp) {
+      pl.spec_counter = pl.walk_tiles ? "attn_pp<0,1,1>" : (has_bias ? "attn_pp<0,1,0>" : "attn_pp<0,0,0>");
+      pl.pp_flags = opt("attn_pp") == 1 ? 1 : (opt("attn_pp") == 3 ? 2 : 0);
+    }
+  }
+  pl.nblk = (unsigned)(B * heads * 8 * sdm_cdiv(sdm_cdiv(Lq, pl.qrows), 8));      // B * heads * 8 units: always a multiple of 8
+  // Key split (split-precision d = 64 with fp32 output only).  A launch whose blocks fill the chip's block slots 1.25 times
+  // takes as long as one that fills them twice; walking half (a quarter) of the keys per block and combining the partial sums afterwards turns
+  // that into 2.5 (5) rounds of half (quarter) length.  Chosen by block count alone - the same for the dense and the tile-list walk, whose ranges are key
+  // ranges - and only for long walks (>= 32 tiles per part).  One image at 1024^2: 640 four-wave blocks on 512 slots at the first U-Net level.
+  if (D == 64 && prec && out_f32 && !pl.pv_split) {
+    const long blocks = pl.nblk, slots = (long)cus * (nw8 ? 1 : 2);
+    const int o = opt("attn_ksplit"), ntiles64 = sdm_cdiv(Lk, 64);
+    if (o >= 2) pl.nsplit = (o == 2 || o == 4 || (o == 3 && pp)) ? o : 1;
+    else if (o == 0) {
+      auto rounds = [&](int s) { return (double)((blocks * s + slots - 1) / slots) / s; };
+      for (int s = 2; s <= 4; ++s)      // (3: 80 one-per-CU blocks - the 16^2 level's cross-attentions - become 240 of a third of the length)
+        if ((s != 3 || pp) && ntiles64 / s >= 32 && rounds(s) < 0.85 * rounds(pl.nsplit)) pl.nsplit = s;
+    }
+    if (pl.nsplit > 1) pl.combine_counter = pl.nsplit == 2 ? "attn_combine/n=2" : (pl.nsplit == 3 ? "attn_combine/n=3" : "attn_combine/n=4");
+  }
+  return pl;
+}
+
 static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* k, int ldk, const half_t* v, int ldv, const float* bias_l2,
                             int B, int heads, int Lq, int Lk, int D, void* out, int ldo, bool q_prescaled = false, const int* tiles = nullptr,
                             AttnPrec ap = AttnPrec()) {
@@ -1358,54 +1461,31 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
   if (ap.prec && D != 64) SDM_FAIL(e, SDM_ERR_INVALID, "attention: the split-precision variant exists for head dim 64 only");
   // the fp8-pair form cannot rescale Q inside the kernel (its pair plane is produced pre-scaled, as the engine always does)
   if (ap.prec == 2 && !q_prescaled) SDM_FAIL(e, SDM_ERR_INVALID, "attention: the fp8-residual form takes pre-scaled queries");
+  if (!e->dry && (ap.has_bias != (bias_l2 != nullptr) || ap.has_tiles != (tiles != nullptr)))
+    SDM_FAIL(e, SDM_ERR_STATE, "attention: bias / tile list do not match what the sizing pass was told");
+  const AttnPlan pl = attn_plan(B, heads, Lq, Lk, D, ap.prec, ap.out_f32, ap.has_bias, ap.has_tiles, device_cus());
+  const AttnKernelInfo& ki = kAttnKernels[pl.kernel];
+  const int nsplit = pl.nsplit;
   const int ldvt = rup(Lk, 64);
   T vt = talloc(e, (ap.prec ? 2 : 1) * B, heads, D, ldvt, 0);      // precise: V^T_hi planes of all images, then V^T_lo
-  // key tiles whose bias underflows the softmax are skipped (exact, AttnParams::tiles); the engine passes one list per U-Net
-  // level, the stand-alone operator entry builds it here.  The option attn_dense = 1 walks every tile (A/B hook).
-  const bool dense_attn = opt("attn_dense") != 0;
   const int ntiles64 = sdm_cdiv(Lk, 64);
-  T tl_own;
-  const bool own_list = (D == 64) && bias_l2 && !tiles && !dense_attn;
-  if (own_list) tl_own = talloc(e, B, 1, 1, ntiles64 + 1, 1);
-  // Key split (k_attn.h AttnParams::nsplit; split-precision d = 64 with fp32 output only).  A launch whose blocks fill the chip's block slots 1.25 times
-  // takes as long as one that fills them twice; walking half (a quarter) of the keys per block and combining the partial sums afterwards turns
-  // that into 2.5 (5) rounds of half (quarter) length.  Chosen by block count alone - the same for the dense and the tile-list walk, whose ranges are key
-  // ranges - and only for long walks (>= 32 tiles per part).  One image at 1024^2: 640 four-wave blocks on 512 slots at the first U-Net level.
-  int nsplit = 1;
-  T part_o, part_ml;
-  if (D == 64 && ap.prec && ap.out_f32 && !(ap.prec == 1 && opt("attn_pv_split"))) {
-    const int force_nw = opt("attn_nw");
-    // ping-pong kernel: always 256-row blocks, one per CU; launches of fewer than 128 such blocks (the 16^2 level: 80) keep the 4-wave pipelines, whose 128-row
-    // blocks spread over twice as many CUs (measured 0.63 vs 0.79 ms at B = 4, profiles/r06_attn_pp_lab.txt)
-    const bool pp = ap.prec == 2 && opt("attn_pp") != 0 && !force_nw && Lk % 64 == 0 && (long)B * heads * sdm_cdiv(Lq, 256) >= opt("attn_pp_min_blocks");
-    const bool nw8 = pp || (force_nw ? (force_nw == 8) : ((long)B * heads * sdm_cdiv(Lq, 256) >= 1024));
-    const long blocks = (long)B * heads * 8 * sdm_cdiv(sdm_cdiv(Lq, nw8 ? 256 : 128), 8), slots = (long)device_cus() * (nw8 ? 1 : 2);
-    const int o = opt("attn_ksplit");
-    if (o >= 2) nsplit = (o == 2 || o == 4 || (o == 3 && pp)) ? o : 1;
-    else if (o == 0) {
-      auto rounds = [&](int s) { return (double)((blocks * s + slots - 1) / slots) / s; };
-      for (int s = 2; s <= 4; ++s)      // (3: 80 one-per-CU blocks - the 16^2 level's cross-attentions - become 240 of a third of the length)
-        if ((s != 3 || pp) && ntiles64 / s >= 32 && rounds(s) < 0.85 * rounds(nsplit)) nsplit = s;
-    }
-    if (nsplit > 1) {
-      part_o = talloc(e, nsplit * B, Lq, 1, ldo, 1);
-      part_ml = talloc(e, nsplit * B, heads, Lq, 2, 1);
-    }
+  T tl_own, part_o, part_ml;
+  if (pl.own_list) tl_own = talloc(e, B, 1, 1, ntiles64 + 1, 1);
+  if (nsplit > 1) {
+    part_o = talloc(e, nsplit * B, Lq, 1, ldo, 1);
+    part_ml = talloc(e, nsplit * B, heads, Lq, 2, 1);
   }
   if (!e->dry) {
-    if (own_list) {
+    if (pl.own_list) {
       SDM_LAUNCH(attn_active_tiles_kernel, dim3(B), dim3(256), 0, e->stream, bias_l2, Lk, ntiles64, (int*)tl_own.p, ntiles64 + 1, SDM_ATTN_SKIP_MARGIN);
       tiles = (const int*)tl_own.p;
     }
-    if (dense_attn || D != 64 || !bias_l2) tiles = nullptr;
+    if (!pl.walk_tiles) tiles = nullptr;
     const long vt_hs = (long)D * ldvt, vt_bs = (long)heads * vt_hs;
     prof_begin(e, "transpose_v", 0, (double)B * Lk * heads * D * 4);
     SDM_LAUNCH(transpose_v_kernel, dim3(ldvt / 64, heads * (D / 64), B), dim3(256), 0, e->stream, v, (long)Lk * ldv, ldv, (half_t*)vt.p, vt_bs,
                vt_hs, ldvt, Lk, D);
-    // split-precision variant: Q.K^T on split operands, P.V on plain fp16 (k_attn.h, PREC = 2) unless SDM_ATTN_PV_SPLIT=1 asks for
-    // the residual terms of P.V too (PREC = 1: then V^T_lo is needed as well)
-    const bool pv_split = ap.prec == 1 && opt("attn_pv_split") != 0;
-    if (pv_split)
+    if (pl.pv_split)
       SDM_LAUNCH(transpose_v_kernel, dim3(ldvt / 64, heads * (D / 64), B), dim3(256), 0, e->stream, v + ap.v_lo, (long)Lk * ldv, ldv,
                  (half_t*)vt.p + (size_t)B * vt_bs, vt_bs, vt_hs, ldvt, Lk, D);
     prof_end(e);
@@ -1425,7 +1505,8 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
     p.Lq = Lq; p.Lk = Lk;
     p.scale_log2e = q_prescaled ? 1.0f : (1.0f / sqrtf((float)D)) * SDM_LOG2E;      // engine: folded into the to_q weights (d = 64 only)
     if (nsplit > 1) { p.nsplit = nsplit; p.o = (half_t*)part_o.p; p.part_stride = (long)B * p.o_bs; p.part_ml = (float*)part_ml.p; }
-    const unsigned gy = (unsigned)(nsplit > 1 ? nsplit : 1);
+    p.batch = B; p.heads = heads; p.nq_blocks = sdm_cdiv(Lq, pl.qrows); p.q_chunks = 8;
+    p.pp_flags = pl.pp_flags;
     double flops = 4.0 * B * heads * (double)Lq * Lk * D;
     const double bytes = 2.0 * B * heads * D * (2.0 * Lq + 2.0 * Lk);
     std::string adesc = "B=" + std::to_string(B) + " h=" + std::to_string(heads) + " Lq=" + std::to_string(Lq) + " Lk=" + std::to_string(Lk);
@@ -1444,43 +1525,12 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
     }
     if (D == 64) {
       prof_begin(e, "attn_d64", flops, bytes, adesc);
-      // 8-wave blocks (256 queries share every K / V^T tile: half the L2 / Infinity-Cache traffic and LDS staging per MFMA) only
-      // where they measured faster: the split-precision variant with >= 4 such blocks per CU (B=4 h=5 L=16384: 4.01 vs 4.25 ms;
-      // h=10 Lq=4096: 2.39 vs 2.24 ms, i.e. slower; the fp16 variant is neutral to -10 %) - profiles/r02_ablate_attn_nw8.txt
-      const int force_nw = opt("attn_nw");                          // A/B / test option: 4 or 8
-      const bool pp = ap.prec == 2 && ap.out_f32 && opt("attn_pp") != 0 && !force_nw && Lk % 64 == 0 &&      // (LDS-DMA tiles: no masked tail rows)
-                      (long)B * heads * sdm_cdiv(Lq, 256) >= opt("attn_pp_min_blocks");
-      const bool nw8 = pp || (force_nw ? (force_nw == 8) : (ap.prec && (long)B * heads * sdm_cdiv(Lq, 256) >= 1024));
-      const int qrows = nw8 ? 256 : 128;
-      p.batch = B; p.heads = heads; p.nq_blocks = sdm_cdiv(Lq, qrows); p.q_chunks = 8;     // B*heads*8 units: always a multiple of 8
-      const int qb = sdm_cdiv(p.nq_blocks, p.q_chunks);
-      const unsigned nblk = (unsigned)(B * heads * p.q_chunks * qb);                         // 1-D grid, XCD-aware mapping in the kernel
-      if (ap.prec == 2) {
-        // 8-wave blocks with fp32 output (the engine's level-0 attentions): the two-tile software pipeline of the kernel (k_attn.h,
-        // attn_d64_pipe_kernel: same arithmetic, bit-identical results, -9 % kernel time); option attn_pipe = 0 selects the plain form.
-        const bool pipe8 = opt("attn_pipe") != 0, pipe4 = opt("attn_pipe4") != 0;
-        if (pp) { count_kernel("attn_d64_pp"); p.pp_flags = opt("attn_pp") == 1 ? 1 : (opt("attn_pp") == 3 ? 2 : 0); const bool pb = p.bias != nullptr;
-          count_kernel(p.tiles && pb ? "attn_pp<0,1,1>" : (pb ? "attn_pp<0,1,0>" : "attn_pp<0,0,0>"));      // (which specialisation: tests)
-          if (p.tiles && pb) { auto kp = attn_d64_pp_kernel<0, 1, 1>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(512), ATTN64PP_SMEM, e->stream, p); }
-          else if (pb) { auto kp = attn_d64_pp_kernel<0, 1, 0>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(512), ATTN64PP_SMEM, e->stream, p); }
-          else { auto kp = attn_d64_pp_kernel<0, 0, 0>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(512), ATTN64PP_SMEM, e->stream, p); } }
-        else if (nw8 && pipe8 && p.o_f32) { count_kernel("attn_d64_pipe<8>"); auto kp = attn_d64_pipe_kernel<8>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(512), ATTN64PIPE_SMEM, e->stream, p); }
-        else if (!nw8 && pipe4 && p.o_f32) { count_kernel("attn_d64_pipe<4>"); auto kp = attn_d64_pipe_kernel<4>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(256), ATTN64PIPE4_SMEM, e->stream, p); }
-        else if (nw8) { count_kernel("attn_d64<prec3,8>"); auto kp = attn_d64_kernel<1, 3, 8>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(512), ATTN64P_SMEM, e->stream, p); }
-        else { count_kernel("attn_d64<prec3,4>"); auto kp = attn_d64_kernel<1, 3, 4>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(256), ATTN64P_SMEM, e->stream, p); }
-      } else if (ap.prec && pv_split) {
-        if (nw8) { count_kernel("attn_d64<prec1,8>"); auto kp = attn_d64_kernel<1, 1, 8>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(512), ATTN64P_SMEM, e->stream, p); }
-        else { count_kernel("attn_d64<prec1,4>"); auto kp = attn_d64_kernel<1, 1, 4>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(256), ATTN64P_SMEM, e->stream, p); }
-      } else if (ap.prec) {
-        if (nw8) { count_kernel("attn_d64<prec2,8>"); auto kp = attn_d64_kernel<1, 2, 8>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(512), ATTN64P_SMEM, e->stream, p); }
-        else { count_kernel("attn_d64<prec2,4>"); auto kp = attn_d64_kernel<1, 2, 4>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk, gy, 1), dim3(256), ATTN64P_SMEM, e->stream, p); }
-      } else {
-        if (nw8) { count_kernel("attn_d64<fp16,8>"); auto kf = attn_d64_kernel<1, 0, 8>; SDM_SET_SMEM(kf, 160 * 1024); SDM_LAUNCH(kf, dim3(nblk, gy, 1), dim3(512), ATTN64P_SMEM, e->stream, p); }
-        else { count_kernel("attn_d64<fp16,4>"); SDM_LAUNCH((attn_d64_kernel<1, 0, 4>), dim3(nblk, gy, 1), dim3(256), ATTN64_SMEM, e->stream, p); }
-      }
+      count_kernel(ki.counter);
+      if (pl.spec_counter) count_kernel(pl.spec_counter);
+      ki.launch(ki, pl, p, e->stream);
       if (nsplit > 1) {
         count_kernel("attn_combine");
-        count_kernel(nsplit == 2 ? "attn_combine/n=2" : (nsplit == 3 ? "attn_combine/n=3" : "attn_combine/n=4"));      // (the split taken: tests)
+        count_kernel(pl.combine_counter);
         if (ap.out_p3) count_kernel("attn_combine_p3");
         const long nthr = (long)B * Lq * heads * 16;
         if (ap.out_p3)
@@ -1493,15 +1543,12 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
       prof_end(e);
     } else {
       prof_begin(e, "attn_d512", flops, bytes);
-      p.batch = B; p.heads = 1; p.nq_blocks = sdm_cdiv(Lq, 128); p.q_chunks = 8;
-      const unsigned nblk = (unsigned)(B * p.q_chunks * sdm_cdiv(p.nq_blocks, p.q_chunks));
-      SDM_SET_SMEM(attn_d512_kernel<0>, ATTN512P_SMEM);
-      SDM_LAUNCH(attn_d512_kernel<0>, dim3(nblk), dim3(512), ATTN512P_SMEM, e->stream, p);
+      ki.launch(ki, pl, p, e->stream);
       prof_end(e);
     }
   }
   if (nsplit > 1) { tfree(e, part_ml); tfree(e, part_o); }
-  if (own_list) tfree(e, tl_own);
+  if (pl.own_list) tfree(e, tl_own);
   tfree(e, vt);
   return 0;
 }
@@ -1521,36 +1568,29 @@ static int conv_simple(sdm_ctx* e, int layer, const T& in, T* out, int Cout_stor
   return op_conv(e, L, a);
 }
 
-// Would op_conv pick tile cfg 0 (the one that has the fused-GroupNorm variant) for this 3x3 stride-1 conv?
-static bool conv_can_fuse_gn(sdm_ctx* e, const ConvL& L, const T& x, const T* x2) {
-  const bool off = opt("no_gn_fuse") != 0;        // A/B option
-  if (off || L.ntaps != 9) return false;
-  const int Cin = x.C + (x2 ? x2->C : 0);
-  if (Cin > 1024 || Cin != L.Cin_pad) return false;
-  ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.C0 = x.C; p.C1 = x2 ? x2->C : 0; p.in_f32 = x.f32; p.N = x.N; p.Hin = x.H; p.Win = x.W; p.Hout = x.H; p.Wout = x.W; p.Cout_pad = L.Cout_pad;
-  p.M = x.rows();
-  p.f8_hint = (L.f8 && L.wdma_bytes && x.f32) ? 1 : 0;
-  const int cfg = conv_pick_cfg(9, 1, p);
-  return cfg == 0 || cfg == 4 || cfg == 5;        // the 256-pixel tiles that carry the fused-GroupNorm variant
-  (void)e;
-}
-
 // GroupNorm(32)(+SiLU) followed by a 3x3 stride-1 conv.  When the conv runs on the 256x128 tile the normalisation is applied
 // inside the conv's operand staging (no normalised copy of the activation is ever written); otherwise the stand-alone apply
 // kernel produces the fp16 operand first.  `a` carries everything except the inputs.
 static int gn_conv(sdm_ctx* e, const NormL& n, const ConvL& L, const T& x, const T* x2, int silu, float eps, ConvArgs a) {
   const int C = x.C + (x2 ? x2->C : 0);
   if (C != n.C) SDM_FAIL(e, SDM_ERR_INVALID, "groupnorm: C %d != %d", C, n.C);
-  if (conv_can_fuse_gn(e, L, x, x2)) {
+  // the tile op_conv would pick: the 256-pixel tiles (cfg 0 / 4 / 5) carry the fused-GroupNorm variant
+  int cfg = -1;
+  if (!opt("no_gn_fuse") && L.ntaps == 9 && a.stride == 1 && C <= 1024 && C == L.Cin_pad) {
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    conv_shape_params(p, L, x, x2, *a.out, a.stride);
+    cfg = conv_pick_cfg(L.ntaps, a.stride, p);
+  }
+  if (cfg == 0 || cfg == 4 || cfg == 5) {
     const bool hs = x.sbytes && (!x2 || x2->sbytes);
     T scratch; float* scale; float* shift;
     TRY(gn_scale_shift(e, x.p, x2 ? x2->p : nullptr, x.C, x2 ? x2->C : 0, x.f32, x.N, x.H * x.W, e->cfg.groups, n.g, n.b, eps, x.stats, x.srows,
                        x2 ? x2->stats : nullptr, x2 ? x2->srows : 0, hs, &scratch, &scale, &shift));
     a.in0 = &x; a.in1 = x2;
     a.gn_scale = e->dry ? (const float*)16 : scale; a.gn_shift = shift; a.gn_silu = silu;
-    int rc = op_conv(e, L, a);          // picks the same tile conv_can_fuse_gn saw
+    a.force_cfg = cfg;
+    int rc = op_conv(e, L, a);
     tfree(e, scratch);
     return rc;
   }
@@ -1696,8 +1736,9 @@ static int vae_attention(sdm_ctx* e, const VaeAttnB& a, const T& x, T* out) {
   return 0;
 }
 
-// Transformer2DModel + BasicTransformerBlock (Appendix A.7); bias = level key-bias [N][L] (log2 domain) or null
-static int transformer(sdm_ctx* e, const TfB& t, const T& x, const T& uin, const float* bias, const int* tiles, T* out) {
+// Transformer2DModel + BasicTransformerBlock (Appendix A.7); masked: the self-attention takes the level's key bias [N][L] (log2 domain) and its list of
+// active key tiles (bias / tiles: null in the sizing pass, which has no memory)
+static int transformer(sdm_ctx* e, const TfB& t, const T& x, const T& uin, bool masked, const float* bias, const int* tiles, T* out) {
   const int sf = e->cfg.stream_f32;
   const int C = t.C, L = x.H * x.W, L0 = uin.H * uin.W;
   T hn, h, n, qkv, ao, h2, q2, kv, f;
@@ -1728,7 +1769,7 @@ static int transformer(sdm_ctx* e, const TfB& t, const T& x, const T& uin, const
   ao = talloc(e, x.N, x.H, x.W, C, p3a ? kFmtP3 : e->act_f32);
   {
     const half_t* q = (const half_t*)qkv.p;
-    AttnPrec ap; ap.prec = pa ? pf - 1 : 0; ap.out_f32 = p3a ? 1 : ao.f32; ap.out_p3 = p3a ? 1 : 0;
+    AttnPrec ap; ap.prec = pa ? pf - 1 : 0; ap.out_f32 = p3a ? 1 : ao.f32; ap.out_p3 = p3a ? 1 : 0; ap.has_bias = ap.has_tiles = masked;
     ap.q_lo = ap.k_lo = ap.v_lo = (long)qkv.rows() * qkv.C;
     TRY(op_attention_raw(e, q, 3 * C, q ? q + C : nullptr, 3 * C, q ? q + 2 * C : nullptr, 3 * C, bias, x.N, t.heads, L, L, 64, ao.p, C, true, tiles, ap));
   }
@@ -1956,7 +1997,7 @@ static int vae_decode(sdm_ctx* e, const T& z, T* dec) {
   return 0;
 }
 
-static int unet_forward(sdm_ctx* e, const T& uin, float* const* bias_lvl, int* const* tiles_lvl, T* out) {
+static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bias_lvl, int* const* tiles_lvl, T* out) {
   const sdm_config& c = e->cfg;
   const float eps = c.unet_res_eps;
   const int sf = c.stream_f32;
@@ -1969,7 +2010,7 @@ static int unet_forward(sdm_ctx* e, const T& uin, float* const* bias_lvl, int* c
       TRY(resblock(e, e->u_down_res[i][j], h, nullptr, eps, &t));
       if (i < 3) {
         T t2;
-        TRY(transformer(e, e->u_down_tf[i][j], t, uin, bias_lvl[i], tiles_lvl[i], &t2));
+        TRY(transformer(e, e->u_down_tf[i][j], t, uin, masked, bias_lvl[i], tiles_lvl[i], &t2));
         tfree(e, t); t = t2;
       }
       h = t;                       // previous h stays alive as a skip
@@ -1983,7 +2024,7 @@ static int unet_forward(sdm_ctx* e, const T& uin, float* const* bias_lvl, int* c
   }
   // mid (h aliases the last skip: do not free it here)
   TRY(resblock(e, e->u_mid0, h, nullptr, eps, &t)); h = t;
-  TRY(transformer(e, e->u_midtf, h, uin, bias_lvl[3], tiles_lvl[3], &t)); tfree(e, h); h = t;
+  TRY(transformer(e, e->u_midtf, h, uin, masked, bias_lvl[3], tiles_lvl[3], &t)); tfree(e, h); h = t;
   TRY(resblock(e, e->u_mid1, h, nullptr, eps, &t)); tfree(e, h); h = t;
   for (int i = 0; i < 4; ++i) {
     for (size_t j = 0; j < e->u_up_res[i].size(); ++j) {
@@ -1991,7 +2032,7 @@ static int unet_forward(sdm_ctx* e, const T& uin, float* const* bias_lvl, int* c
       TRY(resblock(e, e->u_up_res[i][j], h, &s, eps, &t));   // cat([h, skip], dim=1) then ResBlock (replace.py:509-536)
       tfree(e, h); tfree(e, s); h = t;
       if (i > 0) {
-        TRY(transformer(e, e->u_up_tf[i][j], h, uin, bias_lvl[3 - i], tiles_lvl[3 - i], &t));
+        TRY(transformer(e, e->u_up_tf[i][j], h, uin, masked, bias_lvl[3 - i], tiles_lvl[3 - i], &t));
         tfree(e, h); h = t;
       }
     }
@@ -2043,7 +2084,7 @@ static int run_model(sdm_ctx* e, const T& x16, const T& plane, int B, int SH, in
   // cross-attention context (meta_arch.py:215-218: aux_conv_in(trimap latent) as [B, l*l, ctx]) is never materialised:
   // every block's K|V comes straight from the latent through the folded 3x3 conv (transformer())
   T lat;
-  TRY(unet_forward(e, uin, bias_lvl, tiles_lvl, &lat));
+  TRY(unet_forward(e, uin, use_mask, bias_lvl, tiles_lvl, &lat));
   tfree(e, uin);
   for (int k = 3; k >= 0; --k) { tfree(e, tilebuf[k]); tfree(e, biasbuf[k]); }
   // post_quant_conv + decoder (meta_arch.py:255-256)
@@ -3218,14 +3259,13 @@ int sdm_op_attention(sdm_ctx* e, const void* q, int ldq, const void* k, int ldk,
   if (!e || !q || !k || !v || !out) return SDM_ERR_INVALID;
   return run_two_pass(e, [&]() {
     T b2 = talloc(e, B, 1, 1, Lk, 1);
-    // (the sizing pass has no memory but must take the launch pass's branches - op_attention_raw builds a tile list for a bias: a non-null marker)
-    const float* bl2 = !bias ? nullptr : (e->dry ? (const float*)16 : (const float*)b2.p);
+    AttnPrec ap; ap.has_bias = bias != nullptr;
     if (bias && !e->dry) {
       // natural-log bias (reference domain) -> log2 domain used by the kernel
       SDM_LAUNCH(scale_copy_kernel, dim3(sdm_cdiv(B * Lk, 256)), dim3(256), 0, e->stream, bias, (float*)b2.p, (long)B * Lk, SDM_LOG2E);
     }
-    int rc = op_attention_raw(e, (const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)v, ldv, bl2,
-                              B, heads, Lq, Lk, D, (half_t*)out, ldo);
+    int rc = op_attention_raw(e, (const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)v, ldv, bias ? (const float*)b2.p : nullptr,
+                              B, heads, Lq, Lk, D, (half_t*)out, ldo, false, nullptr, ap);
     tfree(e, b2);
     return rc;
   });
@@ -3249,8 +3289,6 @@ int sdm_op_attention_split_ex(sdm_ctx* e, const float* q, const float* k, const 
   return run_two_pass(e, [&]() -> int {
     T b2 = talloc(e, B, 1, 1, Lk, 1);
     T qp = talloc(e, B, 1, Lq, C, mode), kp = talloc(e, B, 1, Lk, C, mode), vp = talloc(e, B, 1, Lk, C, mode);
-    // (the sizing pass has no memory but must take the launch pass's branches - op_attention_raw builds a tile list for a bias: a non-null marker)
-    const float* bl2 = !bias ? nullptr : (e->dry ? (const float*)16 : (const float*)b2.p);
     const long nq = (long)B * Lq * C, nk = (long)B * Lk * C;
     if (!e->dry) {
       if (bias) SDM_LAUNCH(scale_copy_kernel, dim3(sdm_cdiv(B * Lk, 256)), dim3(256), 0, e->stream, bias, (float*)b2.p, (long)B * Lk, SDM_LOG2E);
@@ -3262,7 +3300,8 @@ int sdm_op_attention_split_ex(sdm_ctx* e, const float* q, const float* k, const 
     T to, pl;
     if (out_p3) to = talloc(e, B, 1, Lq, C, out_p3 == 1 ? kFmtP3 : 1);
     AttnPrec ap; ap.prec = mode - 1; ap.q_lo = nq; ap.k_lo = nk; ap.v_lo = nk; ap.out_f32 = 1; ap.out_p3 = out_p3 == 1;
-    TRY(op_attention_raw(e, (const half_t*)qp.p, C, (const half_t*)kp.p, C, (const half_t*)vp.p, C, bl2, B, heads, Lq, Lk, 64,
+    ap.has_bias = bias != nullptr; ap.has_tiles = tiles != nullptr;
+    TRY(op_attention_raw(e, (const half_t*)qp.p, C, (const half_t*)kp.p, C, (const half_t*)vp.p, C, bias ? (const float*)b2.p : nullptr, B, heads, Lq, Lk, 64,
                          out_p3 ? to.p : (void*)out, C, true, tiles, ap));
     if (out_p3 == 2) TRY(op_to_p3(e, to, &pl));
     const T& p3 = out_p3 == 2 ? pl : to;
@@ -3276,6 +3315,16 @@ int sdm_op_attention_split_ex(sdm_ctx* e, const float* q, const float* k, const 
     tfree(e, vp); tfree(e, kp); tfree(e, qp); tfree(e, b2);
     return 0;
   });
+}
+
+int sdm_debug_attn_plan(int B, int heads, int Lq, int Lk, int D, int prec, int out_f32, int has_bias, int has_tiles, int cus, char* kernel, int cap,
+                        int* nsplit) {
+  if (B < 1 || heads < 1 || Lq < 1 || Lk < 1 || cus < 1 || prec < 0 || prec > 2 || !(D == 64 || (D == 512 && heads == 1 && !prec))) return SDM_ERR_INVALID;
+  OptReadLock opt_lock;
+  const AttnPlan pl = attn_plan(B, heads, Lq, Lk, D, prec, out_f32, has_bias != 0, has_tiles != 0, cus);
+  if (kernel && cap > 0) snprintf(kernel, (size_t)cap, "%s", kAttnKernels[pl.kernel].counter);
+  if (nsplit) *nsplit = pl.nsplit;
+  return SDM_OK;
 }
 
 int sdm_op_resize_aa(sdm_ctx* e, const float* in, int P, int Hin, int Win, float* out, int Hout, int Wout) {

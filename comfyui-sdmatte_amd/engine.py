@@ -83,7 +83,7 @@ EXPORTS = [
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
-    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_op_resize_aa",
+    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias",
     "sdm_set_option", "sdm_get_option", "sdm_reset_options", "sdm_option_name", "sdm_option_help", "sdm_kernel_counts", "sdm_kernel_counts_reset",
 ]
@@ -142,6 +142,7 @@ class Bindings:
             "sdm_op_attention": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32]),
             "sdm_op_attention_split": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
             "sdm_op_attention_split_ex": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+            "sdm_debug_attn_plan": (i32, [i32] * 10 + [C.c_char_p, i32, C.POINTER(i32)]),
             "sdm_op_resize_aa": (i32, [vp, vp, i32, i32, i32, vp, i32, i32]),
             "sdm_op_mask_bias": (i32, [vp, vp, i32, i32, i32, vp]),
             "sdm_set_option": (i32, [C.c_char_p, i32]),
@@ -179,6 +180,13 @@ class Bindings:
 
     def reset_options(self):
         self.sdm_reset_options()
+
+    def attn_plan(self, B, heads, Lq, Lk, cus, D=64, prec=2, out_f32=True, has_bias=False, has_tiles=False):
+        """(launch-counter name of the kernel, key split) the attention operator would take under the current options (sdm_debug_attn_plan)."""
+        buf, ns = C.create_string_buffer(64), C.c_int(0)
+        if self.sdm_debug_attn_plan(B, heads, Lq, Lk, D, prec, int(out_f32), int(has_bias), int(has_tiles), cus, buf, 64, C.byref(ns)) != 0:
+            raise ValueError(f"sdm_debug_attn_plan: unsupported attention B={B} heads={heads} Lq={Lq} Lk={Lk} D={D} prec={prec}")
+        return buf.value.decode(), ns.value
 
     def kernel_counts(self, reset=False):
         """{kernel variant: launches since the last reset}"""

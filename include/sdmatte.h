@@ -264,6 +264,12 @@ int sdm_op_attention_split(sdm_ctx* ctx, const float* q, const float* k, const f
  * planes != NULL, the raw planes (ceil(B*Lq/32)*32 * heads*64 * 3 bytes: fp16 hi plane, then the e5m2 xl plane). */
 int sdm_op_attention_split_ex(sdm_ctx* ctx, const float* q, const float* k, const float* v, const float* bias, const int* tiles, int B, int heads, int Lq,
                               int Lk, int out_p3, float* out, void* planes);
+/* Test hook: the launch the attention operator would make for these shapes and flags under the current options, on a device of `cus` compute units:
+ * the launch-counter name of the kernel (see sdm_kernel_counts) into kernel[cap] and the key split into *nsplit (1 = unsplit).  prec as in the engine:
+ * 0 fp16 operands, 1 fp16 hi | lo planes, 2 fp16 + e5m2 pair planes (the default precision); has_bias / has_tiles: a key bias / a caller's tile list
+ * comes with the call.  Touches neither a GPU nor an engine.  D = 64, or 512 with one head and prec 0. */
+int sdm_debug_attn_plan(int B, int heads, int Lq, int Lk, int D, int prec, int out_f32, int has_bias, int has_tiles, int cus, char* kernel, int cap,
+                        int* nsplit);
 /* Antialiased bilinear resize of fp32 planes [P, Hin, Win] -> [P, Hout, Wout] (torchvision Resize). */
 int sdm_op_resize_aa(sdm_ctx* ctx, const float* in, int P, int Hin, int Win, float* out, int Hout, int Wout);
 /* Level-k additive key bias (natural-log domain) from the [-1,1] trimap plane [B,S,S] -> [B,(S/8>>k)^2]. */

@@ -359,6 +359,49 @@ def test_attention_split_matrix(emu_engine, engine_option, case):
     print(f"[attn matrix] {name}: max|d| vs fp64 = {err:.3g} {st}")
 
 
+def _attention_shapes():
+    """(B, heads, Lq, Lk) of every self- and cross-attention the full configuration's U-Net issues (level k: (S/8 >> k)^2 tokens, unet_heads[k] heads;
+    the cross-attention keys are the (S/8)^2 latent pixels) at the node's inference sizes and 1536, 1 / 2 / 4 / 8 images per call, plus the shapes of
+    the split-attention matrices and of the engine-shape cases of the emulator and GPU operator tests."""
+    from comfyui_sdmatte_amd.config import INFERENCE_SIZES, SDMatteConfig
+    import test_gpu_ops as G
+    shapes = set()
+    for size in INFERENCE_SIZES + [1536]:
+        for k, heads in enumerate(SDMatteConfig.full().unet_heads):
+            tokens = ((size // 8) >> k) ** 2
+            for B in (1, 2, 4, 8):
+                shapes.add((B, heads, tokens, tokens))
+                shapes.add((B, heads, tokens, (size // 8) ** 2))
+    for case in ATTN_MATRIX_EMU + G.ATTN_MATRIX_GPU:
+        shapes.add(tuple(case[3:7]))
+    for case in G.ATTN_ENGINE_SHAPES:
+        shapes.add(tuple(case[1:5]))
+    return sorted(shapes)
+
+
+def test_attention_plan_equals_its_python_mirror(emu_engine, engine_option):
+    """sdm_debug_attn_plan - the one statement of the attention launch choice in the engine (attn_plan, which op_attention_raw sizes and launches
+    from) - against ops_suite.attn_launch_choice, the independent statement of the same rule, on 256 compute units: kernel and key split, for every
+    shape above under every value of the options attn_nw, attn_ksplit and attn_pp_min_blocks.  No kernel runs."""
+    lib = emu_engine.lib
+    shapes = _attention_shapes()
+    assert len(shapes) > 150, len(shapes)
+    n = 0
+    for nw in (0, 4, 8):
+        for ksplit in (0, 1, 2, 3, 4):
+            for pp_min in (0, 128):
+                engine_option(lib, "attn_nw", nw)
+                engine_option(lib, "attn_ksplit", ksplit)
+                engine_option(lib, "attn_pp_min_blocks", pp_min)
+                for B, heads, Lq, Lk in shapes:
+                    want = S.attn_launch_choice(B, heads, Lq, Lk, 256, pp_min_blocks=pp_min, ksplit=ksplit, nw=nw)
+                    for masked in (False, True):      # a key bias and its tile list change the specialisation, never the kernel or the split
+                        got = lib.attn_plan(B, heads, Lq, Lk, 256, has_bias=masked, has_tiles=masked)
+                        assert got == want, (B, heads, Lq, Lk, nw, ksplit, pp_min, masked, got, want)
+                        n += 1
+    print(f"[attn plan] {n} plans equal the mirror ({len(shapes)} shapes)")
+
+
 def _fresh_engine(emu_engine):
     from comfyui_sdmatte_amd.engine import Engine
     from comfyui_sdmatte_amd.config import SDMatteConfig
