@@ -1,5 +1,5 @@
 // sdm_engine.cpp - MI355X-native SDMatte engine: model graph, weight registry/packing, activation arena and
-// the C ABI of include/sdmatte.h.  Compiled with `hipcc -x hip --offload-arch=gfx950` (product), or with
+// the product C ABI of include/sdmatte.h (its test hooks and bench helpers: sdm_hooks.h, included at the end).  Compiled with `hipcc -x hip --offload-arch=gfx950` (product), or with
 // -DSDM_EMU against tests/emu/hip_emu.h (kernel-debug build used by tests only; never shipped).
 //
 // The graph executed by run_model() restates SDMatte.forward (/root/reference/src/modeling/SDMatte/
@@ -544,8 +544,45 @@ struct ConvL {
   // Linear layers of the split-precision stages also keep the W3 layout of the plane-fed GEMM (k_gemm.h; same f8_exp)
   size_t w3_off = 0, w3_bytes = 0;
   unsigned char* w3 = nullptr;
+  size_t w_bytes() const { return (size_t)Cin_pad * ntaps * Cout_pad * 2; }      // K16: each of w and w_lo
+  size_t b_bytes() const { return (size_t)Cout_pad * 4; }
 };
 static const int kSplitWeightExp = 8;      // pre-scale 2^8: typical |w| ~ 1e-2 .. 1 -> low parts ~ 1e-3 .. 1e-1 * 2^-4: fp16-normal
+
+static ConvL make_layer(const std::string& name, int ntaps, int I, int O, int geglu, int split) {
+  ConvL L;
+  L.name = name; L.ntaps = ntaps; L.I = I; L.O = O; L.geglu = geglu;
+  L.Cin_pad = rup(I, 16);
+  L.Cout_pad = rup(O, geglu ? 64 : 32);
+  L.split = split ? 1 : 0;
+  L.w_exp = split ? kSplitWeightExp : 0;
+  return L;
+}
+
+// Which derived weight layouts a layer of a given shape can carry - the ONE statement of it, for the model's layers (Builder::conv) and for
+// the temporary layers of the single-operator hooks (sdm_hooks.h TempLayer) alike.  The predicates hold what the kernels need; policy that only
+// the model applies is passed in by its call site and is deliberately absent from the hooks, which build a layout for every eligible layer:
+//   stage-ordered 3x3 copy   model: split-precision layers only, or all with conv_dma_all (measured +4..6 % there; neutral with fp16 operands,
+//                            where the register-staged kernel stays);  hooks: every eligible layer - how the fp16 DMA kernel is op-tested
+//   fp8-residual GEMM copy   model: K >= gemm_f8_min_k;  hooks: any K (small-K op tests of the 8-wave GEMM)
+//   W3                       model: with conv_f8 and gemm_p3;  hooks: the conv hook never, the plane-fed GEMM hooks always
+static bool layer_takes_dma3x3(const ConvL& L) { return L.ntaps == 9 && L.Cout_pad >= 128 && !L.geglu; }
+// Linear / 1x1 layers of the split-precision stages: fp8-residual copy for the 8-wave GEMM kernel (k_conv.h, F8 with NTAPS = 1), used when the
+// launch takes the 256 x 128 tile
+static bool layer_takes_gemm_f8(const ConvL& L) {
+  return L.ntaps == 1 && L.split && L.Cout_pad >= 128 && L.Cin_pad % 32 == 0 && conv_f8_enabled() && gemm_f8_enabled();
+}
+// Linear layers of a split-precision stage whose K splits into 32-channel chunks: W3 copy for the plane-fed GEMM (k_gemm.h)
+static bool layer_takes_w3(const ConvL& L) { return L.ntaps == 1 && L.split && L.Cin_pad % 32 == 0 && L.Cin_pad >= 32; }
+// sizes of the derived copies the caller wants and the layer can carry (0: none), and which of the two layouts w_dma holds
+static void layer_choose_layouts(ConvL& L, bool want_dma3x3, bool want_gemm_f8, bool want_w3) {
+  if (want_dma3x3 && layer_takes_dma3x3(L)) {
+    L.wdma_bytes = L.w_bytes() * (L.split ? 2 : 1);
+    L.f8 = (L.split && L.Cin_pad % 32 == 0 && conv_f8_enabled()) ? 1 : 0;      // same bytes, fp8-residual layout
+  }
+  if (want_gemm_f8 && layer_takes_gemm_f8(L)) { L.wdma_bytes = L.w_bytes() * 2; L.f8 = 1; }
+  if (want_w3 && layer_takes_w3(L)) L.w3_bytes = L.w_bytes() * 2;
+}
 struct NormL {
   int C = 0;
   size_t g_off = 0, b_off = 0;
@@ -709,38 +746,17 @@ struct Builder {
   int stage = 0;           // sdm_precise_stage of the layers being built
   explicit Builder(sdm_ctx* c) : e(c) {}
   int conv(const std::string& name, int ntaps, int I_pad16_src, int O, int geglu = 0) {
-    ConvL L;
-    L.name = name; L.ntaps = ntaps; L.I = I_pad16_src; L.O = O;
-    L.Cin_pad = rup(I_pad16_src, 16);
-    L.Cout_pad = rup(O, geglu ? 64 : 32);
-    L.geglu = geglu;
-    L.w_off = woff; woff += rupz((size_t)L.Cin_pad * ntaps * L.Cout_pad * 2, 256);
-    L.b_off = woff; woff += rupz((size_t)L.Cout_pad * 4, 256);
+    ConvL L = make_layer(name, ntaps, I_pad16_src, O, geglu, e->cfg.precise_mask & stage);
     L.stage = stage;
-    L.split = (e->cfg.precise_mask & stage) ? 1 : 0;
-    if (L.split) { L.w_exp = kSplitWeightExp; L.wlo_off = woff; woff += rupz((size_t)L.Cin_pad * ntaps * L.Cout_pad * 2, 256); }
-    // stage-ordered copy for the DMA-weight kernel: split-precision layers only (measured +4..6 % there; neutral with fp16 operands,
-    // where the register-staged kernel stays; the option conv_dma_all = 1 builds the copy for every wide 3x3 layer)
-    const bool dma_all = opt("conv_dma_all") != 0;
-    if (ntaps == 9 && L.Cout_pad >= 128 && !geglu && (L.split || dma_all)) {
-      L.wdma_bytes = (size_t)L.Cin_pad * 9 * L.Cout_pad * 2 * (L.split ? 2 : 1);
-      L.wdma_off = doff; doff += rupz(L.wdma_bytes, 256);
-      L.f8 = (L.split && L.Cin_pad % 32 == 0 && conv_f8_enabled()) ? 1 : 0;      // same bytes, fp8-residual layout
-    }
-    // Linear / 1x1 layers of the split-precision stages with K >= 1024: fp8-residual copy for the 8-wave GEMM kernel (k_conv.h, F8
-    // with NTAPS = 1), used when the launch takes the 256 x 128 tile; SDM_GEMM_F8=0 disables.  A GEMM has no operand reuse across
-    // taps, so the producer waves (one 32 KB activation tile converted per 1024 MFMA cycles) set the pace: measured against the
-    // 4-wave kernel x1.2-1.5 for K = 1280 ... 5120, x0.84-1.0 for K <= 640 (profiles/r02_gemm_f8_ab.txt) - hence the threshold
-    if (ntaps == 1 && L.split && L.Cout_pad >= 128 && L.Cin_pad % 32 == 0 && L.Cin_pad >= gemm_f8_min_k() && conv_f8_enabled() && gemm_f8_enabled()) {
-      L.wdma_bytes = (size_t)L.Cin_pad * L.Cout_pad * 4;
-      L.wdma_off = doff; doff += rupz(L.wdma_bytes, 256);
-      L.f8 = 1;
-    }
-    // every Linear of a split-precision stage whose K splits into 32-channel chunks: W3 copy for the plane-fed GEMM (k_gemm.h)
-    if (ntaps == 1 && L.split && L.Cin_pad % 32 == 0 && L.Cin_pad >= 32 && conv_f8_enabled() && opt("gemm_p3") != 0) {
-      L.w3_bytes = (size_t)L.Cin_pad * L.Cout_pad * 4;
-      L.w3_off = doff; doff += rupz(L.w3_bytes, 256);
-    }
+    L.w_off = woff; woff += rupz(L.w_bytes(), 256);
+    L.b_off = woff; woff += rupz(L.b_bytes(), 256);
+    if (L.split) { L.wlo_off = woff; woff += rupz(L.w_bytes(), 256); }
+    // The model's own policy on top of what a layer can carry (layer_choose_layouts).  The fp8-residual GEMM copy has a threshold on K: a GEMM
+    // has no operand reuse across taps, so the producer waves (one 32 KB activation tile converted per 1024 MFMA cycles) set the pace: measured
+    // against the 4-wave kernel x1.2-1.5 for K = 1280 ... 5120, x0.84-1.0 for K <= 640 (profiles/r02_gemm_f8_ab.txt)
+    layer_choose_layouts(L, L.split || opt("conv_dma_all") != 0, L.Cin_pad >= gemm_f8_min_k(), conv_f8_enabled() && opt("gemm_p3") != 0);
+    if (L.wdma_bytes) { L.wdma_off = doff; doff += rupz(L.wdma_bytes, 256); }
+    if (L.w3_bytes) { L.w3_off = doff; doff += rupz(L.w3_bytes, 256); }
     e->convs.push_back(L);
     return (int)e->convs.size() - 1;
   }
@@ -804,11 +820,9 @@ struct Builder {
     a.gn = norm_named(p + ".group_norm", C);
     a.qkv = conv(p + ".qkv", 1, C, 3 * C);
     const char* nm[3] = {"to_q", "to_k", "to_v"};
-    const char* legacy[3] = {"query", "key", "value"};
     for (int i = 0; i < 3; ++i) {
       slot(p + "." + nm[i] + ".weight", SLOT_CONV_W, a.qkv, {C, C}, i * C);
       slot(p + "." + nm[i] + ".bias", SLOT_CONV_B, a.qkv, {C}, i * C);
-      (void)legacy;
     }
     a.out = conv_named(p + ".to_out.0", 1, C, C);
     return a;
@@ -2361,6 +2375,17 @@ static float to_f32(const void* p, int dtype, size_t i) {
   float f; memcpy(&f, &u, 4); return f;
 }
 
+// The one pack path of a layer's canonical tensors: fp32 OIHW / [O][I] weights (device) -> K16 w (+ w_lo of a split-precision layer), pre-scaled by
+// w_scale * 2^w_exp, at input / output channel offsets ci_off / co_off of the layer; fp32 bias [n] -> b at co_off.
+static void pack_layer_weight(sdm_ctx* e, const ConvL& L, const float* src, int O, int I, int ci_off, int co_off, float w_scale) {
+  const size_t total = L.w_bytes() / 2;
+  SDM_LAUNCH(pack_conv_weight_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, e->stream, src, L.w, O, I, L.ntaps,
+             L.Cin_pad, L.Cout_pad, ci_off, co_off, L.geglu, w_scale * ldexpf(1.0f, L.w_exp), L.w_lo);
+}
+static void pack_layer_bias(sdm_ctx* e, const ConvL& L, const float* src, int n, int co_off) {
+  SDM_LAUNCH(pack_bias_kernel, dim3(sdm_cdiv(L.Cout_pad, 256)), dim3(256), 0, e->stream, src, L.b, n, L.Cout_pad, co_off, L.geglu);
+}
+
 int sdm_load_tensor(sdm_ctx* e, const char* name, int dtype, int ndim, const int64_t* shape, const void* host_ptr) {
   if (e) dev_use(e->device);
   if (!e || !name || !host_ptr) return SDM_ERR_INVALID;
@@ -2415,16 +2440,9 @@ int sdm_load_tensor(sdm_ctx* e, const char* name, int dtype, int ndim, const int
     dsrc = (float*)e->stage;
 #endif
     if (s.kind == SLOT_CONV_W) {
-      ConvL& L = e->convs[s.layer];
-      const int O = (int)s.shape[0], I = (int)s.shape[1];
-      const size_t total = (size_t)L.Cin_pad * L.ntaps * L.Cout_pad;
-      SDM_LAUNCH(pack_conv_weight_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, e->stream,
-                 (const float*)dsrc, L.w, O, I, L.ntaps, L.Cin_pad, L.Cout_pad, s.ci_off, s.co_off, L.geglu,
-                 s.w_scale * ldexpf(1.0f, L.w_exp), L.w_lo);
+      pack_layer_weight(e, e->convs[s.layer], dsrc, (int)s.shape[0], (int)s.shape[1], s.ci_off, s.co_off, s.w_scale);
     } else if (s.kind == SLOT_CONV_B) {
-      ConvL& L = e->convs[s.layer];
-      SDM_LAUNCH(pack_bias_kernel, dim3(sdm_cdiv(L.Cout_pad, 256)), dim3(256), 0, e->stream, (const float*)dsrc, L.b, (int)s.shape[0],
-                 L.Cout_pad, s.co_off, L.geglu);
+      pack_layer_bias(e, e->convs[s.layer], dsrc, (int)s.shape[0], s.co_off);
     } else {
       NormL& nn = e->norms[s.layer];
       SDM_CHECK_DEV(e, dev_memcpy_d2d(s.kind == SLOT_NORM_G ? nn.g : nn.b, dsrc, n * 4, e->stream));
@@ -2474,15 +2492,13 @@ static int fold_cross_kv(sdm_ctx* e) {
     }
     // upload as an OIHW [2C][4][3][3] tensor; the 4 latent channels sit at channels 4..7 of the 16-channel U-Net input
     if (ensure_buf(e, &e->stage, &e->stage_bytes, std::max(wf.size() * 4, (size_t)1 << 20)) != 0) return SDM_ERR_NOMEM;
-    SDM_CHECK_DEV(e, dev_memset(L.w, 0, (size_t)L.Cin_pad * 9 * L.Cout_pad * 2, e->stream));
-    if (L.w_lo) SDM_CHECK_DEV(e, dev_memset(L.w_lo, 0, (size_t)L.Cin_pad * 9 * L.Cout_pad * 2, e->stream));
+    SDM_CHECK_DEV(e, dev_memset(L.w, 0, L.w_bytes(), e->stream));
+    if (L.w_lo) SDM_CHECK_DEV(e, dev_memset(L.w_lo, 0, L.w_bytes(), e->stream));
     SDM_CHECK_DEV(e, dev_memcpy_h2d(e->stage, wf.data(), wf.size() * 4, e->stream));
-    const size_t total = (size_t)L.Cin_pad * 9 * L.Cout_pad;
-    SDM_LAUNCH(pack_conv_weight_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, e->stream, (const float*)e->stage,
-               L.w, 2 * C, 4, 9, L.Cin_pad, L.Cout_pad, 4, 0, 0, ldexpf(1.0f, L.w_exp), L.w_lo);
+    pack_layer_weight(e, L, (const float*)e->stage, 2 * C, 4, 4, 0, 1.0f);
     SDM_CHECK_DEV(e, dev_sync(e->stream));
     SDM_CHECK_DEV(e, dev_memcpy_h2d(e->stage, bf.data(), bf.size() * 4, e->stream));
-    SDM_LAUNCH(pack_bias_kernel, dim3(sdm_cdiv(L.Cout_pad, 256)), dim3(256), 0, e->stream, (const float*)e->stage, L.b, 2 * C, L.Cout_pad, 0, 0);
+    pack_layer_bias(e, L, (const float*)e->stage, 2 * C, 0);
     SDM_CHECK_DEV(e, dev_sync(e->stream));
   }
   return 0;
@@ -2760,588 +2776,7 @@ int sdm_profile_get(sdm_ctx* e, int i, const char** name, float* ms, int64_t* la
   return SDM_OK;
 }
 
-// ---- single-operator entry points ----
-int sdm_conv_num_cfgs(int ntaps, int stride) { return conv_num_cfgs(ntaps, stride); }
-
-int sdm_op_conv_ex(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1, int in_f32, int N, int Hin, int Win, int up, int stride,
-                   int pad_mode, int ntaps, const float* w, const float* bias, int O, void* out, int out_f32, const void* res, int res_f32,
-                   int geglu, float out_scale, int tile_cfg, int split, const float* gn_gamma, const float* gn_beta, float gn_eps,
-                   int gn_groups, int gn_silu) {
-  if (e) dev_use(e->device);
-  if (!e || !in0 || !w || !out) return SDM_ERR_INVALID;
-  if (C0 % 16 || C1 % 16) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv: channel counts must be multiples of 16");
-  if (split && !in_f32) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv_ex: split precision takes fp32 activations");
-  ConvL L;
-  L.name = "op"; L.ntaps = ntaps; L.I = C0 + C1; L.O = O; L.Cin_pad = C0 + C1; L.Cout_pad = rup(O, geglu ? 64 : 32); L.geglu = geglu;
-  L.split = split ? 1 : 0; L.w_exp = split ? kSplitWeightExp : 0;
-  void* wp = nullptr; void* bp = nullptr; void* wl = nullptr;
-  const size_t wbytes = (size_t)L.Cin_pad * ntaps * L.Cout_pad * 2;
-  SDM_CHECK_DEV(e, dev_malloc(&wp, wbytes));
-  SDM_CHECK_DEV(e, dev_malloc(&bp, (size_t)L.Cout_pad * 4));
-  if (split) { SDM_CHECK_DEV(e, dev_malloc(&wl, wbytes)); dev_memset(wl, 0, wbytes, e->stream); }
-  dev_memset(wp, 0, wbytes, e->stream); dev_memset(bp, 0, (size_t)L.Cout_pad * 4, e->stream);
-  L.w = (half_t*)wp; L.b = (float*)bp; L.w_lo = (half_t*)wl;
-  const size_t total = (size_t)L.Cin_pad * ntaps * L.Cout_pad;
-  SDM_LAUNCH(pack_conv_weight_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, e->stream, w, L.w, O, L.I, ntaps,
-             L.Cin_pad, L.Cout_pad, 0, 0, geglu, ldexpf(1.0f, L.w_exp), L.w_lo);
-  if (bias) SDM_LAUNCH(pack_bias_kernel, dim3(sdm_cdiv(L.Cout_pad, 256)), dim3(256), 0, e->stream, bias, L.b, O, L.Cout_pad, 0, geglu);
-  void* wd = nullptr;
-  if (ntaps == 9 && L.Cout_pad >= 128 && !geglu) {      // stage-ordered copy for the DMA-weight kernel (tile cfg 0), as in the engine
-    SDM_CHECK_DEV(e, dev_malloc(&wd, total * (split ? 2 : 1) * 2));
-    L.w_dma = (half_t*)wd;
-    L.f8 = (split && L.Cin_pad % 32 == 0 && conv_f8_enabled()) ? 1 : 0;
-  }
-  if (ntaps == 1 && split && L.Cout_pad >= 128 && L.Cin_pad % 32 == 0 && conv_f8_enabled() && gemm_f8_enabled()) {      // fp8-residual copy for the 8-wave GEMM kernel
-    SDM_CHECK_DEV(e, dev_malloc(&wd, total * 4));
-    dev_memset(wd, 0, total * 4, e->stream);
-    L.w_dma = (half_t*)wd; L.f8 = 1;
-  }
-  if (L.w_dma) { std::vector<ConvL*> one{&L}; TRY(derive_layers(e, one)); }
-  int Ho = Hin << up, Wo = Win << up;
-  if (stride == 2) { Ho /= 2; Wo /= 2; }
-  const int Cst = rup(geglu ? O / 2 : O, 4);   // rows are stored with 4-channel vectors
-  T tin0, tin1, tout, tres;
-  tin0.p = (void*)in0; tin0.N = N; tin0.H = Hin; tin0.W = Win; tin0.C = C0; tin0.f32 = in_f32;
-  tin1 = tin0; tin1.p = (void*)in1; tin1.C = C1;
-  tout.p = out; tout.N = N; tout.H = Ho; tout.W = Wo; tout.C = Cst; tout.f32 = out_f32;
-  tres = tout; tres.p = (void*)res; tres.f32 = res_f32;
-  if (e->dbg_cmask) { tin0.cmask = const_cast<unsigned char*>(e->dbg_cmask); tin0.cm_bytes = 1; e->dbg_cmask = nullptr; }      // (borrowed: tin0 is never tfree'd)
-  ConvArgs a; a.in0 = &tin0; a.in1 = in1 ? &tin1 : nullptr; a.out = &tout; a.stride = stride; a.pad_mode = pad_mode; a.up = up;
-  a.res = res ? &tres : nullptr; a.out_scale = out_scale; a.force_cfg = tile_cfg; a.cout_valid = Cst;
-  int rc;
-  if (gn_gamma) {
-    // GroupNorm(+SiLU) of the input applied inside the conv's operand staging (the production path of every ResBlock conv):
-    // statistics by the stand-alone kernel, scale/shift table, then the fused-GN instantiation of tile cfg 0 / 4 / 5
-    if (ntaps != 9 || stride != 1 || up) { dev_free(wp); dev_free(bp); if (wl) dev_free(wl); SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv_ex: fused GroupNorm needs a 3x3 stride-1 conv"); }
-    if (a.force_cfg != 0 && a.force_cfg != 4 && a.force_cfg != 5) a.force_cfg = (L.Cout_pad <= 32) ? 4 : 0;
-    const int act_prev = e->act_f32;
-    rc = run_two_pass(e, [&]() {
-      T scratch; float* scale; float* shift;
-      TRY(gn_scale_shift(e, in0, in1, C0, C1, in_f32, N, Hin * Win, gn_groups, gn_gamma, gn_beta, gn_eps, nullptr, 0, nullptr, 0, false, &scratch,
-                         &scale, &shift));
-      ConvArgs b = a;
-      b.gn_scale = e->dry ? (const float*)16 : scale; b.gn_shift = shift; b.gn_silu = gn_silu;
-      int r2 = op_conv(e, L, b);
-      tfree(e, scratch);
-      return r2;
-    });
-    e->act_f32 = act_prev;
-  } else {
-    rc = run_two_pass(e, [&]() { return op_conv(e, L, a); });      // (the arena holds the split-K workspace, if the layer is split)
-  }
-  dev_sync(e->stream);
-  dev_free(wp); dev_free(bp); if (wl) dev_free(wl);
-  if (wd) dev_free(wd);
-  return rc;
-}
-
-/* Plane-fed GEMM (k_gemm.h) as a stand-alone operator: x fp32 [N*H*W][K] (device) is converted to P3 planes (to_p3_kernel, or LayerNorm with P3 output
- * when ln_gamma is given), w fp32 [O][K] is packed to K16 -> W3 exactly as a model layer.  mode 0: fp32 out (+bias, +fp32 residual); 1: GEGLU (O = 2 x outputs);
- * 3: linear (+residual) to P3; both P3 results are decoded to fp32 (hi + xl * 2^-11) into `out`; 2: raw q | k | v operand planes (fp16 hi [rows][O] then the
- * e5m2 pair plane, pair plane for channels < lo_cols only); 4: mode 0 + the consumer's GroupNorm statistics, [N][*srows][O][2] floats into `stats`. */
-int sdm_op_gemm_p3(sdm_ctx* e, const float* x, int N, int H, int W, int K, const float* w, const float* bias, int O, int mode, const float* res,
-                   const float* ln_gamma, const float* ln_beta, float ln_eps, int lo_cols, void* out, float* stats, int* srows) {
-  if (e) dev_use(e->device);
-  if (!e || !x || !w || !out) return SDM_ERR_INVALID;
-  const int geglu = mode == 1;
-  if (K % 32 || O % (geglu ? 64 : 32)) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_gemm_p3: K %% 32 and O %% 32 (GEGLU: 64) required");
-  ConvL L;
-  L.name = "op_gemm_p3"; L.ntaps = 1; L.I = K; L.O = O; L.Cin_pad = K; L.Cout_pad = O; L.geglu = geglu; L.split = 1; L.w_exp = kSplitWeightExp;
-  void* wp = nullptr; void* bp = nullptr; void* wl = nullptr; void* w3 = nullptr;
-  const size_t total = (size_t)K * O, wbytes = total * 2;
-  SDM_CHECK_DEV(e, dev_malloc(&wp, wbytes)); SDM_CHECK_DEV(e, dev_malloc(&wl, wbytes)); SDM_CHECK_DEV(e, dev_malloc(&bp, (size_t)O * 4));
-  SDM_CHECK_DEV(e, dev_malloc(&w3, total * 4));
-  dev_memset(wp, 0, wbytes, e->stream); dev_memset(wl, 0, wbytes, e->stream); dev_memset(bp, 0, (size_t)O * 4, e->stream);
-  L.w = (half_t*)wp; L.w_lo = (half_t*)wl; L.b = (float*)bp; L.w3 = (unsigned char*)w3; L.w3_bytes = total * 4;
-  SDM_LAUNCH(pack_conv_weight_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, e->stream, w, L.w, O, K, 1, K, O, 0, 0, geglu,
-             ldexpf(1.0f, L.w_exp), L.w_lo);
-  if (bias) SDM_LAUNCH(pack_bias_kernel, dim3(sdm_cdiv(O, 256)), dim3(256), 0, e->stream, bias, L.b, O, O, 0, geglu);
-  { std::vector<ConvL*> one{&L}; TRY(derive_layers(e, one)); }
-  const int Cst = geglu ? O / 2 : O;
-  const int act_prev = e->act_f32;
-  e->act_f32 = 1;
-  int rc = run_two_pass(e, [&]() -> int {
-    T tx, xp, to, tres;
-    tx.p = (void*)x; tx.N = N; tx.H = H; tx.W = W; tx.C = K; tx.f32 = 1;
-    if (ln_gamma) {
-      NormL nl; nl.C = K; nl.g = const_cast<float*>(ln_gamma); nl.b = const_cast<float*>(ln_beta);
-      TRY(op_ln(e, nl, tx, ln_eps, &xp, kFmtP3));
-    } else {
-      TRY(op_to_p3(e, tx, &xp));
-    }
-    tres.p = (void*)res; tres.N = N; tres.H = H; tres.W = W; tres.C = Cst; tres.f32 = 1;
-    const bool planes = (mode == 1 || mode == 3);
-    if (planes) to = talloc(e, N, H, W, Cst, kFmtP3);
-    else { to.p = out; to.N = N; to.H = H; to.W = W; to.C = Cst; to.f32 = (mode == 2) ? 3 : 1; }
-    to.want_stats = (mode == 4);
-    TRY(op_gemm_p3(e, L, xp, &to, res ? &tres : nullptr, lo_cols));
-    if (!e->dry) {
-      if (planes) SDM_LAUNCH(from_p3_kernel, dim3((unsigned)std::min<long>((to.rows() * Cst + 255) / 256, 1 << 20)), dim3(256), 0, e->stream, (const unsigned char*)to.p, (float*)out, to.rows(), Cst);
-      if (mode == 4 && stats) {
-        SDM_CHECK_DEV(e, dev_memcpy_d2d(stats, to.stats, (size_t)N * to.srows * Cst * 2 * 4, e->stream));
-        if (srows) *srows = to.srows;
-      }
-    }
-    if (planes) tfree(e, to);
-    else if (to.sbytes) { tfree_raw(e, to.soff, to.sbytes); to.sbytes = 0; }
-    tfree(e, xp);
-    return 0;
-  });
-  e->act_f32 = act_prev;
-  dev_sync(e->stream);
-  dev_free(wp); dev_free(wl); dev_free(bp); dev_free(w3);
-  return rc;
-}
-
-/* Test hook: `mask` (device, [N][Hin][Win] bytes, class ids 0..4; k_misc.h cmask_*) is the class plane of the input of the NEXT sdm_op_conv_ex call -
- * the conv then leaves the output tiles of constant regions to const_tile_fill_kernel, as the VAE encoder does for the trimap images. */
-int sdm_debug_set_input_cmask(sdm_ctx* e, const unsigned char* mask) {
-  if (!e) return SDM_ERR_INVALID;
-  e->dbg_cmask = mask;
-  return SDM_OK;
-}
-
-int sdm_op_conv(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1, int in_f32, int N, int Hin, int Win, int up, int stride,
-                int pad_mode, int ntaps, const float* w, const float* bias, int O, void* out, int out_f32, const void* res, int res_f32,
-                int geglu, float out_scale, int tile_cfg) {
-  return sdm_op_conv_ex(e, in0, in1, C0, C1, in_f32, N, Hin, Win, up, stride, pad_mode, ntaps, w, bias, O, out, out_f32, res, res_f32, geglu,
-                        out_scale, tile_cfg, 0, nullptr, nullptr, 0.0f, 32, 0);
-}
-
-/* ---- test hooks for the exact algebraic folds (SURVEY.md 8a "each needs a fold == unfold CPU test") ----------------------- */
-
-/* Run ONE packed layer of the loaded model (by name, e.g. "unet.down_blocks.0.attentions.0.transformer_blocks.0.attn2.kv_folded",
- * "...attn1.qkv") on an fp32 NHWC input with the layer's padded input channel count; fp32 NHWC output with `Cout` channels. */
-int sdm_debug_run_layer(sdm_ctx* e, const char* layer_name, const float* x, int N, int H, int W, float* out, int Cout) {
-  if (e) dev_use(e->device);
-  if (!e || !layer_name || !x || !out) return SDM_ERR_INVALID;
-  if (!e->finalized) SDM_FAIL(e, SDM_ERR_STATE, "weights not finalised");
-  const ConvL* L = nullptr;
-  for (auto& c : e->convs) if (c.name == layer_name) { L = &c; break; }
-  if (!L) SDM_FAIL(e, SDM_ERR_INVALID, "no packed layer named %s", layer_name);
-  if (Cout % 4 || Cout > L->Cout_pad) SDM_FAIL(e, SDM_ERR_INVALID, "bad Cout %d for layer %s", Cout, layer_name);
-  T tin, tout;
-  tin.p = (void*)x; tin.N = N; tin.H = H; tin.W = W; tin.C = L->Cin_pad; tin.f32 = 1;
-  tout.p = out; tout.N = N; tout.H = H; tout.W = W; tout.C = Cout; tout.f32 = 1;
-  ConvArgs a; a.in0 = &tin; a.out = &tout; a.cout_valid = Cout;
-  int rc = run_two_pass(e, [&]() { return op_conv(e, *L, a); });
-  dev_sync(e->stream);
-  return rc;
-}
-
-/* Folded conv1 bias row (conv1.bias + time_emb_proj(silu(emb)), emb = time_embedding(trans) + bbox_embedding(coords)) of the
- * i-th ResBlock that has a time embedding, for one (is_trans, box) conditioning; out: cout floats on the HOST. */
-int sdm_debug_temb_row(sdm_ctx* e, int temb_index, int is_trans, const float* coords4, float* out_host, int cout) {
-  if (e) dev_use(e->device);
-  if (!e || !out_host || temb_index < 0 || temb_index >= (int)e->tembs.size()) return SDM_ERR_INVALID;
-  if (!e->finalized) SDM_FAIL(e, SDM_ERR_STATE, "weights not finalised");
-  int32_t it = is_trans;
-  TRY(prepare_variants(e, 1, &it, coords4, 4, 0));
-  Variant v; v.trans = 1 - is_trans; v.kind = 0; v.c.assign(4, 0.0f);
-  const float def[4] = {0.f, 0.f, 1.f, 1.f};
-  for (int k = 0; k < 4; ++k) v.c[k] = coords4 ? coords4[k] : def[k];
-  int idx = -1;
-  for (size_t i = 0; i < e->variants.size(); ++i) if (e->variants[i] == v) idx = (int)i;
-  const TembL& t = e->tembs[(size_t)temb_index];
-  if (idx < 0 || cout > t.cout) SDM_FAIL(e, SDM_ERR_INVALID, "temb row: variant not found / bad cout");
-  SDM_CHECK_DEV(e, dev_memcpy_d2h(out_host, t.table + (size_t)idx * t.cout_pad, (size_t)cout * 4, e->stream));
-  SDM_CHECK_DEV(e, dev_sync(e->stream));
-  return SDM_OK;
-}
-
-/* Bench/ablation helper (not used by the engine): times `iters` launches of one conv with HIP events; returns ms per launch
- * (negative on error).  ablate bits: see ConvParams::ablate. */
-/* bench only: ms per launch of the plane-fed GEMM (k_gemm.h) on random operands: M rows, K -> O, epilogue `epi` (0 fp32, 1 GEGLU, 2 q|k|v planes, 3 P3, 4 fp32 +
- * statistics; bit 8: + fp32 residual).  The row tile follows the option gemm_p3_tile. */
-float sdm_bench_gemm_p3(sdm_ctx* e, long M, int K, int O, int epi_flags, int iters) {
-  if (e) dev_use(e->device);
-  if (!e || K % 32 || O % 64) return -1.f;
-#ifdef SDM_EMU
-  (void)M; (void)epi_flags; (void)iters;
-  return -1.f;
-#else
-  const int epi = epi_flags & 255, resf = (epi_flags >> 8) & 1;
-  void *xf = nullptr, *xp = nullptr, *w3 = nullptr, *bp = nullptr, *out = nullptr, *resb = nullptr, *st = nullptr;
-  const int Cst = epi == 1 ? O / 2 : O;
-  int p_sb = 127 - 8;
-  const size_t w3b = (size_t)K * O * 4;
-  if (dev_malloc(&xf, (size_t)M * K * 4) || dev_malloc(&xp, p3_rows_pad((size_t)M) * K * 3) || dev_malloc(&w3, w3b) || dev_malloc(&bp, (size_t)O * 4) ||
-      dev_malloc(&out, p3_rows_pad((size_t)M) * Cst * 4 + 256)) return -2.f;
-  if (resf && dev_malloc(&resb, (size_t)M * Cst * 4)) return -2.f;
-  if (epi == 4 && dev_malloc(&st, ((size_t)(M + 63) / 64 * 2 + 8) * O * 8)) return -2.f;
-  SDM_LAUNCH(fill_random_f32_kernel, dim3(4096), dim3(256), 0, e->stream, (float*)xf, (long)M * K, 5u, 1.0f);
-  SDM_LAUNCH(to_p3_kernel, dim3(4096), dim3(256), 0, e->stream, (const float*)xf, (unsigned char*)xp, M, K);
-  {   // weights: random fp32 [O][K] -> K16 hi | lo -> W3, as a model layer
-    void *wf = nullptr, *wp = nullptr, *wl = nullptr;
-    if (dev_malloc(&wf, (size_t)K * O * 4) || dev_malloc(&wp, (size_t)K * O * 2) || dev_malloc(&wl, (size_t)K * O * 2)) return -2.f;
-    SDM_LAUNCH(fill_random_f32_kernel, dim3(2048), dim3(256), 0, e->stream, (float*)wf, (long)K * O, 17u, 0.05f);
-    ConvL L;
-    L.name = "bench"; L.ntaps = 1; L.I = K; L.O = O; L.Cin_pad = K; L.Cout_pad = O; L.split = 1; L.w_exp = kSplitWeightExp;
-    L.w = (half_t*)wp; L.w_lo = (half_t*)wl; L.w3 = (unsigned char*)w3; L.w3_bytes = w3b;
-    SDM_LAUNCH(pack_conv_weight_kernel, dim3((unsigned)std::min<size_t>(((size_t)K * O + 255) / 256, 65535)), dim3(256), 0, e->stream, (const float*)wf, L.w, O, K, 1, K, O,
-               0, 0, 0, ldexpf(1.0f, L.w_exp), L.w_lo);
-    std::vector<ConvL*> one{&L};
-    if (derive_layers(e, one) != 0) return -2.f;
-    dev_free(wf); dev_free(wp); dev_free(wl);
-    p_sb = 127 - L.f8_exp;
-  }
-  if (resf) SDM_LAUNCH(fill_random_f32_kernel, dim3(4096), dim3(256), 0, e->stream, (float*)resb, (long)M * Cst, 31u, 1.0f);
-  dev_memset(bp, 0, (size_t)O * 4, e->stream);
-  GemmP3Params p;
-  memset(&p, 0, sizeof(p));
-  p.M = M; p.K = K; p.a_hi = (const half_t*)xp; p.a_xl = (const unsigned char*)xp + p3_rows_pad((size_t)M) * K * 2;
-  p.w = (const unsigned char*)w3; p.N = O; p.bias = (const float*)bp; p.out = out; p.ldo = Cst; p.n_valid = Cst;
-  p.out_lo_off = epi == 2 ? (size_t)M * Cst : p3_rows_pad((size_t)M) * Cst * 2; p.lo_cols = (O / 3) * 2;
-  if (resf) { p.res = (const float*)resb; p.ldr = Cst; }
-  if (epi == 4) { p.stats = (float*)st; p.rows_per_img = (int)M; }
-  p.sa = 127 - 11; p.sb = p_sb; p.ablate = opt("gemm_p3_ablate");
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  launch_gemm_p3(p, epi, e->stream);
-  (void)hipEventRecord(e0, (hipStream_t)e->stream);
-  for (int i = 0; i < iters; ++i) launch_gemm_p3(p, epi, e->stream);
-  (void)hipEventRecord(e1, (hipStream_t)e->stream);
-  (void)hipEventSynchronize(e1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  const hipError_t le = hipGetLastError();
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  dev_free(xf); dev_free(xp); dev_free(w3); dev_free(bp); dev_free(out); if (resb) dev_free(resb); if (st) dev_free(st);
-  if (le != hipSuccess) { e->err = hipGetErrorString(le); return -3.f; }
-  return ms / (float)iters;
-#endif
-}
-
-float sdm_bench_conv(sdm_ctx* e, int N, int H, int W, int Cin, int Cout, int ntaps, int stride, int in_f32, int tile_cfg, int ablate, int iters) {
-  // in_f32: bit 0 = fp32 activations, bit 1 = split-precision kernel (implies fp32), bit 2 = fused GroupNorm+SiLU staging,
-  // bit 3 = producer / consumer form of the split-precision DMA kernel
-  const int split = (in_f32 >> 1) & 1, gnf = (in_f32 >> 2) & 1, pcf = (in_f32 >> 3) & 1, f8f = (in_f32 >> 4) & 1;      // bit 4: fp8-residual kernel
-  // bits 5-7: what the engine's ResBlock convs do in the default precision - fp32 output, fp32 residual, GroupNorm statistics of the consumer
-  const int of32 = (in_f32 >> 5) & 1, resf = (in_f32 >> 6) & 1, statf = (in_f32 >> 7) & 1;
-  in_f32 = (in_f32 & 1) | split;
-  if (e) dev_use(e->device);
-  if (!e) return -1.f;
-#ifdef SDM_EMU
-  return -1.f;
-#else
-  ConvL L;
-  L.name = "bench"; L.ntaps = ntaps; L.I = Cin; L.O = Cout; L.Cin_pad = rup(Cin, 16); L.Cout_pad = rup(Cout, 32);
-  void *wp = nullptr, *bp = nullptr, *in = nullptr, *out = nullptr, *wl = nullptr, *gnt = nullptr, *resb = nullptr, *statb = nullptr;
-  const int Ho = stride == 2 ? H / 2 : H, Wo = stride == 2 ? W / 2 : W;
-  const size_t wbytes = (size_t)L.Cin_pad * ntaps * L.Cout_pad * 2, inb = (size_t)N * H * W * L.Cin_pad * (in_f32 ? 4 : 2),
-               outb = (size_t)N * Ho * Wo * L.Cout_pad * (of32 ? 4 : 2);
-  if (dev_malloc(&wp, wbytes) || dev_malloc(&bp, (size_t)L.Cout_pad * 4) || dev_malloc(&in, inb) || dev_malloc(&out, outb)) return -2.f;
-  if (resf) {
-    if (dev_malloc(&resb, (size_t)N * Ho * Wo * L.Cout_pad * 4)) return -2.f;
-    SDM_LAUNCH(fill_random_f32_kernel, dim3(4096), dim3(256), 0, e->stream, (float*)resb, (long)N * Ho * Wo * L.Cout_pad, 31u, 1.0f);
-  }
-  if (statf && dev_malloc(&statb, (size_t)N * (sdm_cdiv(Ho, 4) * sdm_cdiv(Wo, 8) * 4 + 64) * L.Cout_pad * 8)) return -2.f;      // enough partial rows for every tile cfg
-  if (split) { if (dev_malloc(&wl, wbytes)) return -2.f; SDM_LAUNCH(fill_random_f16_kernel, dim3(2048), dim3(256), 0, e->stream, (half_t*)wl, (long)(wbytes / 2), 19u, 0.0001f); }
-  if (gnf) {      // scale = 1, shift = 0 table [N][Cin] x 2
-    if (dev_malloc(&gnt, (size_t)N * L.Cin_pad * 8)) return -2.f;
-    SDM_LAUNCH(fill_random_f32_kernel, dim3(64), dim3(256), 0, e->stream, (float*)gnt, (long)N * L.Cin_pad * 2, 23u, 1.0f);
-  }
-  dev_memset(bp, 0, (size_t)L.Cout_pad * 4, e->stream);
-  SDM_LAUNCH(fill_random_f16_kernel, dim3(2048), dim3(256), 0, e->stream, (half_t*)wp, (long)(wbytes / 2), 17u, 0.05f);
-  if (in_f32) SDM_LAUNCH(fill_random_f32_kernel, dim3(4096), dim3(256), 0, e->stream, (float*)in, (long)(inb / 4), 5u, 1.0f);
-  else SDM_LAUNCH(fill_random_f16_kernel, dim3(4096), dim3(256), 0, e->stream, (half_t*)in, (long)(inb / 2), 5u, 1.0f);
-  L.w = (half_t*)wp; L.b = (float*)bp;
-  T tin, tout;
-  tin.p = in; tin.N = N; tin.H = H; tin.W = W; tin.C = L.Cin_pad; tin.f32 = in_f32;
-  tout.p = out; tout.N = N; tout.H = Ho; tout.W = Wo; tout.C = L.Cout_pad; tout.f32 = 0;
-  ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.in0 = in; p.C0 = L.Cin_pad; p.in_f32 = in_f32; p.N = N; p.Hin = H; p.Win = W; p.Hout = Ho; p.Wout = Wo; p.pad_t = p.pad_l = 1;
-  p.M = (long)N * Ho * Wo; p.w = L.w; p.bias = L.b; p.Cout_pad = L.Cout_pad; p.out = out; p.Cout_store = L.Cout_pad; p.Cout_valid = L.Cout_pad;
-  p.out_scale = 1.f; p.ablate = ablate & 255; p.acc_scale = split ? ldexpf(1.0f, -kSplitWeightExp) : 1.f;
-  p.out_f32 = of32; p.epi_mode = conv_epi_mode(); p.xtile = conv_xtile_enabled() ? 1 : 0;
-  if (resf) { p.res = resb; p.res_f32 = 1; p.res_C = L.Cout_pad; }
-  if (statf) p.stats = (float*)statb;
-  void* wdm = nullptr;
-  const bool bench_dma_off = opt("conv_dma") == 0;
-  if (!bench_dma_off && ntaps == 9 && stride == 1 && L.Cout_pad >= 128) {
-    const size_t nb = wbytes * (split ? 2 : 1);
-    if (dev_malloc(&wdm, nb)) return -2.f;
-    SDM_LAUNCH(fill_random_f16_kernel, dim3(2048), dim3(256), 0, e->stream, (half_t*)wdm, (long)(nb / 2), 29u, 0.05f);
-    p.w_dma = (const half_t*)wdm;
-  }
-  if (split) p.w_lo = (const half_t*)wl;
-  p.pc = (split && p.w_dma && pcf) ? 1 : 0;
-  if (split && p.w_dma && f8f && L.Cin_pad % 32 == 0) { p.f8 = 1; p.f8_sa = 127 - 11; p.f8_sb = 127 - kSplitWeightExp; p.acc_scale = 1.f; }
-  if (split && ntaps == 1 && f8f && L.Cin_pad % 32 == 0 && L.Cout_pad >= 128) {      // 1x1 GEMM on the fp8-residual kernel (tile cfg 4)
-    if (dev_malloc(&wdm, wbytes * 2)) return -2.f;
-    SDM_LAUNCH(fill_random_f16_kernel, dim3(2048), dim3(256), 0, e->stream, (half_t*)wdm, (long)wbytes, 29u, 0.05f);
-    p.w_dma = (const half_t*)wdm; p.f8 = 1; p.f8_sa = 127 - 11; p.f8_sb = 127 - kSplitWeightExp; p.acc_scale = 1.f;
-  }
-  if (gnf) { p.gn_scale = (const float*)gnt; p.gn_shift = (const float*)gnt + (size_t)N * L.Cin_pad; p.gn_silu = 1; }
-  int cfg = tile_cfg >= 0 ? tile_cfg : conv_pick_cfg(ntaps, stride, p);
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  // split-K as the engine would run it (option conv_splitk: -1 by shape, n forced); the partial sums + the reduce kernel are inside the timed loop
-  int ksplit = 1;
-  void* wsb = nullptr;
-  if (!(p.w_dma && ((ntaps == 9 && stride == 1 && cfg == 0) || (ntaps == 1 && cfg == 4)))) ksplit = conv_pick_ksplit(ntaps, stride, cfg, p);      // register-staged kernels only
-  if (ksplit > 1 && dev_malloc(&wsb, (size_t)ksplit * p.M * p.Cout_pad * 4)) return -2.f;
-  if (ksplit > 1) fprintf(stderr, "[bench_conv] split-K %d\n", ksplit);
-  auto run = [&](const ConvParams& pp) { if (ksplit > 1) launch_conv_splitk(ntaps, stride, cfg, pp, ksplit, (float*)wsb, e->stream); else launch_conv(ntaps, stride, cfg, pp, e->stream); };
-  run(p);
-  if (ablate & 256) {      // one traced launch of the F8 3x3 kernel (-DSDM_CONV_TRACE builds): the LDS-parked shader-clock stamps of the first 16 blocks -> stderr
-    void* tr = nullptr;
-    const size_t tb = (size_t)16 * 2 * 384 * 4;
-    if (dev_malloc(&tr, tb) == 0) {
-      dev_memset(tr, 0, tb, e->stream);
-      ConvParams pt = p; pt.trace = (unsigned int*)tr; pt.ablate = ablate & 255; pt.trace_skip = (ablate >> 9) & 7; pt.trace_b0 = ((ablate >> 12) & 0xFF) * 256;
-      launch_conv(ntaps, stride, cfg, pt, e->stream);
-      std::vector<unsigned int> h(tb / 4);
-      (void)dev_memcpy_d2h(h.data(), tr, tb, e->stream);
-      (void)dev_sync(e->stream);
-      for (int b = 0; b < 16; ++b)
-        for (int r = 0; r < 2; ++r) {
-          const unsigned int* ev = &h[((size_t)b * 2 + r) * 384];
-          const int n = (int)ev[383] < 383 ? (int)ev[383] : 383;
-          if (!n) continue;
-          fprintf(stderr, "[trace] block %d %s n=%d:", pt.trace_b0 + b, r ? "producer" : "consumer", n);
-          for (int i = 0; i < n; ++i) fprintf(stderr, " %u", ev[i]);
-          fprintf(stderr, "\n");
-        }
-      dev_free(tr);
-    }
-    p.ablate = ablate & 255;
-  }
-  (void)hipEventRecord(e0, (hipStream_t)e->stream);
-  for (int i = 0; i < iters; ++i) run(p);
-  (void)hipEventRecord(e1, (hipStream_t)e->stream);
-  (void)hipStreamSynchronize((hipStream_t)e->stream);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  dev_free(wp); dev_free(bp); dev_free(in); dev_free(out);
-  if (wl) dev_free(wl);
-  if (gnt) dev_free(gnt);
-  if (wdm) dev_free(wdm);
-  if (resb) dev_free(resb);
-  if (statb) dev_free(statb);
-  if (wsb) dev_free(wsb);
-  return ms / (float)iters;
-#endif
-}
-
-/* Bench/ablation helper for the d=64 attention kernel (not used by the engine). */
-float sdm_bench_attn(sdm_ctx* e, int B, int heads, int Lq, int Lk, int qt, int ablate, int iters) {
-  if (e) dev_use(e->device);
-  if (!e) return -1.f;
-#ifdef SDM_EMU
-  return -1.f;
-#else
-  if (qt & 64) {      // bit 64: the d = 512 single-head kernel (VAE mid-block), ablate = its compile-time ABL mask
-    const int ldvt5 = rup(Lk, 64);
-    void *q5 = nullptr, *k5 = nullptr, *v5 = nullptr, *o5 = nullptr;
-    if (dev_malloc(&q5, (size_t)B * Lq * 512 * 2) || dev_malloc(&k5, (size_t)B * Lk * 512 * 2) || dev_malloc(&v5, (size_t)B * 512 * ldvt5 * 2) || dev_malloc(&o5, (size_t)B * Lq * 512 * 4)) return -2.f;
-    SDM_LAUNCH(fill_random_f16_kernel, dim3(4096), dim3(256), 0, e->stream, (half_t*)q5, (long)B * Lq * 512, 3u, 0.3f);
-    SDM_LAUNCH(fill_random_f16_kernel, dim3(4096), dim3(256), 0, e->stream, (half_t*)k5, (long)B * Lk * 512, 7u, 0.3f);
-    SDM_LAUNCH(fill_random_f16_kernel, dim3(4096), dim3(256), 0, e->stream, (half_t*)v5, (long)B * 512 * ldvt5, 11u, 1.0f);
-    AttnParams p5;
-    memset(&p5, 0, sizeof(p5));
-    p5.q = (const half_t*)q5; p5.q_bs = (long)Lq * 512; p5.ldq = 512; p5.k = (const half_t*)k5; p5.k_bs = (long)Lk * 512; p5.ldk = 512;
-    p5.vt = (const half_t*)v5; p5.vt_hs = (long)512 * ldvt5; p5.vt_bs = p5.vt_hs; p5.ldvt = ldvt5; p5.o = (half_t*)o5; p5.o_bs = (long)Lq * 512; p5.ldo = 512; p5.o_f32 = 1;
-    p5.Lq = Lq; p5.Lk = Lk; p5.scale_log2e = 0.0441941738f * SDM_LOG2E;
-    p5.batch = B; p5.heads = 1; p5.nq_blocks = sdm_cdiv(Lq, 128); p5.q_chunks = 8;
-    const unsigned nb5 = (unsigned)(B * p5.q_chunks * sdm_cdiv(p5.nq_blocks, p5.q_chunks));
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    for (int i = 0; i <= iters; ++i) {
-      if (i == 1) (void)hipEventRecord(e0, (hipStream_t)e->stream);
-#define SDM_D512_ABL(A) case A: { auto kp = attn_d512_kernel<A>; SDM_SET_SMEM(kp, ATTN512P_SMEM); SDM_LAUNCH(kp, dim3(nb5), dim3(512), ATTN512P_SMEM, e->stream, p5); } break;
-      switch (ablate) { SDM_D512_ABL(0) SDM_D512_ABL(1) SDM_D512_ABL(6) SDM_D512_ABL(7) SDM_D512_ABL(8) SDM_D512_ABL(32) SDM_D512_ABL(40) SDM_D512_ABL(41) default: break; }
-#undef SDM_D512_ABL
-    }
-    (void)hipEventRecord(e1, (hipStream_t)e->stream);
-    (void)hipStreamSynchronize((hipStream_t)e->stream);
-    float ms5 = 0.f;
-    (void)hipEventElapsedTime(&ms5, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    dev_free(q5); dev_free(k5); dev_free(v5); dev_free(o5);
-    return ms5 / (float)iters;
-  }
-  const int C = heads * 64, ldvt = rup(Lk, 64);
-  const int prec = (qt & 2) ? 1 : 0, nw8 = (qt & 4) ? 1 : 0;          // qt bits: 2 = split-precision variant (hi | lo planes, fp32 output), 4 = 8-wave blocks
-  void *q = nullptr, *k = nullptr, *vt = nullptr, *o = nullptr;
-  if (dev_malloc(&q, (size_t)B * Lq * C * 2 * (1 + prec)) || dev_malloc(&k, (size_t)B * Lk * C * 2 * (1 + prec)) ||
-      dev_malloc(&vt, (size_t)B * heads * 64 * ldvt * 2 * (1 + prec)) || dev_malloc(&o, (size_t)B * Lq * C * (prec ? 4 : 2) + 4096)) return -2.f;
-  if (prec) {
-    SDM_LAUNCH(fill_random_f16_kernel, dim3(4096), dim3(256), 0, e->stream, (half_t*)q + (size_t)B * Lq * C, (long)B * Lq * C, 13u, 0.0003f);
-    SDM_LAUNCH(fill_random_f16_kernel, dim3(4096), dim3(256), 0, e->stream, (half_t*)k + (size_t)B * Lk * C, (long)B * Lk * C, 17u, 0.0003f);
-    SDM_LAUNCH(fill_random_f16_kernel, dim3(4096), dim3(256), 0, e->stream, (half_t*)vt + (size_t)B * heads * 64 * ldvt, (long)B * heads * 64 * ldvt, 19u, 0.0003f);
-  }
-  if (prec && (qt & 16)) {      // pair planes: random fp16 bit patterns would hold e5m2 NaNs; zero residual pairs time the same instructions
-    (void)hipMemsetAsync((half_t*)q + (size_t)B * Lq * C, 0, (size_t)B * Lq * C * 2, (hipStream_t)e->stream);
-    (void)hipMemsetAsync((half_t*)k + (size_t)B * Lk * C, 0, (size_t)B * Lk * C * 2, (hipStream_t)e->stream);
-  }
-  SDM_LAUNCH(fill_random_f16_kernel, dim3(4096), dim3(256), 0, e->stream, (half_t*)q, (long)B * Lq * C, 3u, 1.0f);
-  SDM_LAUNCH(fill_random_f16_kernel, dim3(4096), dim3(256), 0, e->stream, (half_t*)k, (long)B * Lk * C, 7u, 1.0f);
-  SDM_LAUNCH(fill_random_f16_kernel, dim3(4096), dim3(256), 0, e->stream, (half_t*)vt, (long)B * heads * 64 * ldvt, 11u, 1.0f);
-  AttnParams p;
-  memset(&p, 0, sizeof(p));
-  p.q = (const half_t*)q; p.q_bs = (long)Lq * C; p.ldq = C; p.k = (const half_t*)k; p.k_bs = (long)Lk * C; p.ldk = C;
-  p.vt = (const half_t*)vt; p.vt_hs = (long)64 * ldvt; p.vt_bs = heads * p.vt_hs; p.ldvt = ldvt; p.o = (half_t*)o; p.o_bs = (long)Lq * C; p.ldo = C;
-  p.Lq = Lq; p.Lk = Lk; p.scale_log2e = 0.125f * SDM_LOG2E; p.ablate = ablate;
-  if (prec) { p.q_lo = (long)B * Lq * C; p.k_lo = (long)B * Lk * C; p.vt_lo = (long)B * p.vt_bs; p.o_f32 = 1; }
-  p.batch = B; p.heads = heads; p.nq_blocks = sdm_cdiv(Lq, nw8 ? 256 : 128); p.q_chunks = 8;
-  const unsigned nblk = (unsigned)(B * heads * p.q_chunks * sdm_cdiv(p.nq_blocks, p.q_chunks));
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  for (int i = 0; i <= iters; ++i) {
-    if (i == 1) (void)hipEventRecord(e0, (hipStream_t)e->stream);
-    if (qt & 16) {      // bit 16: the ping-pong kernel (pair planes as the engine's self- and cross-attentions), ablate = its compile-time ABL mask
-      p.pp_flags = (qt & 32) ? 0 : 1;
-      p.part_ml = (float*)((unsigned char*)o + (size_t)B * Lq * C * 4);      // (ablate 64: the segment trace lands behind the output)
-      if (qt & 128) p.pp_flags |= 2;
-#define SDM_PP_ABL(A) case A: { auto kp = attn_d64_pp_kernel<A, 0, 0>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk), dim3(512), ATTN64PP_SMEM + 4096, e->stream, p); } break;
-#define SDM_PP_DS(A, S, V) case V: { auto kp = attn_d64_pp_kernel<A, 0, 0, 0, S, 0>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk), dim3(512), ATTN64PP_SMEM + 4096, e->stream, p); } break;
-#define SDM_PP_KE(K, V) case V: { auto kp = attn_d64_pp_kernel<0, 0, 0, K, 1, 0>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk), dim3(512), ATTN64PP_SMEM, e->stream, p); } break;
-      switch (ablate) { SDM_PP_ABL(0) SDM_PP_ABL(1) SDM_PP_ABL(6) SDM_PP_ABL(7) SDM_PP_ABL(8) SDM_PP_ABL(32) SDM_PP_ABL(56) SDM_PP_ABL(63)
-                        SDM_PP_KE(-1, 100) SDM_PP_KE(2, 101) SDM_PP_KE(1, 102) SDM_PP_ABL(64)
-                        SDM_PP_DS(0, 0, 110) SDM_PP_DS(0, 1, 111) SDM_PP_DS(0, 2, 112) SDM_PP_DS(0, 3, 113) SDM_PP_DS(64, 0, 114) SDM_PP_DS(64, 2, 116) SDM_PP_DS(64, 3, 117) default: break; }      // 100-102: the other fragment / DMA placements (KE), no ablation
-#undef SDM_PP_ABL
-#undef SDM_PP_KE
-#undef SDM_PP_DS
-    }
-    else if (prec && (qt & 8) && nw8) { auto kp = attn_d64_kernel<1, 2, 8>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk), dim3(512), ATTN64P_SMEM, e->stream, p); }      // bit 8: P.V on plain fp16
-    else if (prec && (qt & 8)) { auto kp = attn_d64_kernel<1, 2, 4>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk), dim3(256), ATTN64P_SMEM, e->stream, p); }
-    else if (prec && nw8) { auto kp = attn_d64_kernel<1, 1, 8>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk), dim3(512), ATTN64P_SMEM, e->stream, p); }
-    else if (prec) { auto kp = attn_d64_kernel<1, 1, 4>; SDM_SET_SMEM(kp, 160 * 1024); SDM_LAUNCH(kp, dim3(nblk), dim3(256), ATTN64P_SMEM, e->stream, p); }
-    else if (nw8) { auto kf = attn_d64_kernel<1, 0, 8>; SDM_SET_SMEM(kf, 160 * 1024); SDM_LAUNCH(kf, dim3(nblk), dim3(512), ATTN64P_SMEM, e->stream, p); }
-    else { SDM_LAUNCH((attn_d64_kernel<1, 0, 4>), dim3(nblk), dim3(256), ATTN64_SMEM, e->stream, p); }
-  }
-  (void)hipEventRecord(e1, (hipStream_t)e->stream);
-  (void)hipStreamSynchronize((hipStream_t)e->stream);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  if ((qt & 16) && (ablate == 64 || (ablate >= 114 && ablate <= 117))) {      // segment stamps of waves 0 (half A) and 4 (half B) of block 0: averages over tiles 4 .. 51 of the last launch
-    std::vector<unsigned long long> tr(2 * 8 * 28);
-    (void)hipMemcpy(tr.data(), (unsigned char*)o + (size_t)B * Lq * C * 4, tr.size() * 8, hipMemcpyDeviceToHost);
-    for (int g = 0; g < 2; ++g) {
-      double dm = 0, sm = 0, vr = 0, wa = 0, mx = 0, wb = 0; int n = 0;
-      for (int t = 5; t < 27; ++t) {
-        const unsigned long long* c = &tr[(size_t)g * 224 + (size_t)t * 8];
-        const unsigned long long prev3 = tr[(size_t)g * 224 + (size_t)(t - 1) * 8 + 3];
-        dm += (double)(c[4] - prev3); sm += (double)(c[5] - c[4]); vr += (double)(c[0] - c[5]); wa += (double)(c[1] - c[0]); mx += (double)(c[2] - c[1]); wb += (double)(c[3] - c[2]); ++n;
-      }
-      fprintf(stderr, "[attn_pp trace] wave %d: DMA issue %.0f | softmax VALU %.0f | V^T reads + lgkmcnt(0) %.0f | wait at barrier %.0f | matrix segment %.0f | wait at barrier %.0f  (cycles per tile, mean of %d tiles; each stamp costs an s_memtime round trip)\n",
-              g * 4, dm / n, sm / n, vr / n, wa / n, mx / n, wb / n, n);
-    }
-  }
-  dev_free(q); dev_free(k); dev_free(vt); dev_free(o);
-  return ms / (float)iters;
-#endif
-}
-
-int sdm_op_groupnorm(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1, int in_f32, int N, int HW, int groups, const float* gamma,
-                     const float* beta, float eps, int silu, void* out) {
-  if (e) dev_use(e->device);
-  if (!e || !in0 || !out) return SDM_ERR_INVALID;
-  return run_two_pass(e, [&]() { return op_groupnorm_raw(e, in0, in1, C0, C1, in_f32, N, HW, groups, gamma, beta, eps, silu, out, 0); });
-}
-
-int sdm_op_layernorm(sdm_ctx* e, const void* x, int in_f32, long rows, int C, const float* gamma, const float* beta, float eps, void* out) {
-  if (e) dev_use(e->device);
-  if (!e || !x || !out) return SDM_ERR_INVALID;
-  if (C % 64 || C > 64 * SDM_LN_MAXV) SDM_FAIL(e, SDM_ERR_INVALID, "layernorm: unsupported C %d", C);
-  SDM_LAUNCH(layernorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, e->stream, x, in_f32, gamma, beta, out, 0, rows, C, eps);
-  SDM_CHECK_DEV(e, dev_sync(e->stream));
-  return 0;
-}
-
-int sdm_op_attention(sdm_ctx* e, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* bias, int B, int heads,
-                     int Lq, int Lk, int D, void* out, int ldo) {
-  if (e) dev_use(e->device);
-  if (!e || !q || !k || !v || !out) return SDM_ERR_INVALID;
-  return run_two_pass(e, [&]() {
-    T b2 = talloc(e, B, 1, 1, Lk, 1);
-    AttnPrec ap; ap.has_bias = bias != nullptr;
-    if (bias && !e->dry) {
-      // natural-log bias (reference domain) -> log2 domain used by the kernel
-      SDM_LAUNCH(scale_copy_kernel, dim3(sdm_cdiv(B * Lk, 256)), dim3(256), 0, e->stream, bias, (float*)b2.p, (long)B * Lk, SDM_LOG2E);
-    }
-    int rc = op_attention_raw(e, (const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)v, ldv, bias ? (const float*)b2.p : nullptr,
-                              B, heads, Lq, Lk, D, (half_t*)out, ldo, false, nullptr, ap);
-    tfree(e, b2);
-    return rc;
-  });
-}
-
-/* Split-precision d = 64 attention cores as the default precision runs them.  q [B,Lq,heads*64], k / v [B,Lk,heads*64]: contiguous fp32
- * DEVICE tensors.  They are first turned into the operand planes the producing GEMMs write in the engine (split_planes_kernel: fp16 hi plane
- * + fp16 lo plane, or + e5m2 pair plane when the Q.K^T residual terms run on fp8 MFMAs - the default; the option attn_f8 = 0 selects the former),
- * with the logit scale d^-1/2 * log2(e) applied to Q as the engine's to_q weights do; fp32 output [B,Lq,heads*64].  Test hook. */
-int sdm_op_attention_split(sdm_ctx* e, const float* q, const float* k, const float* v, const float* bias, int B, int heads, int Lq, int Lk, float* out) {
-  return sdm_op_attention_split_ex(e, q, k, v, bias, nullptr, B, heads, Lq, Lk, 0, out, nullptr);
-}
-
-int sdm_op_attention_split_ex(sdm_ctx* e, const float* q, const float* k, const float* v, const float* bias, const int* tiles, int B, int heads, int Lq,
-                              int Lk, int out_p3, float* out, void* planes) {
-  if (e) dev_use(e->device);
-  if (!e || !q || !k || !v || !out) return SDM_ERR_INVALID;
-  if (out_p3 < 0 || out_p3 > 2 || (tiles && !bias)) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_attention_split_ex: out_p3 0..2; a tile list needs the bias");
-  const int C = heads * 64;
-  const int mode = (attn_f8_enabled() && !opt("attn_pv_split")) ? 3 : 2;
-  return run_two_pass(e, [&]() -> int {
-    T b2 = talloc(e, B, 1, 1, Lk, 1);
-    T qp = talloc(e, B, 1, Lq, C, mode), kp = talloc(e, B, 1, Lk, C, mode), vp = talloc(e, B, 1, Lk, C, mode);
-    const long nq = (long)B * Lq * C, nk = (long)B * Lk * C;
-    if (!e->dry) {
-      if (bias) SDM_LAUNCH(scale_copy_kernel, dim3(sdm_cdiv(B * Lk, 256)), dim3(256), 0, e->stream, bias, (float*)b2.p, (long)B * Lk, SDM_LOG2E);
-      SDM_LAUNCH(split_planes_kernel, dim3((unsigned)((nq / 4 + 255) / 256)), dim3(256), 0, e->stream, q, (half_t*)qp.p, (half_t*)qp.p + nq, nq, 0.125f * SDM_LOG2E, mode);
-      SDM_LAUNCH(split_planes_kernel, dim3((unsigned)((nk / 4 + 255) / 256)), dim3(256), 0, e->stream, k, (half_t*)kp.p, (half_t*)kp.p + nk, nk, 1.0f, mode);
-      SDM_LAUNCH(split_planes_kernel, dim3((unsigned)((nk / 4 + 255) / 256)), dim3(256), 0, e->stream, v, (half_t*)vp.p, (half_t*)vp.p + nk, nk, 1.0f, 2);
-    }
-    // out_p3 = 1: the planes written by the kernels (the engine's default); 2: an fp32 result, then to_p3_kernel
-    T to, pl;
-    if (out_p3) to = talloc(e, B, 1, Lq, C, out_p3 == 1 ? kFmtP3 : 1);
-    AttnPrec ap; ap.prec = mode - 1; ap.q_lo = nq; ap.k_lo = nk; ap.v_lo = nk; ap.out_f32 = 1; ap.out_p3 = out_p3 == 1;
-    ap.has_bias = bias != nullptr; ap.has_tiles = tiles != nullptr;
-    TRY(op_attention_raw(e, (const half_t*)qp.p, C, (const half_t*)kp.p, C, (const half_t*)vp.p, C, bias ? (const float*)b2.p : nullptr, B, heads, Lq, Lk, 64,
-                         out_p3 ? to.p : (void*)out, C, true, tiles, ap));
-    if (out_p3 == 2) TRY(op_to_p3(e, to, &pl));
-    const T& p3 = out_p3 == 2 ? pl : to;
-    if (out_p3 && !e->dry) {
-      SDM_LAUNCH(from_p3_kernel, dim3((unsigned)std::min<long>(((long)B * Lq * C + 255) / 256, 1 << 20)), dim3(256), 0, e->stream, (const unsigned char*)p3.p, out,
-                 (long)B * Lq, C);
-      if (planes) SDM_CHECK_DEV(e, dev_memcpy_d2d(planes, p3.p, p3_rows_pad((size_t)B * Lq) * C * 3, e->stream));
-    }
-    if (out_p3 == 2) tfree(e, pl);
-    if (out_p3) tfree(e, to);
-    tfree(e, vp); tfree(e, kp); tfree(e, qp); tfree(e, b2);
-    return 0;
-  });
-}
-
-int sdm_debug_attn_plan(int B, int heads, int Lq, int Lk, int D, int prec, int out_f32, int has_bias, int has_tiles, int cus, char* kernel, int cap,
-                        int* nsplit) {
-  if (B < 1 || heads < 1 || Lq < 1 || Lk < 1 || cus < 1 || prec < 0 || prec > 2 || !(D == 64 || (D == 512 && heads == 1 && !prec))) return SDM_ERR_INVALID;
-  OptReadLock opt_lock;
-  const AttnPlan pl = attn_plan(B, heads, Lq, Lk, D, prec, out_f32, has_bias != 0, has_tiles != 0, cus);
-  if (kernel && cap > 0) snprintf(kernel, (size_t)cap, "%s", kAttnKernels[pl.kernel].counter);
-  if (nsplit) *nsplit = pl.nsplit;
-  return SDM_OK;
-}
-
-int sdm_op_resize_aa(sdm_ctx* e, const float* in, int P, int Hin, int Win, float* out, int Hout, int Wout) {
-  if (e) dev_use(e->device);
-  if (!e || !in || !out) return SDM_ERR_INVALID;
-  SDM_LAUNCH(resize_planes_kernel, dim3((unsigned)(((long)P * Hout * Wout + 255) / 256)), dim3(256), 0, e->stream, in, out, P, Hin, Win, Hout, Wout, 0);
-  SDM_CHECK_DEV(e, dev_sync(e->stream));
-  return 0;
-}
-
-int sdm_op_mask_bias(sdm_ctx* e, const float* plane, int B, int S, int level, float* out) {
-  if (e) dev_use(e->device);
-  if (!e || !plane || !out) return SDM_ERR_INVALID;
-  const int lk = (S / 8) >> level;
-  SDM_LAUNCH(mask_bias_kernel, dim3(sdm_cdiv(B * lk * lk, 256)), dim3(256), 0, e->stream, plane, out, B, S, S, level, e->cfg.attn_mask_value, 1.0f);
-  SDM_CHECK_DEV(e, dev_sync(e->stream));
-  return 0;
-}
-
 }  // extern "C"
+
+// the single-operator test hooks and the lab / bench helpers of the C ABI: no product path calls them (same translation unit, as the k_*.h kernels)
+#include "sdm_hooks.h"

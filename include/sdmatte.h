@@ -200,7 +200,9 @@ const char* sdm_profile_dump(sdm_ctx* ctx);
 int sdm_profile_get(sdm_ctx* ctx, int i, const char** name, float* ms, int64_t* launches, double* flops, double* bytes);
 
 /* ---- single-operator entry points (parity tests call the same kernels the engine uses) --------------
- * All pointers are DEVICE pointers.  Activations are NHWC; fp16 unless the *_f32 flag says otherwise. */
+ * All pointers are DEVICE pointers.  Activations are NHWC; fp16 unless the *_f32 flag says otherwise.
+ * From here to the end of this header: test hooks and lab / bench helpers that no product path calls, implemented in csrc/sdm_hooks.h
+ * (part of sdm_engine.cpp's translation unit); everything above is the product ABI, implemented in csrc/sdm_engine.cpp. */
 
 /* conv3x3 (ntaps=9) or 1x1/linear (ntaps=1): y = conv(concat(in0,in1)) [*scale] [+bias] [+res] | GEGLU.
  * w: fp32 OIHW [O][I][kh][kw] or [O][I]; I = (C0+C1) real channels.  stride 1|2; pad_mode 0: symmetric pad 1,
