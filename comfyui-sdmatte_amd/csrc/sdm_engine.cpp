@@ -17,6 +17,7 @@
 #include "k_norm.h"
 #include "k_attn.h"
 #include "k_misc.h"
+#include "k_trimap.h"
 #include "../../include/sdmatte.h"
 
 #include <algorithm>
@@ -2115,6 +2116,40 @@ static int run_model(sdm_ctx* e, const T& x16, const T& plane, int B, int SH, in
 }
 
 // ------------------------------------------------------------------------------------------------
+// trimap from a mask (k_trimap.h): mask fp32 [B,H,W] -> the signed column-distance plane (int16 [B,H,W]) -> trimap fp32 [B,H,W]
+// ------------------------------------------------------------------------------------------------
+static int trimap_check(sdm_ctx* e, int B, int H, int W, int erode_px, int dilate_px) {
+  if (B <= 0 || H <= 0 || W <= 0) SDM_FAIL(e, SDM_ERR_INVALID, "trimap from mask: bad mask size %dx%dx%d", B, H, W);
+  if (erode_px < 0 || erode_px > SDM_TRIMAP_MAX_RADIUS || dilate_px < 0 || dilate_px > SDM_TRIMAP_MAX_RADIUS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "trimap from mask: erode_px = %d, dilate_px = %d outside 0 .. %d", erode_px, dilate_px, SDM_TRIMAP_MAX_RADIUS);
+  // one row-kernel block per 256-pixel row segment, in a 1-D grid
+  if ((double)B * H * sdm_cdiv(W, SDM_TRIMAP_ROWS_W) >= 2147483647.0) SDM_FAIL(e, SDM_ERR_INVALID, "trimap from mask: %dx%dx%d is too large", B, H, W);
+  return 0;
+}
+
+// rows per block of the column kernel: tall blocks re-read the least halo, short ones fill the chip at small sizes and keep the LDS under 48 KB
+static int trimap_cols_rows(int B, int H, int W, int R) {
+  int rows = 128;
+  while (rows > 32 && ((long)B * sdm_cdiv(H, rows) * sdm_cdiv(W, SDM_TRIMAP_COLS_W) < 512 || trimap_cols_smem(rows, R) > 48 * 1024)) rows /= 2;
+  return rows;
+}
+
+static void op_trimap(sdm_ctx* e, const float* mask, int B, int H, int W, float threshold, int erode_px, int dilate_px, short* plane, float* trimap) {
+  const int R = std::max(erode_px, dilate_px), rows = trimap_cols_rows(B, H, W, R);
+  const double px = (double)B * H * W;
+  prof_begin(e, "trimap_cols", 0, px * 6);
+  count_kernel("trimap_cols");
+  SDM_LAUNCH(trimap_cols_kernel, dim3((unsigned)(B * sdm_cdiv(H, rows) * sdm_cdiv(W, SDM_TRIMAP_COLS_W))), dim3(256), trimap_cols_smem(rows, R), e->stream, mask, plane,
+             B, H, W, threshold, R, rows);
+  prof_end(e);
+  prof_begin(e, "trimap_rows", 0, px * 6);
+  count_kernel("trimap_rows");
+  SDM_LAUNCH(trimap_rows_kernel, dim3((unsigned)((long)B * H * sdm_cdiv(W, SDM_TRIMAP_ROWS_W))), dim3(256), 0, e->stream, (const short*)plane, trimap, B, H, W,
+             erode_px, dilate_px);
+  prof_end(e);
+}
+
+// ------------------------------------------------------------------------------------------------
 // top-level forward helpers
 // ------------------------------------------------------------------------------------------------
 static int ensure_buf(sdm_ctx* e, void** p, size_t* cap, size_t need) {
@@ -2130,7 +2165,12 @@ static int ensure_buf(sdm_ctx* e, void** p, size_t* cap, size_t need) {
 // node tail (mode 1 only): mask_refine + output composition on the GPU, sdmatte_nodes.py:365-397
 // trimap_constraint stays a double up to the two thresholds: the reference compares fp32 tensors with the Python floats c and
 // 1.0 - c (evaluated in double), i.e. with float32(c) and float32(1.0 - c) - for c = 0.8 the latter is 0.2f, not 1.0f - 0.8f
-struct NodeTail { int output_mode = 0, mask_refine = 0; double c = 0.8; float* matted = nullptr; int TH = 0, TW = 0; int channels() const { return output_mode == 1 ? 4 : 3; } };
+struct NodeTail {
+  int output_mode = 0, mask_refine = 0; double c = 0.8; float* matted = nullptr; int TH = 0, TW = 0;
+  // sdm_apply_matte_mask: the `trimap` argument of forward_impl is a mask, and the trimap is made from it on the device (op_trimap)
+  bool from_mask = false; float threshold = 0.5f; int erode_px = 0, dilate_px = 0; float* trimap_out = nullptr;
+  int channels() const { return output_mode == 1 ? 4 : 3; }
+};
 
 static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* trimap, int B, int H, int W, int S, const int32_t* is_trans,
                         const float* cond, int cond_dim, int cond_kind, bool use_mask, float* out, int ptr_kind, void* stream_arg,
@@ -2159,11 +2199,15 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
   const size_t in_tri = (size_t)B * TH * TW * 4;
   const size_t alpha_bytes = (size_t)B * H * W * 4;
   const size_t out_bytes = alpha_bytes * (tail ? 1 + tail->channels() : 1);      // host hand-over: alpha, then the composed image
+  const bool from_mask = tail && tail->from_mask;
+  const size_t tri_out_bytes = (from_mask && tail->trimap_out) ? in_tri : 0;     // ... then the trimap made from the mask, if the caller wants it
   const float* d_img = image; const float* d_tri = trimap; float* d_out = out;
   float* d_matted = tail ? tail->matted : nullptr;
+  float* d_tri_out = from_mask ? tail->trimap_out : nullptr;
   if (ptr_kind == SDM_PTR_HOST) {
     TRY(ensure_buf(e, &e->io_in, &e->io_in_bytes, in_img + in_tri));
-    TRY(ensure_buf(e, &e->io_out, &e->io_out_bytes, out_bytes));
+    TRY(ensure_buf(e, &e->io_out, &e->io_out_bytes, out_bytes + tri_out_bytes));
+    if (tri_out_bytes) d_tri_out = (float*)((unsigned char*)e->io_out + out_bytes);
     SDM_CHECK_DEV(e, dev_memcpy_h2d(e->io_in, image, in_img, e->stream));
     SDM_CHECK_DEV(e, dev_memcpy_h2d((unsigned char*)e->io_in + in_img, trimap, in_tri, e->stream));
     d_img = (const float*)e->io_in; d_tri = (const float*)((unsigned char*)e->io_in + in_img); d_out = (float*)e->io_out;
@@ -2181,6 +2225,18 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
 #ifndef SDM_EMU
     if (pass == 1) (void)hipEventRecord(e->ev0, (hipStream_t)e->stream);
 #endif
+    T gtri;      // sdm_apply_matte_mask: the trimap of this call, made from the mask in d_tri; it stands in for d_tri from here on
+    const float* tri_in = d_tri;
+    if (from_mask) {
+      T dist = talloc(e, B, TH, TW, 1, 0);      // (2 bytes per pixel: the signed column distances)
+      gtri = talloc(e, B, TH, TW, 1, 1);
+      if (!e->dry) {
+        op_trimap(e, d_tri, B, TH, TW, tail->threshold, tail->erode_px, tail->dilate_px, (short*)dist.p, (float*)gtri.p);
+        if (d_tri_out) SDM_CHECK_DEV(e, dev_memcpy_d2d(d_tri_out, gtri.p, in_tri, e->stream));
+      }
+      tfree(e, dist);
+      tri_in = (const float*)gtri.p;
+    }
     T x16 = talloc(e, 2 * B, SH, SW, 16, e->act_f32);
     T plane = talloc(e, B, SH, SW, 1, 1);
     if (!e->dry) {
@@ -2191,7 +2247,7 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
         SDM_LAUNCH(prep_nchw_kernel, dim3(nb), dim3(256), 0, e->stream, d_img, d_tri, img16, tri16, x16.f32, (float*)plane.p, B, SH, SW);
       } else {
         SDM_LAUNCH(prep_image_kernel, dim3(nb), dim3(256), 0, e->stream, d_img, img16, x16.f32, B, H, W, S);
-        SDM_LAUNCH(prep_trimap_kernel, dim3(nb), dim3(256), 0, e->stream, d_tri, tri16, x16.f32, (float*)plane.p, B, TH, TW, S);
+        SDM_LAUNCH(prep_trimap_kernel, dim3(nb), dim3(256), 0, e->stream, tri_in, tri16, x16.f32, (float*)plane.p, B, TH, TW, S);
       }
     }
     T alpha;
@@ -2204,11 +2260,11 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
         SDM_LAUNCH(resize_planes_kernel, dim3((unsigned)(((long)B * H * W + 255) / 256)), dim3(256), 0, e->stream, (const float*)alpha.p, d_out, B,
                    S, S, H, W, 1);
         if (tail)
-          SDM_LAUNCH(refine_compose_kernel, dim3((unsigned)(((long)B * H * W + 255) / 256)), dim3(256), 0, e->stream, d_img, d_tri, d_out, d_matted,
+          SDM_LAUNCH(refine_compose_kernel, dim3((unsigned)(((long)B * H * W + 255) / 256)), dim3(256), 0, e->stream, d_img, tri_in, d_out, d_matted,
                      (long)B * H * W, tail->output_mode, tail->mask_refine, (float)tail->c, (float)(1.0 - tail->c));
       }
     }
-    tfree(e, alpha); tfree(e, plane); tfree(e, x16);
+    tfree(e, alpha); tfree(e, plane); tfree(e, x16); tfree(e, gtri);
     if (pass == 1) TRY(arena_pass_end(e, 0));
   }
   e->dry = false;
@@ -2218,6 +2274,7 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
   if (ptr_kind == SDM_PTR_HOST) {
     SDM_CHECK_DEV(e, dev_memcpy_d2h(out, e->io_out, alpha_bytes, e->stream));
     if (tail) SDM_CHECK_DEV(e, dev_memcpy_d2h(tail->matted, (unsigned char*)e->io_out + alpha_bytes, out_bytes - alpha_bytes, e->stream));
+    if (tri_out_bytes) SDM_CHECK_DEV(e, dev_memcpy_d2h(tail->trimap_out, (unsigned char*)e->io_out + out_bytes, tri_out_bytes, e->stream));
     SDM_CHECK_DEV(e, dev_sync(e->stream));
   }
 #ifndef SDM_EMU
@@ -2730,6 +2787,81 @@ int sdm_apply_matte_node(sdm_ctx* e, const float* image, const float* trimap, in
   NodeTail tail; tail.output_mode = output_mode; tail.mask_refine = mask_refine ? 1 : 0; tail.c = trimap_constraint; tail.matted = matted;
   tail.TH = trimap_h; tail.TW = trimap_w;
   return forward_impl(e, 1, image, trimap, B, H, W, S, it.data(), nullptr, 4, 0, true, alpha, ptr_kind, stream, &tail);
+}
+
+int sdm_apply_matte_mask(sdm_ctx* e, const float* image, const float* mask, int B, int H, int W, int mask_h, int mask_w, int S, int is_transparent,
+                         float threshold, int erode_px, int dilate_px, int output_mode, int mask_refine, double trimap_constraint, float* alpha,
+                         float* matted, float* trimap_out, int ptr_kind, void* stream) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !mask || !alpha || !matted) return SDM_ERR_INVALID;
+  if (output_mode < 0 || output_mode > 2) SDM_FAIL(e, SDM_ERR_INVALID, "unknown output mode %d", output_mode);
+  if (mask_h <= 0 || mask_w <= 0) SDM_FAIL(e, SDM_ERR_INVALID, "bad mask size %dx%d", mask_h, mask_w);
+  // the size rule of sdm_apply_matte_node: the trimap made from the mask has the mask's size
+  if ((mask_h != H || mask_w != W) && (mask_refine || output_mode == 2))
+    SDM_FAIL(e, SDM_ERR_INVALID, "mask %dx%d does not match the image %dx%d (needed by mask_refine / matted_rgb)", mask_h, mask_w, H, W);
+  TRY(trimap_check(e, std::max(B, 1), mask_h, mask_w, erode_px, dilate_px));
+  std::vector<int32_t> it((size_t)std::max(B, 1), is_transparent ? 1 : 0);
+  NodeTail tail; tail.output_mode = output_mode; tail.mask_refine = mask_refine ? 1 : 0; tail.c = trimap_constraint; tail.matted = matted;
+  tail.TH = mask_h; tail.TW = mask_w;
+  tail.from_mask = true; tail.threshold = threshold; tail.erode_px = erode_px; tail.dilate_px = dilate_px; tail.trimap_out = trimap_out;
+  return forward_impl(e, 1, image, mask, B, H, W, S, it.data(), nullptr, 4, 0, true, alpha, ptr_kind, stream, &tail);
+}
+
+/* Trimap from a mask on its own (k_trimap.h).  Needs no weights; the distance plane lives in the activation arena and host pointers go through the
+ * I/O staging buffers, so sdm_resident_bytes counts what the call keeps and sdm_release_memory frees it. */
+int sdm_make_trimap(sdm_ctx* e, const float* mask, int B, int H, int W, float threshold, int erode_px, int dilate_px, float* trimap, int ptr_kind,
+                    void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !mask || !trimap) return SDM_ERR_INVALID;
+  TRY(trimap_check(e, B, H, W, erode_px, dilate_px));
+  OptReadLock opt_lock;
+#ifndef SDM_EMU
+  if (ptr_kind == SDM_PTR_DEVICE) {      // stream contract of the forward calls (include/sdmatte.h)
+    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_in, (hipStream_t)stream_arg));
+    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)e->stream, e->ev_in, 0));
+  }
+#else
+  (void)stream_arg;
+#endif
+  const size_t bytes = (size_t)B * H * W * 4;
+  const float* d_mask = mask; float* d_out = trimap;
+  if (ptr_kind == SDM_PTR_HOST) {
+    TRY(ensure_buf(e, &e->io_in, &e->io_in_bytes, bytes));
+    TRY(ensure_buf(e, &e->io_out, &e->io_out_bytes, bytes));
+    SDM_CHECK_DEV(e, dev_memcpy_h2d(e->io_in, mask, bytes, e->stream));
+    d_mask = (const float*)e->io_in; d_out = (float*)e->io_out;
+  }
+  for (int pass = 0; pass < 2; ++pass) {
+    arena_pass_begin(e, pass);
+    if (pass == 1 && e->peak > e->arena_bytes) {
+      if (e->arena) { SDM_CHECK_DEV(e, dev_sync(e->stream)); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
+      void* p = nullptr;
+      if (dev_malloc(&p, e->peak) != 0) SDM_FAIL(e, SDM_ERR_NOMEM, "cannot allocate %zu bytes of activation arena", e->peak);
+      e->arena = (unsigned char*)p; e->arena_bytes = e->peak;
+    }
+#ifndef SDM_EMU
+    if (pass == 1) (void)hipEventRecord(e->ev0, (hipStream_t)e->stream);      // sdm_last_forward_ms: the two launches of this call
+#endif
+    T dist = talloc(e, B, H, W, 1, 0);
+    if (!e->dry) op_trimap(e, d_mask, B, H, W, threshold, erode_px, dilate_px, (short*)dist.p, d_out);
+    tfree(e, dist);
+    if (pass == 1) TRY(arena_pass_end(e, 0));
+  }
+  e->dry = false;
+#ifndef SDM_EMU
+  (void)hipEventRecord(e->ev1, (hipStream_t)e->stream);
+#endif
+  if (ptr_kind == SDM_PTR_HOST) {
+    SDM_CHECK_DEV(e, dev_memcpy_d2h(trimap, e->io_out, bytes, e->stream));
+    SDM_CHECK_DEV(e, dev_sync(e->stream));
+  }
+#ifndef SDM_EMU
+  else {
+    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_out, (hipStream_t)e->stream));
+    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)stream_arg, e->ev_out, 0));
+  }
+#endif
+  return 0;
 }
 
 int sdm_synchronize(sdm_ctx* e) {

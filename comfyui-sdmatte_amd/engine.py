@@ -82,6 +82,7 @@ EXPORTS = [
     "sdm_default_config", "sdm_create", "sdm_destroy", "sdm_last_error", "sdm_load_tensor", "sdm_finalize_weights",
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
+    "sdm_make_trimap", "sdm_apply_matte_mask",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias",
@@ -115,6 +116,8 @@ class Bindings:
             "sdm_forward_rect": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, i32, vp]),
             "sdm_apply_matte": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
             "sdm_apply_matte_node": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, vp, vp, i32, vp]),
+            "sdm_make_trimap": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, vp, i32, vp]),
+            "sdm_apply_matte_mask": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, C.c_double, vp, vp, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
             "sdm_resident_bytes": (i64, [vp]),
@@ -386,6 +389,65 @@ class Engine:
         if sync:
             self.synchronize()
         return alpha, matted
+
+    TRIMAP_MAX_RADIUS = 255      # SDM_TRIMAP_MAX_RADIUS (include/sdmatte.h)
+
+    @classmethod
+    def _check_radii(cls, what, erode_px, dilate_px):
+        for name, r in (("erode_px", erode_px), ("dilate_px", dilate_px)):
+            if int(r) != r or not 0 <= int(r) <= cls.TRIMAP_MAX_RADIUS:
+                raise ValueError(f"{what}: {name} must be an integer in 0 .. {cls.TRIMAP_MAX_RADIUS}, got {r!r}")
+        return int(erode_px), int(dilate_px)
+
+    def make_trimap(self, mask, threshold=0.5, erode_px=10, dilate_px=10, out=None, sync=True):
+        """Trimap from a mask on the GPU (sdm_make_trimap): mask [B,H,W] -> fp32 [B,H,W] of exactly 1.0 (mask > threshold, farther than
+        erode_px from everything else), 0.0 (not, farther than dilate_px from the foreground) and 0.5.  Needs no loaded weights.
+        `sdmatte_nodes.trimap_from_mask` is the same function on CPU tensors, bit for bit."""
+        if mask.dim() != 3 or mask.numel() == 0:
+            raise ValueError(f"make_trimap: mask must be a non-empty [B,H,W], got {tuple(mask.shape)}")
+        erode_px, dilate_px = self._check_radii("make_trimap", erode_px, dilate_px)
+        B, H, W = (int(v) for v in mask.shape)
+        mask = mask.float().contiguous()
+        if out is None:
+            out = torch.empty(B, H, W, dtype=torch.float32, device=mask.device)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * H * W:
+            raise ValueError("make_trimap: out must be a contiguous fp32 tensor of B*H*W elements")
+        stream = self._check_io("make_trimap", mask, out)
+        self._check(self.lib.sdm_make_trimap(self.h, _ptr(mask), B, H, W, float(threshold), erode_px, dilate_px, _ptr(out), self._kind(mask), stream),
+                    "sdm_make_trimap")
+        if sync:
+            self.synchronize()
+        return out
+
+    def apply_matte_mask(self, image_bhwc, mask_bhw, S, is_transparent, output_mode, mask_refine, trimap_constraint, threshold=0.5, erode_px=10,
+                         dilate_px=10, sync=True):
+        """`apply_matte_node` with the trimap made from `mask_bhw` on the GPU in the same C-ABI call (sdm_apply_matte_mask).  Returns
+        (alpha [B,H,W], matted [B,H,W,3|4], trimap [B,h,w]); bit-identical to make_trimap followed by apply_matte_node."""
+        if output_mode not in self.OUTPUT_MODES:
+            raise ValueError(f"unknown output_mode {output_mode!r}")
+        B, H, W, Cc = image_bhwc.shape
+        if Cc != 3:
+            raise ValueError(f"apply_matte_mask: image must be [B,H,W,3], got {tuple(image_bhwc.shape)}")
+        erode_px, dilate_px = self._check_radii("apply_matte_mask", erode_px, dilate_px)
+        image_bhwc = image_bhwc.float().contiguous()
+        mask_bhw = mask_bhw.float().contiguous()
+        if mask_bhw.dim() != 3 or mask_bhw.shape[0] != B:
+            raise ValueError(f"apply_matte_mask: mask must be [B,h,w] with B = {B}, got {tuple(mask_bhw.shape)}")
+        TH, TW = int(mask_bhw.shape[1]), int(mask_bhw.shape[2])
+        mode = self.OUTPUT_MODES[output_mode]
+        if (TH, TW) != (H, W) and (mask_refine or mode == 2):
+            # the trimap has the mask's size, and apply_matte_node's rule holds for it
+            raise IndexError(f"apply_matte_mask: the mask {(TH, TW)} must match the image {(H, W)} for mask_refine / matted_rgb")
+        alpha = torch.empty(B, H, W, dtype=torch.float32, device=image_bhwc.device)
+        matted = torch.empty(B, H, W, 4 if mode == 1 else 3, dtype=torch.float32, device=image_bhwc.device)
+        trimap = torch.empty(B, TH, TW, dtype=torch.float32, device=image_bhwc.device)
+        stream = self._check_io("apply_matte_mask", image_bhwc, mask_bhw, alpha, matted, trimap)
+        self._check(self.lib.sdm_apply_matte_mask(self.h, _ptr(image_bhwc), _ptr(mask_bhw), B, H, W, TH, TW, int(S), 1 if is_transparent else 0,
+                                                  float(threshold), erode_px, dilate_px, mode, 1 if mask_refine else 0, float(trimap_constraint),
+                                                  _ptr(alpha), _ptr(matted), _ptr(trimap), self._kind(image_bhwc), stream), "sdm_apply_matte_mask")
+        if sync:
+            self.synchronize()
+        return alpha, matted, trimap
 
     def synchronize(self):
         self._check(self.lib.sdm_synchronize(self.h), "sdm_synchronize")

@@ -278,5 +278,32 @@ class MultiGpuEngine:
         self._fan(B, call)
         return alpha, matted
 
+    def make_trimap(self, mask_bhw, threshold=0.5, erode_px=10, dilate_px=10):
+        """Trimap from a mask (no model involved): on the first engine; mask [B,H,W] (host or any device) -> trimap on the HOST."""
+        return self.engines[0].make_trimap(self._to_host(mask_bhw), threshold, erode_px, dilate_px)
+
+    def apply_matte_mask(self, image_bhwc, mask_bhw, S, is_transparent, output_mode, mask_refine, trimap_constraint, threshold=0.5, erode_px=10,
+                         dilate_px=10):
+        """`apply_matte_node` with the trimap made from the mask on each GPU (images are independent: so are their trimaps); returns
+        (alpha [B,H,W], matted [B,H,W,3|4], trimap [B,h,w]) on the HOST."""
+        from .engine import Engine
+        B, H, W, _ = image_bhwc.shape
+        ch = 4 if Engine.OUTPUT_MODES[output_mode] == 1 else 3
+        alpha = self._host(B, H, W)
+        matted = self._host(B, H, W, ch)
+        img = self._to_host(image_bhwc)
+        msk = self._to_host(mask_bhw)
+        trimap = self._host(*msk.shape)
+
+        def call(eng, dev, lo, hi):
+            a, m, t = eng.apply_matte_mask(img[lo:hi], msk[lo:hi], S, is_transparent, output_mode, mask_refine, trimap_constraint, threshold, erode_px,
+                                           dilate_px)
+            alpha[lo:hi].copy_(a)
+            matted[lo:hi].copy_(m)
+            trimap[lo:hi].copy_(t)
+
+        self._fan(B, call)
+        return alpha, matted, trimap
+
     def last_forward_ms(self):
         return max(e.last_forward_ms() for e in self.engines)

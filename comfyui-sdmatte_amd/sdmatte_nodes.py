@@ -10,6 +10,9 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
   * resize / normalise / forward / resize-back / clamp / `mask_refine` / output composition (:339-397) run on the GPU in
     one C-ABI call (`sdm_apply_matte_node`); `refine_and_compose` below is the same tail on CPU tensors, kept as the
     bit-exact restatement the tests compare with;
+  * two nodes beyond the reference, registered only with SDMATTE_EXTRA_NODES=1 (the default surface stays the reference's):
+    `SDMatteTrimapFromMask` makes the trimap from a mask on the GPU (the reference's README leaves "Create Trimap" to other nodes) and
+    `SDMatteApplyMask` is `SDMatteApply` fed with a mask; `trimap_from_mask` below is the bit-exact CPU restatement of both;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -213,6 +216,9 @@ def _trim_engine_memory(model):
 def unload_models():
     """Drop the cached engine(s): every byte the node holds on the GPU is released."""
     with _CACHE_LOCK:
+        for eng in _TRIMAP_ENGINES.values():
+            eng.close()
+        _TRIMAP_ENGINES.clear()
         for model in list(_MODEL_CACHE.values()):
             fan = getattr(model, "_fan", None)
             if fan is not None:
@@ -220,6 +226,26 @@ def unload_models():
             if model.engine is not None:
                 model.engine.close()
         _MODEL_CACHE.clear()
+
+
+_TRIMAP_ENGINES = {}          # device index -> weightless engine of SDMatteTrimapFromMask (under _CACHE_LOCK)
+
+
+def _trimap_engine(device):
+    """Engine for `make_trimap` on `device`: the resident cached model's if there is one on that device, otherwise a minimal context that is
+    created once and kept (the tiny architecture, never loaded: sdm_make_trimap needs no weights, and no checkpoint is read or packed)."""
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    with _CACHE_LOCK:
+        for model in _MODEL_CACHE.values():
+            eng = getattr(model, "engine", None)
+            if eng is not None and eng.h and eng.device == index:
+                return eng
+        eng = _TRIMAP_ENGINES.get(index)
+        if eng is None:
+            from .config import SDMatteConfig
+            from .engine import Engine
+            eng = _TRIMAP_ENGINES[index] = Engine(SDMatteConfig.tiny(), index)
+        return eng
 
 
 def _fan_out(model, batch):
@@ -264,6 +290,49 @@ def refine_and_compose(alpha_bhw, image, trimap, output_mode, mask_refine, trima
     else:
         matted = image_cpu * a4
     return out, matted
+
+
+def _disk_reach(r):
+    """hmax[dx] for dx = 0 .. r: the largest h with h^2 + dx^2 <= r^2 (integers only)."""
+    import math
+    return [math.isqrt(r * r - dx * dx) for dx in range(r + 1)]
+
+
+def _column_distance(other):
+    """Per pixel, the vertical distance to the nearest True of `other` [B,H,W] in its column (0 on a True pixel; beyond any radius if none)."""
+    H = other.shape[1]
+    far = 1 << 20
+    ys = torch.arange(H, dtype=torch.int32).view(1, H, 1)
+    above = torch.where(other, ys, torch.full_like(ys, -far)).cummax(dim=1).values
+    below = -torch.where(other, -ys, torch.full_like(ys, -far - H)).flip(1).cummax(dim=1).values.flip(1)
+    return torch.minimum(ys - above, below - ys)
+
+
+def _near(other, r):
+    """True where a True pixel of `other` lies within the closed Euclidean disk of radius r (pixels beyond the border do not exist)."""
+    W = other.shape[2]
+    dist = _column_distance(other)
+    hit = torch.zeros_like(other)
+    for dx, h in [(s * d, h) for d, h in enumerate(_disk_reach(r)) for s in ((1, -1) if d else (1,))]:
+        lo, hi = max(0, -dx), W - max(0, dx)      # pixels x whose column x + dx exists
+        if hi > lo:
+            hit[:, :, lo:hi] |= dist[:, :, lo + dx:hi + dx] <= h
+    return hit
+
+
+def trimap_from_mask(mask, threshold=0.5, erode_px=10, dilate_px=10):
+    """`Engine.make_trimap` on CPU tensors, bit for bit (the restatement the tests compare the kernels with): mask [B,H,W] -> fp32 trimap of
+    1.0 (mask > threshold and no other pixel within erode_px), 0.0 (mask <= threshold or NaN, and no foreground within dilate_px), 0.5 elsewhere."""
+    if mask.dim() != 3:
+        raise ValueError(f"trimap_from_mask: mask must be [B,H,W], got {tuple(mask.shape)}")
+    for name, r in (("erode_px", erode_px), ("dilate_px", dilate_px)):
+        if int(r) != r or not 0 <= int(r) <= 255:
+            raise ValueError(f"trimap_from_mask: {name} must be an integer in 0 .. 255, got {r!r}")
+    fg = mask.detach().cpu().float() > torch.tensor(float(threshold), dtype=torch.float32)
+    unknown = (fg & _near(~fg, int(erode_px))) | (~fg & _near(fg, int(dilate_px)))
+    out = fg.float()
+    out[unknown] = 0.5
+    return out
 
 
 class SDMatteApply:
@@ -315,10 +384,82 @@ class SDMatteApply:
         return (out, matted)
 
 
-NODE_CLASS_MAPPINGS = {
-    "SDMatteApply": SDMatteApply,
+_TRIMAP_INPUTS = {
+    "threshold": ("FLOAT", {"default": 0.5, "min": 0.0, "max": 1.0, "step": 0.01, "tooltip": "mask values above this are foreground"}),
+    "erode_px": ("INT", {"default": 10, "min": 0, "max": 255, "step": 1, "tooltip": "foreground closer than this to the mask's edge becomes unknown (pixels)"}),
+    "dilate_px": ("INT", {"default": 10, "min": 0, "max": 255, "step": 1, "tooltip": "background closer than this to the mask becomes unknown (pixels)"}),
 }
 
-NODE_DISPLAY_NAME_MAPPINGS = {
-    "SDMatteApply": "Apply SDMatte",
-}
+
+class SDMatteTrimapFromMask:
+    """Mask (SAM, RMBG, a hand-drawn selection) -> trimap, on the GPU; needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": dict({"mask": ("MASK", {"tooltip": "mask to turn into a trimap"})}, **_TRIMAP_INPUTS)}
+
+    RETURN_TYPES = ("MASK", )
+    RETURN_NAMES = ("trimap", )
+    FUNCTION = "make_trimap"
+    CATEGORY = "Matting/SDMatte"
+
+    def make_trimap(self, mask, threshold=0.5, erode_px=10, dilate_px=10):
+        if mask.dim() == 2:
+            mask = mask.unsqueeze(0)
+        if mask.dim() != 3:
+            raise ValueError(f"[SDMatte] mask must be [B,H,W], got {tuple(mask.shape)}")
+        eng = _trimap_engine(_torch_device())
+        return (eng.make_trimap(mask.detach().cpu(), float(threshold), int(erode_px), int(dilate_px)), )
+
+
+class SDMatteApplyMask:
+    """`Apply SDMatte` fed with a mask: the trimap is made from it on the GPU inside the same engine call, and returned as well."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        base = SDMatteApply.INPUT_TYPES()
+        required = {}
+        for key, spec in base["required"].items():
+            if key == "trimap":
+                required["mask"] = ("MASK", {"tooltip": "mask of the object: the trimap is made from it (threshold, erode_px, dilate_px)"})
+                required.update(_TRIMAP_INPUTS)
+            else:
+                required[key] = spec
+        return {"required": required, "optional": base["optional"]}
+
+    RETURN_TYPES = ("MASK", "IMAGE", "MASK")
+    RETURN_NAMES = ("alpha_mask", "matted_image", "trimap")
+    FUNCTION = "apply_matte"
+    CATEGORY = "Matting/SDMatte"
+
+    def apply_matte(self, ckpt_name, image, mask, threshold, erode_px, dilate_px, inference_size, is_transparent, output_mode, mask_refine,
+                    trimap_constraint, force_cpu=False):
+        if force_cpu:
+            raise RuntimeError("[SDMatte] force_cpu=True is not available: this node runs hand-written gfx950 kernels only "
+                               "(no CPU path).  Use the reference plugin for CPU inference.")
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        if mask.dim() != 3 or mask.shape[0] != image.shape[0]:
+            raise ValueError(f"[SDMatte] mask must be [B,h,w] with the image's batch size, got {tuple(mask.shape)}")
+        model = get_model(ckpt_name, _torch_device())
+        fan = _fan_out(model, image.shape[0])
+        runner = fan if fan is not None else model.engine
+        out, matted, trimap = runner.apply_matte_mask(image, mask, int(inference_size), bool(is_transparent), output_mode, bool(mask_refine),
+                                                      float(trimap_constraint), float(threshold), int(erode_px), int(dilate_px))
+        out, matted, trimap = out.detach().cpu(), matted.detach().cpu(), trimap.detach().cpu()
+        _trim_engine_memory(model)
+        return (out, matted, trimap)
+
+
+def node_mappings(extra: bool):
+    """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`."""
+    classes = {"SDMatteApply": SDMatteApply}
+    names = {"SDMatteApply": "Apply SDMatte"}
+    if extra:
+        classes.update({"SDMatteTrimapFromMask": SDMatteTrimapFromMask, "SDMatteApplyMask": SDMatteApplyMask})
+        names.update({"SDMatteTrimapFromMask": "SDMatte Trimap From Mask", "SDMatteApplyMask": "Apply SDMatte (Mask)"})
+    return classes, names
+
+
+# the two nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1), like the multi-GPU fan-out (SDMATTE_MULTI_GPU)
+NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1")

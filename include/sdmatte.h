@@ -162,6 +162,26 @@ int sdm_apply_matte_node(sdm_ctx* ctx, const float* image_bhwc, const float* tri
                          int is_transparent, int output_mode, int mask_refine, double trimap_constraint, float* alpha_bhw, float* matted_bhwc,
                          int ptr_kind, void* stream);
 
+/* Trimap from a mask, on the GPU (beyond the reference, whose README leaves "Create Trimap" to other nodes): mask fp32 [B,H,W] ->
+ * trimap fp32 [B,H,W] with F = { p : mask[p] > threshold } (one fp32 compare, so NaN is background) and
+ *   1.0 where p is in F and no pixel of the image outside F lies within Euclidean distance erode_px of p (dx^2 + dy^2 <= erode_px^2),
+ *   0.0 where p is not in F and no pixel of F lies within distance dilate_px of p,
+ *   0.5 elsewhere.
+ * Pixels beyond the image border do not exist (neither foreground nor background): an object cut by the frame keeps its definite foreground up
+ * to the edge.  Radii 0 give the binarised mask.  Integer arithmetic and compares only: the values are exactly 0.0 / 0.5 / 1.0.
+ * Radii in 0 .. SDM_TRIMAP_MAX_RADIUS, any H, W >= 1 (SDM_ERR_INVALID otherwise).  Stream contract and pointer kinds as sdm_forward.  Needs no
+ * weights: it works on a context that never loaded any.  Its scratch memory is part of the activation arena / I/O staging
+ * (sdm_resident_bytes counts it, sdm_release_memory frees it). */
+#define SDM_TRIMAP_MAX_RADIUS 255
+int sdm_make_trimap(sdm_ctx* ctx, const float* mask_bhw, int B, int H, int W, float threshold, int erode_px, int dilate_px,
+                    float* trimap_bhw, int ptr_kind, void* stream);
+/* sdm_apply_matte_node with the trimap made from `mask` [B,mask_h,mask_w] on the device, in the same call: bit-identical, in alpha,
+ * matted and trimap, to sdm_make_trimap followed by sdm_apply_matte_node.  The size rule is that call's, with the mask in the trimap's place.
+ * trimap_out (may be NULL) receives the trimap [B,mask_h,mask_w]. */
+int sdm_apply_matte_mask(sdm_ctx* ctx, const float* image_bhwc, const float* mask_bhw, int B, int H, int W, int mask_h, int mask_w, int S,
+                         int is_transparent, float threshold, int erode_px, int dilate_px, int output_mode, int mask_refine,
+                         double trimap_constraint, float* alpha_bhw, float* matted_bhwc, float* trimap_out, int ptr_kind, void* stream);
+
 /* Memory the engine holds outside any framework allocator: packed weights + activation arena (sized by the largest batch /
  * resolution seen) + I/O staging.  sdm_release_memory frees everything but the weights (the next forward re-allocates). */
 int64_t sdm_resident_bytes(sdm_ctx* ctx);
@@ -187,7 +207,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte, measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap: its two launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
