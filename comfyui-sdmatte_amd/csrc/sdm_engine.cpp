@@ -18,6 +18,7 @@
 #include "k_attn.h"
 #include "k_misc.h"
 #include "k_trimap.h"
+#include "k_foreground.h"
 #include "../../include/sdmatte.h"
 
 #include <algorithm>
@@ -2853,6 +2854,114 @@ int sdm_make_trimap(sdm_ctx* e, const float* mask, int B, int H, int W, float th
 #endif
   if (ptr_kind == SDM_PTR_HOST) {
     SDM_CHECK_DEV(e, dev_memcpy_d2h(trimap, e->io_out, bytes, e->stream));
+    SDM_CHECK_DEV(e, dev_sync(e->stream));
+  }
+#ifndef SDM_EMU
+  else {
+    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_out, (hipStream_t)e->stream));
+    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)stream_arg, e->ev_out, 0));
+  }
+#endif
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// foreground / background colours from image + alpha (k_foreground.h)
+// ------------------------------------------------------------------------------------------------
+struct FgLevel { int h, w; };
+
+// the levels from (H, W) down to the largest small one (the last entry): everything in front of it is a launch of fg_level_kernel
+static std::vector<FgLevel> fg_large_levels(int H, int W) {
+  std::vector<FgLevel> lv;
+  int h = H, w = W;
+  while (std::max(h, w) > SDM_FG_SMALL) { lv.push_back({h, w}); h = (h + 1) / 2; w = (w + 1) / 2; }
+  lv.push_back({h, w});
+  return lv;
+}
+
+/* Needs no weights; the level planes live in the activation arena and host pointers go through the I/O staging buffers, so sdm_resident_bytes
+ * counts what the call keeps and sdm_release_memory frees it. */
+int sdm_estimate_foreground(sdm_ctx* e, const float* image, const float* alpha, int B, int H, int W, float regularization, float gradient_weight,
+                            int n_small_iters, int n_big_iters, float* fg, int fg_channels, float* bg, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !alpha || !fg) return SDM_ERR_INVALID;
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "estimate foreground: bad image size %dx%dx%d", B, H, W);
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "estimate foreground: %dx%dx%d is too large (sides up to %d, %d pixels in all)", B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  if (!(regularization > 0.0f) || !std::isfinite(regularization))
+    SDM_FAIL(e, SDM_ERR_INVALID, "estimate foreground: regularization = %g must be a finite number above 0", (double)regularization);
+  if (!(gradient_weight >= 0.0f) || !std::isfinite(gradient_weight))
+    SDM_FAIL(e, SDM_ERR_INVALID, "estimate foreground: gradient_weight = %g must be a finite number, 0 or above", (double)gradient_weight);
+  if (n_small_iters < 1 || n_small_iters > SDM_FG_MAX_SMALL_ITERS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "estimate foreground: n_small_iters = %d outside 1 .. %d", n_small_iters, SDM_FG_MAX_SMALL_ITERS);
+  if (n_big_iters < 1 || n_big_iters > SDM_FG_MAX_BIG_ITERS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "estimate foreground: n_big_iters = %d outside 1 .. %d", n_big_iters, SDM_FG_MAX_BIG_ITERS);
+  if (fg_channels != 3 && fg_channels != 4) SDM_FAIL(e, SDM_ERR_INVALID, "estimate foreground: fg_channels = %d, must be 3 or 4", fg_channels);
+  OptReadLock opt_lock;
+#ifndef SDM_EMU
+  if (ptr_kind == SDM_PTR_DEVICE) {      // stream contract of the forward calls (include/sdmatte.h)
+    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_in, (hipStream_t)stream_arg));
+    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)e->stream, e->ev_in, 0));
+  }
+#else
+  (void)stream_arg;
+#endif
+  const size_t px = (size_t)B * H * W;
+  const size_t img_bytes = px * 12, alpha_bytes = px * 4, fg_bytes = px * 4 * fg_channels, bg_bytes = bg ? px * 12 : 0;
+  const float* d_img = image; const float* d_alpha = alpha; float* d_fg = fg; float* d_bg = bg;
+  if (ptr_kind == SDM_PTR_HOST) {
+    TRY(ensure_buf(e, &e->io_in, &e->io_in_bytes, img_bytes + alpha_bytes));
+    TRY(ensure_buf(e, &e->io_out, &e->io_out_bytes, fg_bytes + bg_bytes));
+    SDM_CHECK_DEV(e, dev_memcpy_h2d(e->io_in, image, img_bytes, e->stream));
+    SDM_CHECK_DEV(e, dev_memcpy_h2d((unsigned char*)e->io_in + img_bytes, alpha, alpha_bytes, e->stream));
+    d_img = (const float*)e->io_in; d_alpha = (const float*)((unsigned char*)e->io_in + img_bytes);
+    d_fg = (float*)e->io_out; d_bg = bg ? (float*)((unsigned char*)e->io_out + fg_bytes) : nullptr;
+  }
+  const std::vector<FgLevel> lv = fg_large_levels(H, W);
+  const int nl = (int)lv.size();
+  const int tw = fg_tile_w(n_big_iters), th = fg_tile_h(n_big_iters);
+  for (int pass = 0; pass < 2; ++pass) {
+    arena_pass_begin(e, pass);
+    if (pass == 1 && e->peak > e->arena_bytes) {
+      if (e->arena) { SDM_CHECK_DEV(e, dev_sync(e->stream)); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
+      void* p = nullptr;
+      if (dev_malloc(&p, e->peak) != 0) SDM_FAIL(e, SDM_ERR_NOMEM, "cannot allocate %zu bytes of activation arena", e->peak);
+      e->arena = (unsigned char*)p; e->arena_bytes = e->peak;
+    }
+#ifndef SDM_EMU
+    if (pass == 1) (void)hipEventRecord(e->ev0, (hipStream_t)e->stream);      // sdm_last_forward_ms: the launches of this call
+#endif
+    // one plane of 8 floats per pixel for every level below the top one, the largest small level included: planes[i] belongs to lv[i]
+    std::vector<T> planes((size_t)nl);
+    for (int i = 1; i < nl; ++i) planes[i] = talloc(e, B, lv[i].h, lv[i].w, 8, 1);
+    if (!e->dry) {
+      const FgLevel s = lv[nl - 1];
+      // the largest small level gathers 16 bytes per pixel and stores its result; the levels below it add about a third of its gathers
+      prof_begin(e, "fg_small", 0, (double)B * s.h * s.w * (16 + (nl == 1 ? 4 * fg_channels + (bg ? 12 : 0) : 32)) * 4.0 / 3.0);
+      count_kernel("fg_small");
+      SDM_LAUNCH(fg_small_kernel, dim3((unsigned)B), dim3(SDM_FG_SMALL_PX), 0, e->stream, d_img, d_alpha, B, H, W, s.h, s.w, regularization, gradient_weight,
+                 n_small_iters, (float*)planes[nl - 1].p, d_fg, fg_channels, d_bg);
+      prof_end(e);
+      for (int i = nl - 2; i >= 0; --i) {
+        const double lpx = (double)B * lv[i].h * lv[i].w;
+        // per pixel of the level: image 12 + alpha 4 + a quarter of a 32-byte pixel of the previous level, and the stores
+        prof_begin(e, "fg_level", 0, lpx * (24 + (i == 0 ? 4 * fg_channels + (bg ? 12 : 0) : 32)));
+        count_kernel("fg_level");
+        SDM_LAUNCH(fg_level_kernel, dim3((unsigned)(B * sdm_cdiv(lv[i].h, th) * sdm_cdiv(lv[i].w, tw))), dim3(256), 0, e->stream, d_img, d_alpha, B, H, W,
+                   lv[i].h, lv[i].w, (const float*)planes[i + 1].p, regularization, gradient_weight, n_big_iters, (float*)planes[i].p, d_fg, fg_channels, d_bg);
+        prof_end(e);
+      }
+    }
+    for (int i = nl - 1; i >= 1; --i) tfree(e, planes[i]);
+    if (pass == 1) TRY(arena_pass_end(e, 0));
+  }
+  e->dry = false;
+#ifndef SDM_EMU
+  (void)hipEventRecord(e->ev1, (hipStream_t)e->stream);
+#endif
+  if (ptr_kind == SDM_PTR_HOST) {
+    SDM_CHECK_DEV(e, dev_memcpy_d2h(fg, e->io_out, fg_bytes, e->stream));
+    if (bg) SDM_CHECK_DEV(e, dev_memcpy_d2h(bg, (unsigned char*)e->io_out + fg_bytes, bg_bytes, e->stream));
     SDM_CHECK_DEV(e, dev_sync(e->stream));
   }
 #ifndef SDM_EMU

@@ -82,7 +82,7 @@ EXPORTS = [
     "sdm_default_config", "sdm_create", "sdm_destroy", "sdm_last_error", "sdm_load_tensor", "sdm_finalize_weights",
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
-    "sdm_make_trimap", "sdm_apply_matte_mask",
+    "sdm_make_trimap", "sdm_apply_matte_mask", "sdm_estimate_foreground",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias",
@@ -118,6 +118,7 @@ class Bindings:
             "sdm_apply_matte_node": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, vp, vp, i32, vp]),
             "sdm_make_trimap": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, vp, i32, vp]),
             "sdm_apply_matte_mask": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, C.c_double, vp, vp, vp, i32, vp]),
+            "sdm_estimate_foreground": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
             "sdm_resident_bytes": (i64, [vp]),
@@ -448,6 +449,54 @@ class Engine:
         if sync:
             self.synchronize()
         return alpha, matted, trimap
+
+    # SDM_FG_* (include/sdmatte.h)
+    FG_DEFAULTS = {"regularization": 1e-5, "gradient_weight": 1.0, "n_small_iters": 10, "n_big_iters": 2}
+    FG_MAX_SMALL_ITERS = 64
+    FG_MAX_BIG_ITERS = 4
+    FG_MAX_SIDE = 32768
+    FG_MAX_PIXELS = 1 << 28
+
+    @classmethod
+    def _check_fg_params(cls, what, regularization, gradient_weight, n_small_iters, n_big_iters):
+        import math
+        regularization, gradient_weight = float(regularization), float(gradient_weight)
+        if not (math.isfinite(regularization) and regularization > 0.0):
+            raise ValueError(f"{what}: regularization must be a finite number above 0, got {regularization!r}")
+        if not (math.isfinite(gradient_weight) and gradient_weight >= 0.0):
+            raise ValueError(f"{what}: gradient_weight must be a finite number, 0 or above, got {gradient_weight!r}")
+        for name, v, hi in (("n_small_iters", n_small_iters, cls.FG_MAX_SMALL_ITERS), ("n_big_iters", n_big_iters, cls.FG_MAX_BIG_ITERS)):
+            if int(v) != v or not 1 <= int(v) <= hi:
+                raise ValueError(f"{what}: {name} must be an integer in 1 .. {hi}, got {v!r}")
+        return regularization, gradient_weight, int(n_small_iters), int(n_big_iters)
+
+    def estimate_foreground(self, image_bhwc, alpha_bhw, regularization=1e-5, gradient_weight=1.0, n_small_iters=10, n_big_iters=2, rgba=False,
+                            want_background=True, sync=True):
+        """Foreground / background colours of every pixel from the image [B,H,W,3] and its alpha [B,H,W] on the GPU (sdm_estimate_foreground, the
+        multi-level estimator defined in include/sdmatte.h).  Returns (fg [B,H,W,3], or [B,H,W,4] with the sanitised alpha as channel 3 when `rgba`;
+        bg [B,H,W,3], or None without `want_background`).  Needs no loaded weights.  `sdmatte_nodes.estimate_foreground` is the same function on CPU
+        tensors, equal to fp32 rounding."""
+        if image_bhwc.dim() != 4 or image_bhwc.shape[-1] != 3 or image_bhwc.numel() == 0:
+            raise ValueError(f"estimate_foreground: image must be a non-empty [B,H,W,3], got {tuple(image_bhwc.shape)}")
+        B, H, W, _ = (int(v) for v in image_bhwc.shape)
+        if tuple(alpha_bhw.shape) != (B, H, W):
+            raise ValueError(f"estimate_foreground: alpha must be [B,H,W] = {(B, H, W)}, got {tuple(alpha_bhw.shape)}")
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"estimate_foreground: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        regularization, gradient_weight, n_small_iters, n_big_iters = self._check_fg_params("estimate_foreground", regularization, gradient_weight,
+                                                                                            n_small_iters, n_big_iters)
+        image_bhwc = image_bhwc.float().contiguous()
+        alpha_bhw = alpha_bhw.float().contiguous()
+        ch = 4 if rgba else 3
+        fg = torch.empty(B, H, W, ch, dtype=torch.float32, device=image_bhwc.device)
+        bg = torch.empty(B, H, W, 3, dtype=torch.float32, device=image_bhwc.device) if want_background else None
+        stream = self._check_io("estimate_foreground", image_bhwc, alpha_bhw, fg, bg)
+        self._check(self.lib.sdm_estimate_foreground(self.h, _ptr(image_bhwc), _ptr(alpha_bhw), B, H, W, regularization, gradient_weight, n_small_iters,
+                                                     n_big_iters, _ptr(fg), ch, _ptr(bg), self._kind(image_bhwc), stream),
+                    "sdm_estimate_foreground")
+        if sync:
+            self.synchronize()
+        return fg, bg
 
     def synchronize(self):
         self._check(self.lib.sdm_synchronize(self.h), "sdm_synchronize")

@@ -282,6 +282,13 @@ class MultiGpuEngine:
         """Trimap from a mask (no model involved): on the first engine; mask [B,H,W] (host or any device) -> trimap on the HOST."""
         return self.engines[0].make_trimap(self._to_host(mask_bhw), threshold, erode_px, dilate_px)
 
+    def estimate_foreground(self, image_bhwc, alpha_bhw, regularization=1e-5, gradient_weight=1.0, n_small_iters=10, n_big_iters=2, rgba=False,
+                            want_background=True):
+        """Foreground / background colours from image + alpha (no model involved): on the first engine; inputs on the host or any device ->
+        (fg, bg | None) on the HOST."""
+        return self.engines[0].estimate_foreground(self._to_host(image_bhwc), self._to_host(alpha_bhw), regularization, gradient_weight, n_small_iters,
+                                                   n_big_iters, rgba, want_background)
+
     def apply_matte_mask(self, image_bhwc, mask_bhw, S, is_transparent, output_mode, mask_refine, trimap_constraint, threshold=0.5, erode_px=10,
                          dilate_px=10):
         """`apply_matte_node` with the trimap made from the mask on each GPU (images are independent: so are their trimaps); returns

@@ -13,6 +13,9 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
   * two nodes beyond the reference, registered only with SDMATTE_EXTRA_NODES=1 (the default surface stays the reference's):
     `SDMatteTrimapFromMask` makes the trimap from a mask on the GPU (the reference's README leaves "Create Trimap" to other nodes) and
     `SDMatteApplyMask` is `SDMatteApply` fed with a mask; `trimap_from_mask` below is the bit-exact CPU restatement of both;
+  * one more node beyond the reference, registered only with SDMATTE_FOREGROUND_NODE=1: `SDMatteForeground` estimates the foreground and
+    background colours from the image and the alpha on the GPU (clean cut-outs without the old background's halo); `estimate_foreground`
+    below is its CPU restatement;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -335,6 +338,56 @@ def trimap_from_mask(mask, threshold=0.5, erode_px=10, dilate_px=10):
     return out
 
 
+def _nearest_index(n_dst, n_src):
+    """src = min(n_src - 1, (i * n_src) // n_dst) for i = 0 .. n_dst - 1 (integers only)."""
+    return torch.clamp((torch.arange(n_dst, dtype=torch.int64) * n_src) // n_dst, max=n_src - 1)
+
+
+def _neighbours(t):
+    """t [B,h,w,...] -> its left, right, up and down neighbours, coordinates clamped to the level (a border pixel is its own neighbour)."""
+    return (torch.cat([t[:, :, :1], t[:, :, :-1]], 2), torch.cat([t[:, :, 1:], t[:, :, -1:]], 2),
+            torch.cat([t[:, :1], t[:, :-1]], 1), torch.cat([t[:, 1:], t[:, -1:]], 1))
+
+
+def estimate_foreground(image, alpha, regularization=1e-5, gradient_weight=1.0, n_small_iters=10, n_big_iters=2):
+    """`Engine.estimate_foreground` on CPU tensors in fp32 (the multi-level estimator defined in include/sdmatte.h): image [B,H,W,3], alpha [B,H,W] ->
+    (fg [B,H,W,3], bg [B,H,W,3], sanitised alpha [B,H,W]).  It and the GPU kernels evaluate the same formulas in fp32 but not in the same order
+    (summation order, FMA contraction), so they agree to rounding, not bit for bit."""
+    from .engine import Engine
+    if image.dim() != 4 or image.shape[-1] != 3 or image.numel() == 0:
+        raise ValueError(f"estimate_foreground: image must be a non-empty [B,H,W,3], got {tuple(image.shape)}")
+    if tuple(alpha.shape) != tuple(image.shape[:3]):
+        raise ValueError(f"estimate_foreground: alpha must be [B,H,W] = {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+    reg, gw, n_small, n_big = Engine._check_fg_params("estimate_foreground", regularization, gradient_weight, n_small_iters, n_big_iters)
+    image = image.detach().cpu().float()
+    alpha = torch.nan_to_num(alpha.detach().cpu().float(), nan=0.0, posinf=1.0, neginf=0.0).clamp(0.0, 1.0)
+    H, W = int(image.shape[1]), int(image.shape[2])
+    sizes = [(H, W)]
+    while sizes[-1] != (1, 1):
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    F = B = None
+    for h, w in reversed(sizes):
+        iy, ix = _nearest_index(h, H), _nearest_index(w, W)
+        I = image[:, iy][:, :, ix]
+        a0 = alpha[:, iy][:, :, ix].unsqueeze(-1)
+        if F is None:
+            F, B = I.clone(), I.clone()
+        else:
+            py, px = _nearest_index(h, F.shape[1]), _nearest_index(w, F.shape[2])
+            F, B = F[:, py][:, :, px], B[:, py][:, :, px]
+        a1 = 1.0 - a0
+        wq = [reg + gw * (a0 - q).abs() for q in _neighbours(a0)]
+        s = wq[0] + wq[1] + wq[2] + wq[3]
+        D = a0 * a0 + a1 * a1 + s
+        for _ in range(n_small if max(h, w) <= 32 else n_big):
+            Fq, Bq = _neighbours(F), _neighbours(B)
+            Fm = (wq[0] * Fq[0] + wq[1] * Fq[1] + wq[2] * Fq[2] + wq[3] * Fq[3]) / s
+            Bm = (wq[0] * Bq[0] + wq[1] * Bq[1] + wq[2] * Bq[2] + wq[3] * Bq[3]) / s
+            r = (I - a0 * Fm - a1 * Bm) / D
+            F, B = (Fm + a0 * r).clamp(0.0, 1.0), (Bm + a1 * r).clamp(0.0, 1.0)
+    return F.contiguous(), B.contiguous(), alpha
+
+
 class SDMatteApply:
 
     @classmethod
@@ -451,15 +504,56 @@ class SDMatteApplyMask:
         return (out, matted, trimap)
 
 
-def node_mappings(extra: bool):
-    """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`."""
+_FOREGROUND_INPUTS = {
+    "regularization": ("FLOAT", {"default": 1e-5, "min": 1e-9, "max": 1.0, "step": 1e-6, "tooltip": "smoothness weight between all neighbours (must be above 0)"}),
+    "gradient_weight": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 100.0, "step": 0.01, "tooltip": "extra smoothness weight across alpha edges"}),
+    "n_small_iters": ("INT", {"default": 10, "min": 1, "max": 64, "step": 1, "tooltip": "iterations on every level up to 32 pixels"}),
+    "n_big_iters": ("INT", {"default": 2, "min": 1, "max": 4, "step": 1, "tooltip": "iterations on every larger level"}),
+}
+
+
+class SDMatteForeground:
+    """Image + alpha -> foreground and background colours on the GPU: a cut-out without the old background baked into its soft pixels.  Needs no
+    checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE", {"tooltip": "the image the alpha was made for"}),
+                             "alpha": ("MASK", {"tooltip": "alpha matte of the image (alpha_mask of Apply SDMatte)"})},
+                "optional": dict(_FOREGROUND_INPUTS)}
+
+    RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE")
+    RETURN_NAMES = ("foreground", "background", "foreground_rgba")
+    FUNCTION = "estimate"
+    CATEGORY = "Matting/SDMatte"
+
+    def estimate(self, image, alpha, regularization=1e-5, gradient_weight=1.0, n_small_iters=10, n_big_iters=2):
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        if alpha.dim() == 2:
+            alpha = alpha.unsqueeze(0)
+        if tuple(alpha.shape) != tuple(image.shape[:3]):
+            raise ValueError(f"[SDMatte] alpha must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+        eng = _trimap_engine(_torch_device())
+        rgba, bg = eng.estimate_foreground(image.detach().cpu(), alpha.detach().cpu(), float(regularization), float(gradient_weight), int(n_small_iters),
+                                           int(n_big_iters), rgba=True)
+        return (rgba[..., :3].contiguous(), bg, rgba)
+
+
+def node_mappings(extra: bool, foreground: bool = False):
+    """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
+    node when `foreground`."""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
         classes.update({"SDMatteTrimapFromMask": SDMatteTrimapFromMask, "SDMatteApplyMask": SDMatteApplyMask})
         names.update({"SDMatteTrimapFromMask": "SDMatte Trimap From Mask", "SDMatteApplyMask": "Apply SDMatte (Mask)"})
+    if foreground:
+        classes["SDMatteForeground"] = SDMatteForeground
+        names["SDMatteForeground"] = "SDMatte Foreground Colours"
     return classes, names
 
 
-# the two nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1), like the multi-GPU fan-out (SDMATTE_MULTI_GPU)
-NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1")
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1), like the multi-GPU fan-out (SDMATTE_MULTI_GPU)
+NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
+                                                                os.environ.get("SDMATTE_FOREGROUND_NODE") == "1")

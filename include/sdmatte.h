@@ -182,6 +182,35 @@ int sdm_apply_matte_mask(sdm_ctx* ctx, const float* image_bhwc, const float* mas
                          int is_transparent, float threshold, int erode_px, int dilate_px, int output_mode, int mask_refine,
                          double trimap_constraint, float* alpha_bhw, float* matted_bhwc, float* trimap_out, int ptr_kind, void* stream);
 
+/* Foreground / background colours from an image and its alpha, on the GPU (beyond the reference: its matted_rgba keeps the composite
+ * a*F + (1-a)*B in every semi-transparent pixel, and with it a halo of the old background).  A multi-level estimator in the style of Germer et al.,
+ * "Fast Multi-Level Foreground Estimation"; it uses the image and the alpha only.
+ *   image fp32 [B,H,W,3] (values used as they are), alpha fp32 [B,H,W] (NaN -> 0, then clamped to [0,1])
+ *   fg fp32 [B,H,W,fg_channels], fg_channels 3 or 4: with 4, channel 3 is the sanitised alpha (a straight-alpha RGBA cut-out)
+ *   bg fp32 [B,H,W,3], may be NULL.  Colours are clamped to [0,1].
+ * Levels (h,w) = (H,W), (ceil(h/2), ceil(w/2)), ... down to (1,1), processed from (1,1) upwards; a level with max(h,w) <= 32 runs n_small_iters
+ * Jacobi steps, every other level n_big_iters.  Nearest resampling src = min(Ns-1, (i*Ns)/Nd): a level's image I and alpha a0 come from the
+ * full-resolution inputs, F and B from the previous level (F = B = I at (1,1)).  Per pixel p, with neighbours q = left, right, up, down clamped
+ * to the level: w_q = regularization + gradient_weight * |a0[p] - a0[q]|, s = sum w_q, a1 = 1 - a0, D = a0^2 + a1^2 + s, and per step and channel
+ *   Fm = (sum w_q F[q]) / s, Bm = (sum w_q B[q]) / s, r = (I - a0 Fm - a1 Bm) / D, F' = clamp(Fm + a0 r, 0, 1), B' = clamp(Bm + a1 r, 0, 1).
+ * Every step reads the previous step only, so an image's result does not depend on the batch it is in.  sdmatte_nodes.estimate_foreground is the
+ * same function on CPU tensors (equal to fp32 rounding, not bit for bit).
+ * regularization > 0, gradient_weight >= 0 (both finite), n_small_iters in 1 .. SDM_FG_MAX_SMALL_ITERS, n_big_iters in 1 .. SDM_FG_MAX_BIG_ITERS,
+ * H and W in 1 .. SDM_FG_MAX_SIDE (the resampling products i*Ns are 32-bit) and B*H*W <= SDM_FG_MAX_PIXELS (pixel counts are 32-bit; byte offsets
+ * are 64-bit): SDM_ERR_INVALID otherwise.  Stream contract and pointer kinds as sdm_make_trimap.  Needs no weights.  The level planes are part of
+ * the activation arena, host pointers go through the I/O staging (sdm_resident_bytes counts both, sdm_release_memory frees them). */
+#define SDM_FG_REGULARIZATION 1e-5f
+#define SDM_FG_GRADIENT_WEIGHT 1.0f
+#define SDM_FG_SMALL_ITERS 10
+#define SDM_FG_BIG_ITERS 2
+#define SDM_FG_MAX_SMALL_ITERS 64
+#define SDM_FG_MAX_BIG_ITERS 4
+#define SDM_FG_MAX_SIDE 32768
+#define SDM_FG_MAX_PIXELS 268435456 /* 2^28 */
+int sdm_estimate_foreground(sdm_ctx* ctx, const float* image_bhwc, const float* alpha_bhw, int B, int H, int W, float regularization,
+                            float gradient_weight, int n_small_iters, int n_big_iters, float* fg_bhwc, int fg_channels, float* bg_bhwc,
+                            int ptr_kind, void* stream);
+
 /* Memory the engine holds outside any framework allocator: packed weights + activation arena (sized by the largest batch /
  * resolution seen) + I/O staging.  sdm_release_memory frees everything but the weights (the next forward re-allocates). */
 int64_t sdm_resident_bytes(sdm_ctx* ctx);
@@ -207,7 +236,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap: its two launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_estimate_foreground: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
