@@ -19,6 +19,7 @@
 #include "k_misc.h"
 #include "k_trimap.h"
 #include "k_foreground.h"
+#include "k_guided.h"
 #include "../../include/sdmatte.h"
 
 #include <algorithm>
@@ -2962,6 +2963,108 @@ int sdm_estimate_foreground(sdm_ctx* e, const float* image, const float* alpha, 
   if (ptr_kind == SDM_PTR_HOST) {
     SDM_CHECK_DEV(e, dev_memcpy_d2h(fg, e->io_out, fg_bytes, e->stream));
     if (bg) SDM_CHECK_DEV(e, dev_memcpy_d2h(bg, (unsigned char*)e->io_out + fg_bytes, bg_bytes, e->stream));
+    SDM_CHECK_DEV(e, dev_sync(e->stream));
+  }
+#ifndef SDM_EMU
+  else {
+    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_out, (hipStream_t)e->stream));
+    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)stream_arg, e->ev_out, 0));
+  }
+#endif
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// alpha refinement at full resolution: the subsampled colour guided filter (k_guided.h)
+// ------------------------------------------------------------------------------------------------
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+/* Needs no weights; the three coarse planes live in the activation arena and host pointers go through the I/O staging buffers, so sdm_resident_bytes
+ * counts what the call keeps and sdm_release_memory frees it.  Four launches, whatever the arguments. */
+int sdm_refine_alpha_guided(sdm_ctx* e, const float* image, const float* alpha, int B, int H, int W, int subsample, int radius, float eps, float* out,
+                            int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !alpha || !out) return SDM_ERR_INVALID;
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "refine alpha: bad image size %dx%dx%d", B, H, W);
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "refine alpha: %dx%dx%d is too large (sides up to %d, %d pixels in all)", B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  if (subsample < 1 || subsample > SDM_GF_MAX_SUBSAMPLE)
+    SDM_FAIL(e, SDM_ERR_INVALID, "refine alpha: subsample = %d outside 1 .. %d", subsample, SDM_GF_MAX_SUBSAMPLE);
+  if (radius < 1 || radius > SDM_GF_MAX_RADIUS) SDM_FAIL(e, SDM_ERR_INVALID, "refine alpha: radius = %d outside 1 .. %d", radius, SDM_GF_MAX_RADIUS);
+  if (!std::isfinite(eps) || !(eps >= 1e-6f) || !(eps <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "refine alpha: eps = %g must be a finite number in [1e-6, 1]", (double)eps);
+  OptReadLock opt_lock;
+#ifndef SDM_EMU
+  if (ptr_kind == SDM_PTR_DEVICE) {      // stream contract of the forward calls (include/sdmatte.h)
+    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_in, (hipStream_t)stream_arg));
+    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)e->stream, e->ev_in, 0));
+  }
+#else
+  (void)stream_arg;
+#endif
+  const size_t px = (size_t)B * H * W;
+  const size_t img_bytes = px * 12, alpha_bytes = px * 4;
+  const float* d_img = image; const float* d_alpha = alpha; float* d_out = out;
+  if (ptr_kind == SDM_PTR_HOST) {
+    TRY(ensure_buf(e, &e->io_in, &e->io_in_bytes, img_bytes + alpha_bytes));
+    TRY(ensure_buf(e, &e->io_out, &e->io_out_bytes, alpha_bytes));
+    SDM_CHECK_DEV(e, dev_memcpy_h2d(e->io_in, image, img_bytes, e->stream));
+    SDM_CHECK_DEV(e, dev_memcpy_h2d((unsigned char*)e->io_in + img_bytes, alpha, alpha_bytes, e->stream));
+    d_img = (const float*)e->io_in; d_alpha = (const float*)((unsigned char*)e->io_in + img_bytes);
+    d_out = (float*)e->io_out;
+  }
+  const int s = subsample, h = sdm_cdiv(H, s), w = sdm_cdiv(W, s);
+  const double cpx = (double)B * h * w;
+  // runs of 4 pixels = 3 x 16 bytes of image: whole rows of them in the block-mean pass, the flat pixel index in the apply pass
+  const bool mean_vec = W % 4 == 0 && (s == 1 || s == 2 || s % 4 == 0) && aligned16(d_img) && aligned16(d_alpha);
+  const int apply_vec = aligned16(d_img) && aligned16(d_out) ? 1 : 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    arena_pass_begin(e, pass);
+    if (pass == 1 && e->peak > e->arena_bytes) {
+      if (e->arena) { SDM_CHECK_DEV(e, dev_sync(e->stream)); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
+      void* p = nullptr;
+      if (dev_malloc(&p, e->peak) != 0) SDM_FAIL(e, SDM_ERR_NOMEM, "cannot allocate %zu bytes of activation arena", e->peak);
+      e->arena = (unsigned char*)p; e->arena_bytes = e->peak;
+    }
+#ifndef SDM_EMU
+    if (pass == 1) (void)hipEventRecord(e->ev0, (hipStream_t)e->stream);      // sdm_last_forward_ms: the four launches of this call
+#endif
+    // three planes of 4 floats per coarse pixel: (I', p'), (a, b), (abar, bbar)
+    T coarse = talloc(e, B, h, w, 4, 1), ab = talloc(e, B, h, w, 4, 1), abar = talloc(e, B, h, w, 4, 1);
+    if (!e->dry) {
+      const int G = mean_vec && s < 4 ? 4 / s : 1;
+      const dim3 mgrid((unsigned)sdm_cdiv(B * h * (w / G), 256)), blk(256);
+      prof_begin(e, "gf_mean", 0, (double)px * 16 + cpx * 16);
+      count_kernel("gf_mean");
+      if (!mean_vec) SDM_LAUNCH((gf_mean_kernel<1, false>), mgrid, blk, 0, e->stream, d_img, d_alpha, B, H, W, s, h, w, (float*)coarse.p);
+      else if (G == 4) SDM_LAUNCH((gf_mean_kernel<4, true>), mgrid, blk, 0, e->stream, d_img, d_alpha, B, H, W, s, h, w, (float*)coarse.p);
+      else if (G == 2) SDM_LAUNCH((gf_mean_kernel<2, true>), mgrid, blk, 0, e->stream, d_img, d_alpha, B, H, W, s, h, w, (float*)coarse.p);
+      else SDM_LAUNCH((gf_mean_kernel<1, true>), mgrid, blk, 0, e->stream, d_img, d_alpha, B, H, W, s, h, w, (float*)coarse.p);
+      prof_end(e);
+      const dim3 bgrid((unsigned)(B * sdm_cdiv(h, gf_tile_h(radius)) * sdm_cdiv(w, SDM_GF_TW)));
+      prof_begin(e, "gf_fit", 0, cpx * 32);
+      count_kernel("gf_fit");
+      SDM_LAUNCH((gf_box_kernel<true>), bgrid, blk, 0, e->stream, (const float*)coarse.p, B, h, w, radius, eps, (float*)ab.p);
+      prof_end(e);
+      prof_begin(e, "gf_smooth", 0, cpx * 32);
+      count_kernel("gf_smooth");
+      SDM_LAUNCH((gf_box_kernel<false>), bgrid, blk, 0, e->stream, (const float*)ab.p, B, h, w, radius, eps, (float*)abar.p);
+      prof_end(e);
+      prof_begin(e, "gf_apply", 0, (double)px * 16 + cpx * 16);
+      count_kernel("gf_apply");
+      SDM_LAUNCH(gf_apply_kernel, dim3((unsigned)sdm_cdiv((int)((px + 3) / 4), 256)), blk, 0, e->stream, d_img, (const float*)abar.p, B, H, W, s, h, w,
+                 apply_vec, d_out);
+      prof_end(e);
+    }
+    tfree(e, abar); tfree(e, ab); tfree(e, coarse);
+    if (pass == 1) TRY(arena_pass_end(e, 0));
+  }
+  e->dry = false;
+#ifndef SDM_EMU
+  (void)hipEventRecord(e->ev1, (hipStream_t)e->stream);
+#endif
+  if (ptr_kind == SDM_PTR_HOST) {
+    SDM_CHECK_DEV(e, dev_memcpy_d2h(out, e->io_out, alpha_bytes, e->stream));
     SDM_CHECK_DEV(e, dev_sync(e->stream));
   }
 #ifndef SDM_EMU

@@ -82,7 +82,7 @@ EXPORTS = [
     "sdm_default_config", "sdm_create", "sdm_destroy", "sdm_last_error", "sdm_load_tensor", "sdm_finalize_weights",
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
-    "sdm_make_trimap", "sdm_apply_matte_mask", "sdm_estimate_foreground",
+    "sdm_make_trimap", "sdm_apply_matte_mask", "sdm_estimate_foreground", "sdm_refine_alpha_guided",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias",
@@ -119,6 +119,7 @@ class Bindings:
             "sdm_make_trimap": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, vp, i32, vp]),
             "sdm_apply_matte_mask": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, C.c_double, vp, vp, vp, i32, vp]),
             "sdm_estimate_foreground": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
+            "sdm_refine_alpha_guided": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
             "sdm_resident_bytes": (i64, [vp]),
@@ -497,6 +498,45 @@ class Engine:
         if sync:
             self.synchronize()
         return fg, bg
+
+    # SDM_GF_* (include/sdmatte.h)
+    GF_DEFAULTS = {"radius": 2, "eps": 1e-4}
+    GF_MAX_SUBSAMPLE = 16
+    GF_MAX_RADIUS = 32
+
+    @classmethod
+    def _check_gf_params(cls, what, subsample, radius, eps):
+        import math
+        for name, v, hi in (("subsample", subsample, cls.GF_MAX_SUBSAMPLE), ("radius", radius, cls.GF_MAX_RADIUS)):
+            if int(v) != v or not 1 <= int(v) <= hi:
+                raise ValueError(f"{what}: {name} must be an integer in 1 .. {hi}, got {v!r}")
+        eps = C.c_float(float(eps)).value                                # the value that crosses the C ABI
+        if not (math.isfinite(eps) and C.c_float(1e-6).value <= eps <= 1.0):
+            raise ValueError(f"{what}: eps must be a finite number in [1e-6, 1], got {eps!r}")
+        return int(subsample), int(radius), eps
+
+    def refine_alpha_guided(self, image_bhwc, alpha_bhw, subsample, radius=2, eps=1e-4, sync=True):
+        """The alpha [B,H,W] refined at the resolution of the image [B,H,W,3] on the GPU (sdm_refine_alpha_guided, the subsampled colour guided filter
+        defined in include/sdmatte.h): `subsample` is the factor between the image and the resolution the alpha was made at
+        (`sdmatte_nodes.auto_subsample`).  Returns fp32 [B,H,W] in [0,1] on the inputs' device.  Needs no loaded weights.
+        `sdmatte_nodes.guided_refine_alpha` is the same function in torch, equal to fp32 rounding."""
+        if image_bhwc.dim() != 4 or image_bhwc.shape[-1] != 3 or image_bhwc.numel() == 0:
+            raise ValueError(f"refine_alpha_guided: image must be a non-empty [B,H,W,3], got {tuple(image_bhwc.shape)}")
+        B, H, W, _ = (int(v) for v in image_bhwc.shape)
+        if tuple(alpha_bhw.shape) != (B, H, W):
+            raise ValueError(f"refine_alpha_guided: alpha must be [B,H,W] = {(B, H, W)}, got {tuple(alpha_bhw.shape)}")
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"refine_alpha_guided: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        subsample, radius, eps = self._check_gf_params("refine_alpha_guided", subsample, radius, eps)
+        image_bhwc = image_bhwc.float().contiguous()
+        alpha_bhw = alpha_bhw.float().contiguous()
+        out = torch.empty(B, H, W, dtype=torch.float32, device=image_bhwc.device)
+        stream = self._check_io("refine_alpha_guided", image_bhwc, alpha_bhw, out)
+        self._check(self.lib.sdm_refine_alpha_guided(self.h, _ptr(image_bhwc), _ptr(alpha_bhw), B, H, W, subsample, radius, eps, _ptr(out),
+                                                     self._kind(image_bhwc), stream), "sdm_refine_alpha_guided")
+        if sync:
+            self.synchronize()
+        return out
 
     def synchronize(self):
         self._check(self.lib.sdm_synchronize(self.h), "sdm_synchronize")

@@ -289,6 +289,11 @@ class MultiGpuEngine:
         return self.engines[0].estimate_foreground(self._to_host(image_bhwc), self._to_host(alpha_bhw), regularization, gradient_weight, n_small_iters,
                                                    n_big_iters, rgba, want_background)
 
+    def refine_alpha_guided(self, image_bhwc, alpha_bhw, subsample, radius=2, eps=1e-4):
+        """The alpha refined at the image's resolution (no model involved): on the first engine; inputs on the host or any device -> alpha [B,H,W]
+        on the HOST."""
+        return self.engines[0].refine_alpha_guided(self._to_host(image_bhwc), self._to_host(alpha_bhw), subsample, radius, eps)
+
     def apply_matte_mask(self, image_bhwc, mask_bhw, S, is_transparent, output_mode, mask_refine, trimap_constraint, threshold=0.5, erode_px=10,
                          dilate_px=10):
         """`apply_matte_node` with the trimap made from the mask on each GPU (images are independent: so are their trimaps); returns

@@ -16,6 +16,9 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
   * one more node beyond the reference, registered only with SDMATTE_FOREGROUND_NODE=1: `SDMatteForeground` estimates the foreground and
     background colours from the image and the alpha on the GPU (clean cut-outs without the old background's halo); `estimate_foreground`
     below is its CPU restatement;
+  * and one registered only with SDMATTE_REFINE_NODE=1: `SDMatteRefineAlpha` refines the alpha at the image's own resolution with the subsampled
+    colour guided filter on the GPU (the model never sees more than `inference_size` pixels per side); `guided_refine_alpha` below is its torch
+    restatement;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -388,6 +391,78 @@ def estimate_foreground(image, alpha, regularization=1e-5, gradient_weight=1.0, 
     return F.contiguous(), B.contiguous(), alpha
 
 
+def auto_subsample(H, W, inference_size):
+    """The factor between an (H, W) image and the resolution the model saw it at: clamp(ceil(max(H, W) / inference_size), 1, 16)."""
+    H, W, inference_size = int(H), int(W), int(inference_size)
+    if H < 1 or W < 1 or inference_size < 1:
+        raise ValueError(f"auto_subsample: sizes must be positive, got {(H, W, inference_size)}")
+    return min(max(-(-max(H, W) // inference_size), 1), 16)
+
+
+def _window_mean(t, radius):
+    """Mean of t [B,h,w,C] over the (2 radius + 1)^2 window clipped to the grid: direct sums along x, then along y, divided by the window's count."""
+    for axis in (2, 1):
+        n = t.shape[axis]
+        acc = torch.zeros_like(t)
+        for d in range(-radius, radius + 1):
+            lo, hi = max(0, -d), n - max(0, d)          # entries i whose neighbour i + d exists
+            if hi > lo:
+                acc.narrow(axis, lo, hi - lo).add_(t.narrow(axis, lo + d, hi - lo))
+        t = acc
+    h, w = t.shape[1], t.shape[2]
+    iy, ix = torch.arange(h, device=t.device), torch.arange(w, device=t.device)
+    ny = torch.clamp(iy + radius, max=h - 1) - torch.clamp(iy - radius, min=0) + 1
+    nx = torch.clamp(ix + radius, max=w - 1) - torch.clamp(ix - radius, min=0) + 1
+    return t / (ny[:, None] * nx[None, :]).to(t.dtype)[None, :, :, None]
+
+
+def _bilinear_axis(n_full, n_coarse, s, device):
+    u = ((torch.arange(n_full, dtype=torch.float32, device=device) + 0.5) / float(s) - 0.5).clamp(0.0, float(n_coarse - 1))
+    i0 = u.floor().long()
+    return i0, torch.clamp(i0 + 1, max=n_coarse - 1), u - i0.float()
+
+
+def guided_refine_alpha(image, alpha, subsample, radius=2, eps=1e-4):
+    """`Engine.refine_alpha_guided` in torch fp32, on the tensors' own device (the subsampled colour guided filter defined in include/sdmatte.h):
+    image [B,H,W,3], alpha [B,H,W] -> refined alpha [B,H,W] in [0,1].  It and the GPU kernels evaluate the same formulas in fp32 but not in the same
+    order (summation order, FMA contraction), so they agree to rounding, not bit for bit."""
+    from .engine import Engine
+    import torch.nn.functional as F
+    if image.dim() != 4 or image.shape[-1] != 3 or image.numel() == 0:
+        raise ValueError(f"guided_refine_alpha: image must be a non-empty [B,H,W,3], got {tuple(image.shape)}")
+    if tuple(alpha.shape) != tuple(image.shape[:3]):
+        raise ValueError(f"guided_refine_alpha: alpha must be [B,H,W] = {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+    s, radius, eps = Engine._check_gf_params("guided_refine_alpha", subsample, radius, eps)
+    image = image.detach().float()
+    p = torch.nan_to_num(alpha.detach().float(), nan=0.0, posinf=1.0, neginf=0.0).clamp(0.0, 1.0)
+    B, H, W = p.shape
+    h, w = -(-H // s), -(-W // s)
+    x = torch.cat([image, p.unsqueeze(-1)], -1)
+    # block means over the existing pixels: zero-pad to whole blocks, sum, divide by the count
+    x = F.pad(x, (0, 0, 0, w * s - W, 0, h * s - H)).view(B, h, s, w, s, 4).sum(dim=(2, 4))
+    cy = torch.clamp(torch.arange(h, device=x.device) * s + s, max=H) - torch.arange(h, device=x.device) * s
+    cx = torch.clamp(torch.arange(w, device=x.device) * s + s, max=W) - torch.arange(w, device=x.device) * s
+    x = x / (cy[:, None] * cx[None, :]).float()[None, :, :, None]
+    Ic, pc = x[..., :3], x[..., 3:]
+    pairs = [(0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)]
+    m = _window_mean(torch.cat([Ic, pc, Ic * pc] + [Ic[..., i:i + 1] * Ic[..., j:j + 1] for i, j in pairs], -1), radius)       # the 13 moments
+    mu, mup = m[..., 0:3], m[..., 3]
+    c = m[..., 4:7] - mu * mup.unsqueeze(-1)
+    s00, s01, s02, s11, s12, s22 = (m[..., 7 + k] - mu[..., i] * mu[..., j] + (eps if i == j else 0.0) for k, (i, j) in enumerate(pairs))
+    k00, k01, k02 = s11 * s22 - s12 * s12, s02 * s12 - s01 * s22, s01 * s12 - s02 * s11
+    k11, k12, k22 = s00 * s22 - s02 * s02, s01 * s02 - s00 * s12, s00 * s11 - s01 * s01
+    det = s00 * k00 + s01 * k01 + s02 * k02
+    a = torch.stack([k00 * c[..., 0] + k01 * c[..., 1] + k02 * c[..., 2], k01 * c[..., 0] + k11 * c[..., 1] + k12 * c[..., 2],
+                     k02 * c[..., 0] + k12 * c[..., 1] + k22 * c[..., 2]], -1) / det.unsqueeze(-1)
+    b = mup - (a * mu).sum(-1)
+    ab = _window_mean(torch.cat([a, b.unsqueeze(-1)], -1), radius)
+    i0, i1, fy = _bilinear_axis(H, h, s, ab.device)
+    j0, j1, fx = _bilinear_axis(W, w, s, ab.device)
+    rows = (1.0 - fy)[None, :, None, None] * ab[:, i0] + fy[None, :, None, None] * ab[:, i1]
+    up = (1.0 - fx)[None, None, :, None] * rows[:, :, j0] + fx[None, None, :, None] * rows[:, :, j1]
+    return ((up[..., :3] * image).sum(-1) + up[..., 3]).clamp(0.0, 1.0).contiguous()
+
+
 class SDMatteApply:
 
     @classmethod
@@ -540,9 +615,42 @@ class SDMatteForeground:
         return (rgba[..., :3].contiguous(), bg, rgba)
 
 
-def node_mappings(extra: bool, foreground: bool = False):
+class SDMatteRefineAlpha:
+    """Image + alpha -> the alpha refined at the image's own resolution on the GPU (the subsampled colour guided filter): what `Apply SDMatte` returns for
+    a photo larger than `inference_size` is a bilinear enlargement, whose edges are ramps of max(H, W) / inference_size pixels.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE", {"tooltip": "the image the alpha was made for, at its own resolution"}),
+                             "alpha": ("MASK", {"tooltip": "alpha matte of the image (alpha_mask of Apply SDMatte)"}),
+                             "inference_size": SDMatteApply.INPUT_TYPES()["required"]["inference_size"]},
+                "optional": {
+                    "subsample": ("INT", {"default": 0, "min": 0, "max": 16, "step": 1, "tooltip": "factor between the image and the resolution the alpha was made at; 0 = ceil(max(H, W) / inference_size)"}),
+                    "radius": ("INT", {"default": 2, "min": 1, "max": 32, "step": 1, "tooltip": "window radius of the fit, in pixels of the subsampled image"}),
+                    "eps": ("FLOAT", {"default": 1e-4, "min": 1e-6, "max": 1.0, "step": 1e-6, "tooltip": "regularisation of the fit: larger = smoother, follows the image's edges less"}),
+                }}
+
+    RETURN_TYPES = ("MASK", )
+    RETURN_NAMES = ("alpha_mask", )
+    FUNCTION = "refine"
+    CATEGORY = "Matting/SDMatte"
+
+    def refine(self, image, alpha, inference_size=1024, subsample=0, radius=2, eps=1e-4):
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        if alpha.dim() == 2:
+            alpha = alpha.unsqueeze(0)
+        if tuple(alpha.shape) != tuple(image.shape[:3]):
+            raise ValueError(f"[SDMatte] alpha must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+        if int(subsample) == 0:
+            subsample = auto_subsample(image.shape[1], image.shape[2], int(inference_size))
+        eng = _trimap_engine(_torch_device())
+        return (eng.refine_alpha_guided(image.detach().cpu(), alpha.detach().cpu(), int(subsample), int(radius), float(eps)), )
+
+
+def node_mappings(extra: bool, foreground: bool = False, refine: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
-    node when `foreground`."""
+    node when `foreground`, plus the alpha refinement node when `refine`."""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
@@ -551,9 +659,14 @@ def node_mappings(extra: bool, foreground: bool = False):
     if foreground:
         classes["SDMatteForeground"] = SDMatteForeground
         names["SDMatteForeground"] = "SDMatte Foreground Colours"
+    if refine:
+        classes["SDMatteRefineAlpha"] = SDMatteRefineAlpha
+        names["SDMatteRefineAlpha"] = "SDMatte Refine Alpha"
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1), like the multi-GPU fan-out (SDMATTE_MULTI_GPU)
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1), like the multi-GPU fan-out
+# (SDMATTE_MULTI_GPU)
 NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
-                                                                os.environ.get("SDMATTE_FOREGROUND_NODE") == "1")
+                                                                os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
+                                                                os.environ.get("SDMATTE_REFINE_NODE") == "1")

@@ -211,6 +211,36 @@ int sdm_estimate_foreground(sdm_ctx* ctx, const float* image_bhwc, const float* 
                             float gradient_weight, int n_small_iters, int n_big_iters, float* fg_bhwc, int fg_channels, float* bg_bhwc,
                             int ptr_kind, void* stream);
 
+/* Alpha refinement at the caller's resolution, on the GPU (beyond the reference, whose alpha is the model's alpha at `inference_size` brought back
+ * with a bilinear resize: at 4K every edge is a ramp of several pixels).  The colour guided filter in its subsampled form (He, Sun, Tang, "Guided Image
+ * Filtering"; He, Sun, "Fast Guided Filter"): fit alpha ~ a.I + b per window between the coarse alpha and the coarse image, apply the smoothed
+ * coefficients to the full-resolution image.  Everything is fp32.
+ *   image fp32 [B,H,W,3] (values used as they are), alpha fp32 [B,H,W] (p = alpha with NaN -> 0, then clamped to [0,1]), out fp32 [B,H,W] in [0,1]
+ *   coarse    s = subsample, (h,w) = (ceil(H/s), ceil(W/s)); coarse pixel (i,j) of I' (3 channels) and p' is the mean over the existing pixels of block
+ *             [i*s, min(H, i*s+s)) x [j*s, min(W, j*s+s)).  With s = 1 the coarse grid is the image.
+ *   window    Win(i,j) = coarse pixels within Chebyshev distance `radius`, clipped to the grid; n = its pixel count; m(x) = (sum of x over Win) / n
+ *   moments   mu = m(I'), mup = m(p'), c = m(I'*p') - mu*mup, Sigma = m(I' I'^T) - mu mu^T + eps*Id (symmetric: 6 distinct entries)
+ *   solve     a = Sigma^-1 c by the closed-form adjugate of the symmetric 3x3, divided by the determinant; b = mup - a.mu
+ *   smooth    abar = m(a), bbar = m(b)
+ *   upsample  bilinear with half-pixel centres: u = clamp((y + 0.5)/s - 0.5, 0, h - 1), rows i0 = floor(u) and min(i0 + 1, h - 1) with weights
+ *             1 - (u - i0) and u - i0, likewise in x (rows first, then columns)
+ *   apply     out = clamp(abar^ . I + bbar^, 0, 1) at every full-resolution pixel
+ * The window sums are direct sums in a fixed order and every division is a true fp32 division, so an image's result does not depend on the batch it is in.
+ * The subsample is the point of the call: with s = 1 it is the classic filter on the already blurred alpha, which recovers almost nothing; with
+ * s = ceil(max(H,W) / inference_size) the fit is made at the resolution the model saw.  sdmatte_nodes.guided_refine_alpha is the same function in torch
+ * (equal to fp32 rounding, not bit for bit).
+ * subsample in 1 .. SDM_GF_MAX_SUBSAMPLE, radius in 1 .. SDM_GF_MAX_RADIUS, eps finite in [1e-6, 1], H and W >= 1 and within SDM_FG_MAX_SIDE /
+ * SDM_FG_MAX_PIXELS: SDM_ERR_INVALID otherwise.  Stream contract and pointer kinds as sdm_make_trimap.  Needs no weights.  Four kernel launches per call,
+ * whatever B, H, W, subsample and radius (csrc/k_guided.h); with s > 1 exactly two of them touch full-resolution memory (16 bytes per pixel each).  The
+ * three coarse planes are part of the activation arena, host pointers go through the I/O staging (sdm_resident_bytes counts both, sdm_release_memory
+ * frees them). */
+#define SDM_GF_RADIUS 2
+#define SDM_GF_EPS 1e-4f
+#define SDM_GF_MAX_SUBSAMPLE 16
+#define SDM_GF_MAX_RADIUS 32
+int sdm_refine_alpha_guided(sdm_ctx* ctx, const float* image_bhwc, const float* alpha_bhw, int B, int H, int W, int subsample, int radius, float eps,
+                            float* out_bhw, int ptr_kind, void* stream);
+
 /* Memory the engine holds outside any framework allocator: packed weights + activation arena (sized by the largest batch /
  * resolution seen) + I/O staging.  sdm_release_memory frees everything but the weights (the next forward re-allocates). */
 int64_t sdm_resident_bytes(sdm_ctx* ctx);
@@ -236,7 +266,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_estimate_foreground: their launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_estimate_foreground / sdm_refine_alpha_guided: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
