@@ -1055,7 +1055,7 @@ static void arena_release_aside(sdm_ctx* e) {
   e->aside.clear();
 }
 
-// every two-pass loop (forward, run_two_pass): pass 0 sizes the arena without memory, pass 1 launches in it
+// start of either pass of arena_two_pass: pass 0 sizes the arena without memory, pass 1 launches in it
 static void arena_pass_begin(sdm_ctx* e, int pass) {
   arena_release_aside(e);                        // (left behind by a launch pass that ended early)
   e->dry = (pass == 0);
@@ -1072,6 +1072,36 @@ static int arena_pass_end(sdm_ctx* e, int rc) {
   if (!e->adiverged && e->atrace_i != e->atrace.size())
     arena_diverged(e, "allocation %zu: the sizing pass made %zu allocations, the launch pass %zu", e->atrace_i, e->atrace.size(), e->atrace_i);
   if (e->adiverged) SDM_FAIL(e, SDM_ERR_ARENA, "activation arena: the launch pass diverged from the sizing pass at %s", e->adiv_msg.c_str());
+  return 0;
+}
+
+// replaces the arena by one of `bytes`, once the kernels that still use the old one are done
+static int arena_grow(sdm_ctx* e, size_t bytes) {
+  if (e->arena) { SDM_CHECK_DEV(e, dev_sync(e->stream)); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
+  void* p = nullptr;
+  if (dev_malloc(&p, bytes) != 0) SDM_FAIL(e, SDM_ERR_NOMEM, "cannot allocate %zu bytes of activation arena", bytes);
+  e->arena = (unsigned char*)p; e->arena_bytes = bytes;
+  return 0;
+}
+
+// The one two-pass loop: body() runs twice, its tallocs sized without memory first (e->dry), then placed in an arena of at least `floor` bytes
+// that holds their peak.  mark_ev0: the launch pass starts at ev0 (sdm_last_forward_ms).  Every error return goes through arena_pass_end.
+template <typename F>
+static int arena_two_pass(sdm_ctx* e, size_t floor, bool mark_ev0, F body) {
+  for (int pass = 0; pass < 2; ++pass) {
+    arena_pass_begin(e, pass);
+    int rc = 0;
+    if (pass == 1) {
+      if (e->peak > e->arena_bytes) rc = arena_grow(e, std::max(e->peak, floor));
+#ifndef SDM_EMU
+      if (!rc && mark_ev0) (void)hipEventRecord(e->ev0, (hipStream_t)e->stream);
+#else
+      (void)mark_ev0;
+#endif
+    }
+    if (!rc) rc = body();
+    if (rc || pass == 1) return arena_pass_end(e, rc);
+  }
   return 0;
 }
 
@@ -2174,59 +2204,84 @@ struct NodeTail {
   int channels() const { return output_mode == 1 ? 4 : 3; }
 };
 
-static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* trimap, int B, int H, int W, int S, const int32_t* is_trans,
-                        const float* cond, int cond_dim, int cond_kind, bool use_mask, float* out, int ptr_kind, void* stream_arg,
-                        const NodeTail* tail = nullptr) {
-  if (!e->finalized) SDM_FAIL(e, SDM_ERR_STATE, "weights not finalised: call sdm_load_tensor(...) and sdm_finalize_weights first");
-  OptReadLock opt_lock;          // kernel-selection options stay put for both passes of this forward
-  const int SH = (mode == 0) ? H : S, SW = (mode == 0) ? W : S;
-  if (B <= 0 || SH <= 0 || SW <= 0 || SH % 64 || SW % 64)
-    SDM_FAIL(e, SDM_ERR_INVALID, "inference size must be a positive multiple of 64 (got %dx%d)", SH, SW);
-  if (mode == 1 && (H <= 0 || W <= 0)) SDM_FAIL(e, SDM_ERR_INVALID, "bad image size %dx%d", H, W);
-  // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the
-  // stream on which it produced the inputs and will consume the outputs (NULL = the device's default stream): the engine
-  // stream waits for everything queued there at call time, and that stream waits for the outputs before the call returns
-  // control (no host synchronisation).  HOST pointers are copied on the engine stream, followed by a host sync below.
+// One input or output of a product call: the caller's pointer and its size.  product_call replaces `p` by the device-side pointer - the same one
+// for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
+struct IoSpan { void* p; size_t bytes; };
+
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_estimate_foreground, sdm_refine_alpha_guided) around its body, the
+// talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
+// Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
+// produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
+// at call time, and that stream waits for the outputs before the call returns control (no host synchronisation).  HOST pointers are copied
+// on the engine stream through the staging buffers io_in / io_out, packed back to back in list order (the body may pick a kernel by the
+// alignment of what it is given), followed by a host sync.  The arena and the staging are what sdm_resident_bytes counts beside the weights.
+template <size_t NI, size_t NO, typename F>
+static int product_call(sdm_ctx* e, int ptr_kind, void* stream_arg, IoSpan (&in)[NI], IoSpan (&out)[NO], F body) {
+  if (ptr_kind != SDM_PTR_HOST && ptr_kind != SDM_PTR_DEVICE)
+    SDM_FAIL(e, SDM_ERR_INVALID, "unknown ptr_kind %d (SDM_PTR_HOST = %d or SDM_PTR_DEVICE = %d)", ptr_kind, SDM_PTR_HOST, SDM_PTR_DEVICE);
+  OptReadLock opt_lock;          // kernel-selection options stay put for both passes of this call
+  const bool host = ptr_kind == SDM_PTR_HOST;
+  void* host_out[NO];
+  if (host) {
+    size_t in_bytes = 0, out_bytes = 0;
+    for (const IoSpan& s : in) in_bytes += s.bytes;
+    for (const IoSpan& s : out) out_bytes += s.bytes;
+    TRY(ensure_buf(e, &e->io_in, &e->io_in_bytes, in_bytes));
+    TRY(ensure_buf(e, &e->io_out, &e->io_out_bytes, out_bytes));
+    unsigned char* d = (unsigned char*)e->io_in;
+    for (IoSpan& s : in) { SDM_CHECK_DEV(e, dev_memcpy_h2d(d, s.p, s.bytes, e->stream)); s.p = d; d += s.bytes; }
+    d = (unsigned char*)e->io_out;
+    for (size_t i = 0; i < NO; ++i) { host_out[i] = out[i].p; if (out[i].bytes) out[i].p = d; d += out[i].bytes; }
+  }
 #ifndef SDM_EMU
-  if (ptr_kind == SDM_PTR_DEVICE) {
+  else {
     SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_in, (hipStream_t)stream_arg));
     SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)e->stream, e->ev_in, 0));
+  }
+#endif
+  TRY(arena_two_pass(e, 0, true, body));
+#ifndef SDM_EMU
+  (void)hipEventRecord(e->ev1, (hipStream_t)e->stream);
+#endif
+  if (host) {
+    for (size_t i = 0; i < NO; ++i)
+      if (out[i].bytes) SDM_CHECK_DEV(e, dev_memcpy_d2h(host_out[i], out[i].p, out[i].bytes, e->stream));
+    SDM_CHECK_DEV(e, dev_sync(e->stream));
+  }
+#ifndef SDM_EMU
+  else {
+    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_out, (hipStream_t)e->stream));
+    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)stream_arg, e->ev_out, 0));
   }
 #else
   (void)stream_arg;
 #endif
+  return 0;
+}
+
+static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* trimap, int B, int H, int W, int S, const int32_t* is_trans,
+                        const float* cond, int cond_dim, int cond_kind, bool use_mask, float* out, int ptr_kind, void* stream_arg,
+                        const NodeTail* tail = nullptr) {
+  if (!e->finalized) SDM_FAIL(e, SDM_ERR_STATE, "weights not finalised: call sdm_load_tensor(...) and sdm_finalize_weights first");
+  const int SH = (mode == 0) ? H : S, SW = (mode == 0) ? W : S;
+  if (B <= 0 || SH <= 0 || SW <= 0 || SH % 64 || SW % 64)
+    SDM_FAIL(e, SDM_ERR_INVALID, "inference size must be a positive multiple of 64 (got %dx%d)", SH, SW);
+  if (mode == 1 && (H <= 0 || W <= 0)) SDM_FAIL(e, SDM_ERR_INVALID, "bad image size %dx%d", H, W);
   // node API: the trimap may have its own size (the reference resizes image and trimap independently, sdmatte_nodes.py:212-214,349)
   const int TH = (tail && tail->TH > 0) ? tail->TH : H, TW = (tail && tail->TW > 0) ? tail->TW : W;
-  const size_t in_img = (size_t)B * H * W * 3 * 4;          // mode 0: [B,3,SH,SW]; mode 1: [B,H,W,3]
   const size_t in_tri = (size_t)B * TH * TW * 4;
   const size_t alpha_bytes = (size_t)B * H * W * 4;
-  const size_t out_bytes = alpha_bytes * (tail ? 1 + tail->channels() : 1);      // host hand-over: alpha, then the composed image
   const bool from_mask = tail && tail->from_mask;
-  const size_t tri_out_bytes = (from_mask && tail->trimap_out) ? in_tri : 0;     // ... then the trimap made from the mask, if the caller wants it
-  const float* d_img = image; const float* d_tri = trimap; float* d_out = out;
-  float* d_matted = tail ? tail->matted : nullptr;
-  float* d_tri_out = from_mask ? tail->trimap_out : nullptr;
-  if (ptr_kind == SDM_PTR_HOST) {
-    TRY(ensure_buf(e, &e->io_in, &e->io_in_bytes, in_img + in_tri));
-    TRY(ensure_buf(e, &e->io_out, &e->io_out_bytes, out_bytes + tri_out_bytes));
-    if (tri_out_bytes) d_tri_out = (float*)((unsigned char*)e->io_out + out_bytes);
-    SDM_CHECK_DEV(e, dev_memcpy_h2d(e->io_in, image, in_img, e->stream));
-    SDM_CHECK_DEV(e, dev_memcpy_h2d((unsigned char*)e->io_in + in_img, trimap, in_tri, e->stream));
-    d_img = (const float*)e->io_in; d_tri = (const float*)((unsigned char*)e->io_in + in_img); d_out = (float*)e->io_out;
-    if (tail) d_matted = (float*)((unsigned char*)e->io_out + alpha_bytes);
-  }
-  TRY(prepare_variants(e, B, is_trans, cond, cond_dim, cond_kind));
-  for (int pass = 0; pass < 2; ++pass) {
-    arena_pass_begin(e, pass);
-    if (pass == 1 && e->peak > e->arena_bytes) {
-      if (e->arena) { SDM_CHECK_DEV(e, dev_sync(e->stream)); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
-      void* p = nullptr;
-      if (dev_malloc(&p, e->peak) != 0) SDM_FAIL(e, SDM_ERR_NOMEM, "cannot allocate %zu bytes of activation arena", e->peak);
-      e->arena = (unsigned char*)p; e->arena_bytes = e->peak;
-    }
-#ifndef SDM_EMU
-    if (pass == 1) (void)hipEventRecord(e->ev0, (hipStream_t)e->stream);
-#endif
+  IoSpan in[] = {{(void*)image, (size_t)B * H * W * 3 * 4},      // mode 0: [B,3,SH,SW]; mode 1: [B,H,W,3]
+                 {(void*)trimap, in_tri}};
+  IoSpan outs[] = {{out, alpha_bytes},                           // host hand-over: alpha, then the composed image
+                   {tail ? tail->matted : nullptr, tail ? alpha_bytes * tail->channels() : 0},
+                   // ... then the trimap made from the mask, if the caller wants it
+                   {from_mask ? tail->trimap_out : nullptr, (from_mask && tail->trimap_out) ? in_tri : 0}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_img = (const float*)in[0].p; const float* d_tri = (const float*)in[1].p;
+    float* d_out = (float*)outs[0].p; float* d_matted = (float*)outs[1].p; float* d_tri_out = (float*)outs[2].p;
+    if (e->dry) TRY(prepare_variants(e, B, is_trans, cond, cond_dim, cond_kind));      // once per call: behind the input copies, ahead of the launches
     T gtri;      // sdm_apply_matte_mask: the trimap of this call, made from the mask in d_tri; it stands in for d_tri from here on
     const float* tri_in = d_tri;
     if (from_mask) {
@@ -2253,8 +2308,7 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
       }
     }
     T alpha;
-    int rc = run_model(e, x16, plane, B, SH, SW, use_mask, &alpha);
-    if (rc) return arena_pass_end(e, rc);
+    TRY(run_model(e, x16, plane, B, SH, SW, use_mask, &alpha));
     if (!e->dry) {
       if (mode == 0) {
         SDM_CHECK_DEV(e, dev_memcpy_d2d(d_out, alpha.p, (size_t)B * SH * SW * 4, e->stream));
@@ -2267,50 +2321,23 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
       }
     }
     tfree(e, alpha); tfree(e, plane); tfree(e, x16); tfree(e, gtri);
-    if (pass == 1) TRY(arena_pass_end(e, 0));
-  }
-  e->dry = false;
-#ifndef SDM_EMU
-  (void)hipEventRecord(e->ev1, (hipStream_t)e->stream);
-#endif
-  if (ptr_kind == SDM_PTR_HOST) {
-    SDM_CHECK_DEV(e, dev_memcpy_d2h(out, e->io_out, alpha_bytes, e->stream));
-    if (tail) SDM_CHECK_DEV(e, dev_memcpy_d2h(tail->matted, (unsigned char*)e->io_out + alpha_bytes, out_bytes - alpha_bytes, e->stream));
-    if (tri_out_bytes) SDM_CHECK_DEV(e, dev_memcpy_d2h(tail->trimap_out, (unsigned char*)e->io_out + out_bytes, tri_out_bytes, e->stream));
-    SDM_CHECK_DEV(e, dev_sync(e->stream));
-  }
-#ifndef SDM_EMU
-  else {
-    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_out, (hipStream_t)e->stream));
-    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)stream_arg, e->ev_out, 0));
-  }
-#endif
-  return 0;
+    return 0;
+  });
 }
 
-// runs an op outside forward(): arena sized by a dry pass of the same code
+// runs an op outside forward(), for the hooks of sdm_hooks.h: no caller data to stage, an arena of 1 MB or more, a host sync at the end
 template <typename F>
 static int run_two_pass(sdm_ctx* e, F body) {
-  OptReadLock opt_lock;          // (never nested: forward_impl does not come through here)
-  for (int pass = 0; pass < 2; ++pass) {
-    arena_pass_begin(e, pass);
-    if (pass == 1 && e->peak > e->arena_bytes) {
-      if (e->arena) { dev_sync(e->stream); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
-      void* p = nullptr;
-      if (dev_malloc(&p, std::max(e->peak, (size_t)1 << 20)) != 0) { e->dry = false; SDM_FAIL(e, SDM_ERR_NOMEM, "arena alloc failed"); }
-      e->arena = (unsigned char*)p; e->arena_bytes = std::max(e->peak, (size_t)1 << 20);
-    }
+  OptReadLock opt_lock;          // (never nested: the product calls do not come through here)
+  TRY(arena_two_pass(e, (size_t)1 << 20, false, [&]() -> int {
 #ifdef SDM_EMU
-    if (pass == 1 && opt("emu_arena_extra")) {      // self-test of the check: one block the sizing pass did not make, ahead of the op's own
+    if (!e->dry && opt("emu_arena_extra")) {      // self-test of the check: one block the sizing pass did not make, ahead of the op's own
       const size_t b0 = (e->atrace.empty() ? 0 : e->atrace[0]) + 256;
       (void)talloc(e, 1, 1, 1, (int)(b0 / 4), 1);
     }
 #endif
-    int rc = body();
-    if (rc) { if (e->dry) { e->dry = false; return rc; } return arena_pass_end(e, rc); }
-    if (pass == 1) TRY(arena_pass_end(e, 0));
-  }
-  e->dry = false;
+    return body();
+  }));
   SDM_CHECK_DEV(e, dev_sync(e->stream));
   return 0;
 }
@@ -2809,61 +2836,20 @@ int sdm_apply_matte_mask(sdm_ctx* e, const float* image, const float* mask, int 
   return forward_impl(e, 1, image, mask, B, H, W, S, it.data(), nullptr, 4, 0, true, alpha, ptr_kind, stream, &tail);
 }
 
-/* Trimap from a mask on its own (k_trimap.h).  Needs no weights; the distance plane lives in the activation arena and host pointers go through the
- * I/O staging buffers, so sdm_resident_bytes counts what the call keeps and sdm_release_memory frees it. */
+/* Trimap from a mask on its own (k_trimap.h).  The distance plane lives in the activation arena. */
 int sdm_make_trimap(sdm_ctx* e, const float* mask, int B, int H, int W, float threshold, int erode_px, int dilate_px, float* trimap, int ptr_kind,
                     void* stream_arg) {
   if (e) dev_use(e->device);
   if (!e || !mask || !trimap) return SDM_ERR_INVALID;
   TRY(trimap_check(e, B, H, W, erode_px, dilate_px));
-  OptReadLock opt_lock;
-#ifndef SDM_EMU
-  if (ptr_kind == SDM_PTR_DEVICE) {      // stream contract of the forward calls (include/sdmatte.h)
-    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_in, (hipStream_t)stream_arg));
-    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)e->stream, e->ev_in, 0));
-  }
-#else
-  (void)stream_arg;
-#endif
   const size_t bytes = (size_t)B * H * W * 4;
-  const float* d_mask = mask; float* d_out = trimap;
-  if (ptr_kind == SDM_PTR_HOST) {
-    TRY(ensure_buf(e, &e->io_in, &e->io_in_bytes, bytes));
-    TRY(ensure_buf(e, &e->io_out, &e->io_out_bytes, bytes));
-    SDM_CHECK_DEV(e, dev_memcpy_h2d(e->io_in, mask, bytes, e->stream));
-    d_mask = (const float*)e->io_in; d_out = (float*)e->io_out;
-  }
-  for (int pass = 0; pass < 2; ++pass) {
-    arena_pass_begin(e, pass);
-    if (pass == 1 && e->peak > e->arena_bytes) {
-      if (e->arena) { SDM_CHECK_DEV(e, dev_sync(e->stream)); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
-      void* p = nullptr;
-      if (dev_malloc(&p, e->peak) != 0) SDM_FAIL(e, SDM_ERR_NOMEM, "cannot allocate %zu bytes of activation arena", e->peak);
-      e->arena = (unsigned char*)p; e->arena_bytes = e->peak;
-    }
-#ifndef SDM_EMU
-    if (pass == 1) (void)hipEventRecord(e->ev0, (hipStream_t)e->stream);      // sdm_last_forward_ms: the two launches of this call
-#endif
+  IoSpan in[] = {{(void*)mask, bytes}}, out[] = {{trimap, bytes}};
+  return product_call(e, ptr_kind, stream_arg, in, out, [&]() -> int {
     T dist = talloc(e, B, H, W, 1, 0);
-    if (!e->dry) op_trimap(e, d_mask, B, H, W, threshold, erode_px, dilate_px, (short*)dist.p, d_out);
+    if (!e->dry) op_trimap(e, (const float*)in[0].p, B, H, W, threshold, erode_px, dilate_px, (short*)dist.p, (float*)out[0].p);
     tfree(e, dist);
-    if (pass == 1) TRY(arena_pass_end(e, 0));
-  }
-  e->dry = false;
-#ifndef SDM_EMU
-  (void)hipEventRecord(e->ev1, (hipStream_t)e->stream);
-#endif
-  if (ptr_kind == SDM_PTR_HOST) {
-    SDM_CHECK_DEV(e, dev_memcpy_d2h(trimap, e->io_out, bytes, e->stream));
-    SDM_CHECK_DEV(e, dev_sync(e->stream));
-  }
-#ifndef SDM_EMU
-  else {
-    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_out, (hipStream_t)e->stream));
-    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)stream_arg, e->ev_out, 0));
-  }
-#endif
-  return 0;
+    return 0;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2880,8 +2866,7 @@ static std::vector<FgLevel> fg_large_levels(int H, int W) {
   return lv;
 }
 
-/* Needs no weights; the level planes live in the activation arena and host pointers go through the I/O staging buffers, so sdm_resident_bytes
- * counts what the call keeps and sdm_release_memory frees it. */
+/* The level planes live in the activation arena. */
 int sdm_estimate_foreground(sdm_ctx* e, const float* image, const float* alpha, int B, int H, int W, float regularization, float gradient_weight,
                             int n_small_iters, int n_big_iters, float* fg, int fg_channels, float* bg, int ptr_kind, void* stream_arg) {
   if (e) dev_use(e->device);
@@ -2898,40 +2883,15 @@ int sdm_estimate_foreground(sdm_ctx* e, const float* image, const float* alpha, 
   if (n_big_iters < 1 || n_big_iters > SDM_FG_MAX_BIG_ITERS)
     SDM_FAIL(e, SDM_ERR_INVALID, "estimate foreground: n_big_iters = %d outside 1 .. %d", n_big_iters, SDM_FG_MAX_BIG_ITERS);
   if (fg_channels != 3 && fg_channels != 4) SDM_FAIL(e, SDM_ERR_INVALID, "estimate foreground: fg_channels = %d, must be 3 or 4", fg_channels);
-  OptReadLock opt_lock;
-#ifndef SDM_EMU
-  if (ptr_kind == SDM_PTR_DEVICE) {      // stream contract of the forward calls (include/sdmatte.h)
-    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_in, (hipStream_t)stream_arg));
-    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)e->stream, e->ev_in, 0));
-  }
-#else
-  (void)stream_arg;
-#endif
   const size_t px = (size_t)B * H * W;
-  const size_t img_bytes = px * 12, alpha_bytes = px * 4, fg_bytes = px * 4 * fg_channels, bg_bytes = bg ? px * 12 : 0;
-  const float* d_img = image; const float* d_alpha = alpha; float* d_fg = fg; float* d_bg = bg;
-  if (ptr_kind == SDM_PTR_HOST) {
-    TRY(ensure_buf(e, &e->io_in, &e->io_in_bytes, img_bytes + alpha_bytes));
-    TRY(ensure_buf(e, &e->io_out, &e->io_out_bytes, fg_bytes + bg_bytes));
-    SDM_CHECK_DEV(e, dev_memcpy_h2d(e->io_in, image, img_bytes, e->stream));
-    SDM_CHECK_DEV(e, dev_memcpy_h2d((unsigned char*)e->io_in + img_bytes, alpha, alpha_bytes, e->stream));
-    d_img = (const float*)e->io_in; d_alpha = (const float*)((unsigned char*)e->io_in + img_bytes);
-    d_fg = (float*)e->io_out; d_bg = bg ? (float*)((unsigned char*)e->io_out + fg_bytes) : nullptr;
-  }
+  IoSpan in[] = {{(void*)image, px * 12}, {(void*)alpha, px * 4}};
+  IoSpan out[] = {{fg, px * 4 * fg_channels}, {bg, bg ? px * 12 : 0}};
   const std::vector<FgLevel> lv = fg_large_levels(H, W);
   const int nl = (int)lv.size();
   const int tw = fg_tile_w(n_big_iters), th = fg_tile_h(n_big_iters);
-  for (int pass = 0; pass < 2; ++pass) {
-    arena_pass_begin(e, pass);
-    if (pass == 1 && e->peak > e->arena_bytes) {
-      if (e->arena) { SDM_CHECK_DEV(e, dev_sync(e->stream)); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
-      void* p = nullptr;
-      if (dev_malloc(&p, e->peak) != 0) SDM_FAIL(e, SDM_ERR_NOMEM, "cannot allocate %zu bytes of activation arena", e->peak);
-      e->arena = (unsigned char*)p; e->arena_bytes = e->peak;
-    }
-#ifndef SDM_EMU
-    if (pass == 1) (void)hipEventRecord(e->ev0, (hipStream_t)e->stream);      // sdm_last_forward_ms: the launches of this call
-#endif
+  return product_call(e, ptr_kind, stream_arg, in, out, [&]() -> int {
+    const float* d_img = (const float*)in[0].p; const float* d_alpha = (const float*)in[1].p;
+    float* d_fg = (float*)out[0].p; float* d_bg = (float*)out[1].p;
     // one plane of 8 floats per pixel for every level below the top one, the largest small level included: planes[i] belongs to lv[i]
     std::vector<T> planes((size_t)nl);
     for (int i = 1; i < nl; ++i) planes[i] = talloc(e, B, lv[i].h, lv[i].w, 8, 1);
@@ -2954,24 +2914,8 @@ int sdm_estimate_foreground(sdm_ctx* e, const float* image, const float* alpha, 
       }
     }
     for (int i = nl - 1; i >= 1; --i) tfree(e, planes[i]);
-    if (pass == 1) TRY(arena_pass_end(e, 0));
-  }
-  e->dry = false;
-#ifndef SDM_EMU
-  (void)hipEventRecord(e->ev1, (hipStream_t)e->stream);
-#endif
-  if (ptr_kind == SDM_PTR_HOST) {
-    SDM_CHECK_DEV(e, dev_memcpy_d2h(fg, e->io_out, fg_bytes, e->stream));
-    if (bg) SDM_CHECK_DEV(e, dev_memcpy_d2h(bg, (unsigned char*)e->io_out + fg_bytes, bg_bytes, e->stream));
-    SDM_CHECK_DEV(e, dev_sync(e->stream));
-  }
-#ifndef SDM_EMU
-  else {
-    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_out, (hipStream_t)e->stream));
-    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)stream_arg, e->ev_out, 0));
-  }
-#endif
-  return 0;
+    return 0;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2979,8 +2923,7 @@ int sdm_estimate_foreground(sdm_ctx* e, const float* image, const float* alpha, 
 // ------------------------------------------------------------------------------------------------
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-/* Needs no weights; the three coarse planes live in the activation arena and host pointers go through the I/O staging buffers, so sdm_resident_bytes
- * counts what the call keeps and sdm_release_memory frees it.  Four launches, whatever the arguments. */
+/* The three coarse planes live in the activation arena.  Four launches, whatever the arguments. */
 int sdm_refine_alpha_guided(sdm_ctx* e, const float* image, const float* alpha, int B, int H, int W, int subsample, int radius, float eps, float* out,
                             int ptr_kind, void* stream_arg) {
   if (e) dev_use(e->device);
@@ -2993,42 +2936,15 @@ int sdm_refine_alpha_guided(sdm_ctx* e, const float* image, const float* alpha, 
   if (radius < 1 || radius > SDM_GF_MAX_RADIUS) SDM_FAIL(e, SDM_ERR_INVALID, "refine alpha: radius = %d outside 1 .. %d", radius, SDM_GF_MAX_RADIUS);
   if (!std::isfinite(eps) || !(eps >= 1e-6f) || !(eps <= 1.0f))
     SDM_FAIL(e, SDM_ERR_INVALID, "refine alpha: eps = %g must be a finite number in [1e-6, 1]", (double)eps);
-  OptReadLock opt_lock;
-#ifndef SDM_EMU
-  if (ptr_kind == SDM_PTR_DEVICE) {      // stream contract of the forward calls (include/sdmatte.h)
-    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_in, (hipStream_t)stream_arg));
-    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)e->stream, e->ev_in, 0));
-  }
-#else
-  (void)stream_arg;
-#endif
   const size_t px = (size_t)B * H * W;
-  const size_t img_bytes = px * 12, alpha_bytes = px * 4;
-  const float* d_img = image; const float* d_alpha = alpha; float* d_out = out;
-  if (ptr_kind == SDM_PTR_HOST) {
-    TRY(ensure_buf(e, &e->io_in, &e->io_in_bytes, img_bytes + alpha_bytes));
-    TRY(ensure_buf(e, &e->io_out, &e->io_out_bytes, alpha_bytes));
-    SDM_CHECK_DEV(e, dev_memcpy_h2d(e->io_in, image, img_bytes, e->stream));
-    SDM_CHECK_DEV(e, dev_memcpy_h2d((unsigned char*)e->io_in + img_bytes, alpha, alpha_bytes, e->stream));
-    d_img = (const float*)e->io_in; d_alpha = (const float*)((unsigned char*)e->io_in + img_bytes);
-    d_out = (float*)e->io_out;
-  }
+  IoSpan in[] = {{(void*)image, px * 12}, {(void*)alpha, px * 4}}, outs[] = {{out, px * 4}};
   const int s = subsample, h = sdm_cdiv(H, s), w = sdm_cdiv(W, s);
   const double cpx = (double)B * h * w;
-  // runs of 4 pixels = 3 x 16 bytes of image: whole rows of them in the block-mean pass, the flat pixel index in the apply pass
-  const bool mean_vec = W % 4 == 0 && (s == 1 || s == 2 || s % 4 == 0) && aligned16(d_img) && aligned16(d_alpha);
-  const int apply_vec = aligned16(d_img) && aligned16(d_out) ? 1 : 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    arena_pass_begin(e, pass);
-    if (pass == 1 && e->peak > e->arena_bytes) {
-      if (e->arena) { SDM_CHECK_DEV(e, dev_sync(e->stream)); dev_free(e->arena); e->arena = nullptr; e->arena_bytes = 0; }
-      void* p = nullptr;
-      if (dev_malloc(&p, e->peak) != 0) SDM_FAIL(e, SDM_ERR_NOMEM, "cannot allocate %zu bytes of activation arena", e->peak);
-      e->arena = (unsigned char*)p; e->arena_bytes = e->peak;
-    }
-#ifndef SDM_EMU
-    if (pass == 1) (void)hipEventRecord(e->ev0, (hipStream_t)e->stream);      // sdm_last_forward_ms: the four launches of this call
-#endif
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_img = (const float*)in[0].p; const float* d_alpha = (const float*)in[1].p; float* d_out = (float*)outs[0].p;
+    // runs of 4 pixels = 3 x 16 bytes of image: whole rows of them in the block-mean pass, the flat pixel index in the apply pass
+    const bool mean_vec = W % 4 == 0 && (s == 1 || s == 2 || s % 4 == 0) && aligned16(d_img) && aligned16(d_alpha);
+    const int apply_vec = aligned16(d_img) && aligned16(d_out) ? 1 : 0;
     // three planes of 4 floats per coarse pixel: (I', p'), (a, b), (abar, bbar)
     T coarse = talloc(e, B, h, w, 4, 1), ab = talloc(e, B, h, w, 4, 1), abar = talloc(e, B, h, w, 4, 1);
     if (!e->dry) {
@@ -3057,23 +2973,8 @@ int sdm_refine_alpha_guided(sdm_ctx* e, const float* image, const float* alpha, 
       prof_end(e);
     }
     tfree(e, abar); tfree(e, ab); tfree(e, coarse);
-    if (pass == 1) TRY(arena_pass_end(e, 0));
-  }
-  e->dry = false;
-#ifndef SDM_EMU
-  (void)hipEventRecord(e->ev1, (hipStream_t)e->stream);
-#endif
-  if (ptr_kind == SDM_PTR_HOST) {
-    SDM_CHECK_DEV(e, dev_memcpy_d2h(out, e->io_out, alpha_bytes, e->stream));
-    SDM_CHECK_DEV(e, dev_sync(e->stream));
-  }
-#ifndef SDM_EMU
-  else {
-    SDM_CHECK_DEV(e, (int)hipEventRecord(e->ev_out, (hipStream_t)e->stream));
-    SDM_CHECK_DEV(e, (int)hipStreamWaitEvent((hipStream_t)stream_arg, e->ev_out, 0));
-  }
-#endif
-  return 0;
+    return 0;
+  });
 }
 
 int sdm_synchronize(sdm_ctx* e) {

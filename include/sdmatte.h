@@ -8,7 +8,8 @@
  *
  * Pointer kinds: every data pointer is either a HOST pointer or a DEVICE pointer of the engine's GPU,
  * selected by the `ptr_kind` argument (SDM_PTR_HOST / SDM_PTR_DEVICE).  Device pointers are what
- * `tensor.data_ptr()` returns for PyTorch-ROCm tensors at the node boundary.
+ * `tensor.data_ptr()` returns for PyTorch-ROCm tensors at the node boundary.  Any other `ptr_kind` is SDM_ERR_INVALID: nothing is queued and no
+ * output is written.
  */
 #ifndef SDMATTE_H_
 #define SDMATTE_H_
