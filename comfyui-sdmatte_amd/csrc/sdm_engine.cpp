@@ -18,6 +18,7 @@
 #include "k_attn.h"
 #include "k_misc.h"
 #include "k_trimap.h"
+#include "k_cclabel.h"
 #include "k_foreground.h"
 #include "k_guided.h"
 #include "../../include/sdmatte.h"
@@ -2208,7 +2209,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_estimate_foreground, sdm_refine_alpha_guided) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_estimate_foreground, sdm_refine_alpha_guided) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -2973,6 +2974,90 @@ int sdm_refine_alpha_guided(sdm_ctx* e, const float* image, const float* alpha, 
       prof_end(e);
     }
     tfree(e, abar); tfree(e, ab); tfree(e, coarse);
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// mask clean-up: islands, holes, largest component (k_cclabel.h)
+// ------------------------------------------------------------------------------------------------
+static int clean_check(sdm_ctx* e, int B, int H, int W, float threshold, int min_area, int keep_largest, int max_hole_area, int binarize) {
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "clean mask: bad mask size %dx%dx%d", B, H, W);
+  // the labels are global pixel indices in an int
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "clean mask: %dx%dx%d is too large (sides up to %d, %d pixels in all)", B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  // below 1, so that the 0.0 and 1.0 the call writes lie on the right side of it
+  if (!std::isfinite(threshold) || !(threshold >= 0.0f) || !(threshold < 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "clean mask: threshold = %g must be a finite number in [0, 1)", (double)threshold);
+  if (min_area < 0 || min_area > SDM_FG_MAX_PIXELS || max_hole_area < 0 || max_hole_area > SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "clean mask: min_area = %d, max_hole_area = %d outside 0 .. %d", min_area, max_hole_area, SDM_FG_MAX_PIXELS);
+  if ((keep_largest != 0 && keep_largest != 1) || (binarize != 0 && binarize != 1))
+    SDM_FAIL(e, SDM_ERR_INVALID, "clean mask: keep_largest = %d, binarize = %d must be 0 or 1", keep_largest, binarize);
+  return 0;
+}
+
+// one labelling: tile, seam, flatten (3 launches).  Afterwards root[p] is the smallest pixel index of p's component (-1 outside the class) and
+// area[root] its pixel count, or >= SDM_CC_BORDER for a stage B component on the image border.
+static void op_cc_label(sdm_ctx* e, const float* src, int B, int H, int W, float threshold, bool stage_b, int* label, int* root, int* area, int* sel,
+                        int* stats) {
+  const double px = (double)B * H * W;
+  const int tiles = B * sdm_cdiv(H, SDM_CC_T) * sdm_cdiv(W, SDM_CC_T);
+  const int vec = (H * W) % 4 == 0 ? 1 : 0;      // (the planes start on arena boundaries of 256 bytes)
+  prof_begin(e, "cc_tile", 0, px * 12);
+  count_kernel("cc_tile");
+  SDM_LAUNCH(cc_tile_kernel, dim3((unsigned)tiles), dim3(256), 0, e->stream, src, label, area, B, H, W, threshold, stage_b ? 1 : 0, stage_b ? 0 : 1, sel, stats);
+  prof_end(e);
+  prof_begin(e, "cc_seam", 0, px * 4 * 3 / SDM_CC_T);
+  count_kernel("cc_seam");
+  SDM_LAUNCH(cc_seam_kernel, dim3((unsigned)tiles), dim3(256), 0, e->stream, label, B, H, W, stage_b ? 0 : 1);
+  prof_end(e);
+  prof_begin(e, "cc_flatten", 0, px * 8);
+  count_kernel("cc_flatten");
+  SDM_LAUNCH(cc_flatten_kernel, dim3((unsigned)(B * sdm_cdiv(H * W, SDM_CC_FLAT_PX))), dim3(256), 0, e->stream, (const int*)label, root, area, B, H, W, stage_b ? 1 : 0, vec, stats);
+  prof_end(e);
+}
+
+/* The label, root and area planes (4 bytes per pixel each) and the selection words live in the activation arena.  Launches: stage A 6 (tile, seam, flatten,
+ * select x 2, apply), stage B 4 (tile, seam, flatten, fill); with stage A off the apply launch is the threshold / copy, preceded by one labelling
+ * (3 launches) if statistics are asked for. */
+int sdm_clean_mask(sdm_ctx* e, const float* mask, int B, int H, int W, float threshold, int min_area, int keep_largest, int max_hole_area, int binarize,
+                   float* out, int32_t* stats, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !mask || !out) return SDM_ERR_INVALID;
+  TRY(clean_check(e, B, H, W, threshold, min_area, keep_largest, max_hole_area, binarize));
+  const size_t px = (size_t)B * H * W;
+  IoSpan in[] = {{(void*)mask, px * 4}}, outs[] = {{out, px * 4}, {stats, stats ? (size_t)B * SDM_CLEAN_STATS * 4 : 0}};
+  const bool stage_a = min_area > 1 || keep_largest, stage_b = max_hole_area > 0;
+  const bool label_a = stage_a || stats != nullptr;      // the first statistic is the component count of the input
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_mask = (const float*)in[0].p; float* d_out = (float*)outs[0].p; int* d_stats = (int*)outs[1].p;
+    T label, root, area, sel;
+    if (label_a || stage_b) { label = talloc(e, B, H, W, 1, 1); root = talloc(e, B, H, W, 1, 1); area = talloc(e, B, H, W, 1, 1); sel = talloc(e, B, 1, 1, 2, 1); }
+    if (!e->dry) {
+      const int chunks = B * sdm_cdiv(H * W, SDM_CC_PX);
+      const int vec = (H * W) % 4 == 0 ? 1 : 0;
+      if (label_a) op_cc_label(e, d_mask, B, H, W, threshold, false, (int*)label.p, (int*)root.p, (int*)area.p, (int*)sel.p, d_stats);
+      if (stage_a)
+        for (int phase = 0; phase < 2; ++phase) {
+          prof_begin(e, "cc_select", 0, (double)px * 4);
+          count_kernel("cc_select");
+          SDM_LAUNCH(cc_select_kernel, dim3((unsigned)chunks), dim3(256), 0, e->stream, (const int*)root.p, (const int*)area.p, B, H, W, phase, vec, (int*)sel.p);
+          prof_end(e);
+        }
+      prof_begin(e, "cc_apply", 0, (double)px * (stage_a ? 12 : 8));
+      count_kernel("cc_apply");
+      SDM_LAUNCH(cc_apply_kernel, dim3((unsigned)chunks), dim3(256), 0, e->stream, d_mask, (const int*)root.p, (const int*)area.p, (const int*)sel.p, d_out, B, H, W,
+                 threshold, stage_a ? 1 : 0, min_area, keep_largest, binarize, (vec && aligned16(d_mask) && aligned16(d_out)) ? 1 : 0, d_stats);
+      prof_end(e);
+      if (stage_b) {
+        op_cc_label(e, d_out, B, H, W, threshold, true, (int*)label.p, (int*)root.p, (int*)area.p, nullptr, nullptr);
+        prof_begin(e, "cc_fill", 0, (double)px * 4);
+        count_kernel("cc_fill");
+        SDM_LAUNCH(cc_fill_kernel, dim3((unsigned)chunks), dim3(256), 0, e->stream, (const int*)root.p, (const int*)area.p, d_out, B, H, W, max_hole_area, vec, d_stats);
+        prof_end(e);
+      }
+    }
+    if (label_a || stage_b) { tfree(e, sel); tfree(e, area); tfree(e, root); tfree(e, label); }
     return 0;
   });
 }

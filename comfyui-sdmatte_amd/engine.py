@@ -82,7 +82,7 @@ EXPORTS = [
     "sdm_default_config", "sdm_create", "sdm_destroy", "sdm_last_error", "sdm_load_tensor", "sdm_finalize_weights",
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
-    "sdm_make_trimap", "sdm_apply_matte_mask", "sdm_estimate_foreground", "sdm_refine_alpha_guided",
+    "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_estimate_foreground", "sdm_refine_alpha_guided",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias",
@@ -117,6 +117,7 @@ class Bindings:
             "sdm_apply_matte": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
             "sdm_apply_matte_node": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, vp, vp, i32, vp]),
             "sdm_make_trimap": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, vp, i32, vp]),
+            "sdm_clean_mask": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, vp, vp, i32, vp]),
             "sdm_apply_matte_mask": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, C.c_double, vp, vp, vp, i32, vp]),
             "sdm_estimate_foreground": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
             "sdm_refine_alpha_guided": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp]),
@@ -420,6 +421,37 @@ class Engine:
         if sync:
             self.synchronize()
         return out
+
+    CLEAN_MAX_AREA = 1 << 28     # SDM_FG_MAX_PIXELS (include/sdmatte.h)
+
+    def clean_mask(self, mask, threshold=0.5, min_area=64, keep_largest=False, max_hole_area=64, binarize=False, out=None, sync=True,
+                   return_stats=False):
+        """Mask clean-up on the GPU (sdm_clean_mask): mask [B,H,W] -> fp32 [B,H,W] without the 8-connected components of `mask > threshold` smaller than
+        min_area (with keep_largest: without all but the largest one) and with the holes of at most max_hole_area pixels filled; removed pixels are 0.0,
+        filled ones 1.0, every other pixel keeps its value (or becomes 1.0 / 0.0 with binarize).  return_stats: also int32 [B,4] = per image {components,
+        components removed, holes filled, pixels changed}.  Needs no loaded weights.  `sdmatte_nodes.clean_mask` is the same function on CPU tensors,
+        bit for bit."""
+        if mask.dim() != 3 or mask.numel() == 0:
+            raise ValueError(f"clean_mask: mask must be a non-empty [B,H,W], got {tuple(mask.shape)}")
+        threshold = float(threshold)
+        if not (0.0 <= threshold < 1.0) or float(np.float32(threshold)) >= 1.0:
+            raise ValueError(f"clean_mask: threshold must be in [0, 1), got {threshold!r}")
+        for name, v in (("min_area", min_area), ("max_hole_area", max_hole_area)):
+            if int(v) != v or not 0 <= int(v) <= self.CLEAN_MAX_AREA:
+                raise ValueError(f"clean_mask: {name} must be an integer in 0 .. {self.CLEAN_MAX_AREA}, got {v!r}")
+        B, H, W = (int(v) for v in mask.shape)
+        mask = mask.float().contiguous()
+        if out is None:
+            out = torch.empty(B, H, W, dtype=torch.float32, device=mask.device)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * H * W:
+            raise ValueError("clean_mask: out must be a contiguous fp32 tensor of B*H*W elements")
+        stats = torch.empty(B, 4, dtype=torch.int32, device=mask.device) if return_stats else None
+        stream = self._check_io("clean_mask", mask, out)
+        self._check(self.lib.sdm_clean_mask(self.h, _ptr(mask), B, H, W, threshold, int(min_area), 1 if keep_largest else 0, int(max_hole_area),
+                                            1 if binarize else 0, _ptr(out), _ptr(stats), self._kind(mask), stream), "sdm_clean_mask")
+        if sync:
+            self.synchronize()
+        return (out, stats) if return_stats else out
 
     def apply_matte_mask(self, image_bhwc, mask_bhw, S, is_transparent, output_mode, mask_refine, trimap_constraint, threshold=0.5, erode_px=10,
                          dilate_px=10, sync=True):

@@ -282,6 +282,11 @@ class MultiGpuEngine:
         """Trimap from a mask (no model involved): on the first engine; mask [B,H,W] (host or any device) -> trimap on the HOST."""
         return self.engines[0].make_trimap(self._to_host(mask_bhw), threshold, erode_px, dilate_px)
 
+    def clean_mask(self, mask_bhw, threshold=0.5, min_area=64, keep_largest=False, max_hole_area=64, binarize=False, return_stats=False):
+        """Mask clean-up (no model involved): on the first engine; mask [B,H,W] (host or any device) -> cleaned mask (and statistics) on the HOST."""
+        return self.engines[0].clean_mask(self._to_host(mask_bhw), threshold, min_area, keep_largest, max_hole_area, binarize,
+                                          return_stats=return_stats)
+
     def estimate_foreground(self, image_bhwc, alpha_bhw, regularization=1e-5, gradient_weight=1.0, n_small_iters=10, n_big_iters=2, rgba=False,
                             want_background=True):
         """Foreground / background colours from image + alpha (no model involved): on the first engine; inputs on the host or any device ->

@@ -341,6 +341,97 @@ def trimap_from_mask(mask, threshold=0.5, erode_px=10, dilate_px=10):
     return out
 
 
+def _component_roots(cls, conn8):
+    """cls bool [H,W] -> int64 [H,W]: per pixel of the class the smallest flat index y*W + x of its component (8- or 4-connected), H*W elsewhere.
+    Label equivalence in numpy: every pixel takes the smallest label around it, hooks its root to it, then all pointers are jumped to their roots;
+    repeated until nothing moves.  Labels are pixel indices of the component and only decrease, so the fixed point is the component's smallest index."""
+    import numpy as np
+    H, W = cls.shape
+    n = H * W
+    flat = cls.ravel()
+    lab = np.where(flat, np.arange(n, dtype=np.int64), n)
+    lab = np.append(lab, n)                                   # slot n: "no pixel", its own root
+    idx = np.flatnonzero(flat)
+    steps = [(0, 1), (1, 0)] + ([(1, 1), (1, -1)] if conn8 else [])
+    while True:
+        grid = lab[:n].reshape(H, W)
+        best = grid.copy()
+        for dy, dx in steps:
+            for sy, sx in ((dy, dx), (-dy, -dx)):
+                y0, y1, x0, x1 = max(0, -sy), H - max(0, sy), max(0, -sx), W - max(0, sx)
+                if y1 > y0 and x1 > x0:
+                    np.minimum(best[y0:y1, x0:x1], grid[y0 + sy:y1 + sy, x0 + sx:x1 + sx], out=best[y0:y1, x0:x1])
+        best = best.ravel()[idx]
+        low = best < lab[idx]
+        if not low.any():
+            return lab[:n].reshape(H, W)
+        np.minimum.at(lab, lab[idx][low], best[low])
+        while True:
+            nxt = lab[lab[idx]]
+            if np.array_equal(nxt, lab[idx]):
+                break
+            lab[idx] = nxt
+
+
+def clean_mask(mask, threshold=0.5, min_area=64, keep_largest=False, max_hole_area=64, binarize=False, return_stats=False):
+    """`Engine.clean_mask` on CPU tensors, bit for bit (compares and counts only; the definition is in include/sdmatte.h, sdm_clean_mask): mask [B,H,W] ->
+    fp32 [B,H,W], and with return_stats int32 [B,4] = per image {components, components removed, holes filled, pixels whose class changed}."""
+    import numpy as np
+    if mask.dim() != 3 or mask.numel() == 0:
+        raise ValueError(f"clean_mask: mask must be a non-empty [B,H,W], got {tuple(mask.shape)}")
+    thr = np.float32(threshold)
+    if not (np.float32(0) <= thr < np.float32(1)) or not 0.0 <= float(threshold) < 1.0:
+        raise ValueError(f"clean_mask: threshold must be in [0, 1), got {threshold!r}")
+    for name, v in (("min_area", min_area), ("max_hole_area", max_hole_area)):
+        if int(v) != v or not 0 <= int(v) <= (1 << 28):
+            raise ValueError(f"clean_mask: {name} must be an integer in 0 .. {1 << 28}, got {v!r}")
+    m = mask.detach().cpu().float().contiguous().numpy()
+    B, H, W = m.shape
+    n = H * W
+    out = m.copy()
+    stats = np.zeros((B, 4), np.int32)
+    for b in range(B):
+        with np.errstate(invalid="ignore"):
+            fg = m[b] > thr
+        keep = fg
+        if min_area > 1 or keep_largest or return_stats:
+            roots = _component_roots(fg, True).ravel()
+            area = np.bincount(roots, minlength=n + 1)[:n]
+            ids = np.flatnonzero(area)                         # ascending = by smallest pixel index
+            stats[b, 0] = ids.size
+            if min_area > 1 or keep_largest:
+                ok = area[ids] >= min_area
+                if keep_largest and ids.size:
+                    ok &= ids == ids[np.argmax(area[ids])]      # argmax: the first of equal areas
+                good = np.zeros(n + 1, bool)
+                good[ids[ok]] = True
+                keep = good[roots].reshape(H, W)
+                stats[b, 1] = int((~ok).sum())
+        filled = np.zeros_like(fg)
+        if max_hole_area > 0:
+            roots = _component_roots(~keep, False).ravel()
+            area = np.bincount(roots, minlength=n + 1)[:n]
+            edge = np.zeros((H, W), bool)
+            edge[0] = edge[-1] = True
+            edge[:, 0] = edge[:, -1] = True
+            open_ = np.zeros(n + 1, bool)
+            open_[roots[edge.ravel()]] = True
+            ids = np.flatnonzero(area)
+            holes = ids[~open_[ids] & (area[ids] <= max_hole_area)]
+            good = np.zeros(n + 1, bool)
+            good[holes] = True
+            filled = good[roots].reshape(H, W)
+            stats[b, 2] = holes.size
+        removed = fg & ~keep
+        if binarize:
+            out[b] = fg.astype(np.float32)
+        out[b][removed] = 0.0
+        out[b][filled] = 1.0
+        stats[b, 3] = int(removed.sum()) + int(filled.sum())
+    out = torch.from_numpy(out)
+    return (out, torch.from_numpy(stats)) if return_stats else out
+
+
 def _nearest_index(n_dst, n_src):
     """src = min(n_src - 1, (i * n_src) // n_dst) for i = 0 .. n_dst - 1 (integers only)."""
     return torch.clamp((torch.arange(n_dst, dtype=torch.int64) * n_src) // n_dst, max=n_src - 1)
@@ -540,6 +631,42 @@ class SDMatteTrimapFromMask:
         return (eng.make_trimap(mask.detach().cpu(), float(threshold), int(erode_px), int(dilate_px)), )
 
 
+_CLEAN_INPUTS = {
+    "threshold": ("FLOAT", {"default": 0.5, "min": 0.0, "max": 0.99, "step": 0.01, "tooltip": "mask values above this are foreground"}),
+    "min_area": ("INT", {"default": 64, "min": 0, "max": 1 << 28, "step": 1, "tooltip": "foreground islands of fewer pixels are removed (0 or 1: none)"}),
+    "keep_largest": ("BOOLEAN", {"default": False, "tooltip": "keep only the largest foreground component"}),
+    "max_hole_area": ("INT", {"default": 64, "min": 0, "max": 1 << 28, "step": 1, "tooltip": "holes of at most this many pixels are filled (0: none)"}),
+    "binarize": ("BOOLEAN", {"default": False, "tooltip": "return 1.0 / 0.0 instead of the mask's own values where nothing changed"}),
+}
+
+
+class SDMatteCleanMask:
+    """Mask -> the mask without stray islands and pin-holes (optionally: only its largest component), on the GPU, for the trimap node after it;
+    needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": dict({"mask": ("MASK", {"tooltip": "mask to clean (SAM, RMBG, a selection)"})}, **_CLEAN_INPUTS)}
+
+    RETURN_TYPES = ("MASK", )
+    RETURN_NAMES = ("mask", )
+    FUNCTION = "clean"
+    CATEGORY = "Matting/SDMatte"
+
+    def clean(self, mask, threshold=0.5, min_area=64, keep_largest=False, max_hole_area=64, binarize=False):
+        if mask.dim() == 2:
+            mask = mask.unsqueeze(0)
+        if mask.dim() != 3 or mask.numel() == 0:
+            raise ValueError(f"[SDMatte] mask must be a non-empty [B,H,W], got {tuple(mask.shape)}")
+        if not 0.0 <= float(threshold) < 1.0:
+            raise ValueError(f"[SDMatte] threshold must be in [0, 1), got {threshold!r}")
+        for name, v in (("min_area", min_area), ("max_hole_area", max_hole_area)):
+            if int(v) != v or not 0 <= int(v) <= (1 << 28):
+                raise ValueError(f"[SDMatte] {name} must be an integer in 0 .. {1 << 28}, got {v!r}")
+        eng = _trimap_engine(_torch_device())
+        return (eng.clean_mask(mask.detach().cpu(), float(threshold), int(min_area), bool(keep_largest), int(max_hole_area), bool(binarize)), )
+
+
 class SDMatteApplyMask:
     """`Apply SDMatte` fed with a mask: the trimap is made from it on the GPU inside the same engine call, and returned as well."""
 
@@ -648,9 +775,9 @@ class SDMatteRefineAlpha:
         return (eng.refine_alpha_guided(image.detach().cpu(), alpha.detach().cpu(), int(subsample), int(radius), float(eps)), )
 
 
-def node_mappings(extra: bool, foreground: bool = False, refine: bool = False):
+def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
-    node when `foreground`, plus the alpha refinement node when `refine`."""
+    node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`."""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
@@ -662,11 +789,15 @@ def node_mappings(extra: bool, foreground: bool = False, refine: bool = False):
     if refine:
         classes["SDMatteRefineAlpha"] = SDMatteRefineAlpha
         names["SDMatteRefineAlpha"] = "SDMatte Refine Alpha"
+    if clean:
+        classes["SDMatteCleanMask"] = SDMatteCleanMask
+        names["SDMatteCleanMask"] = "SDMatte Clean Mask"
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1), like the multi-GPU fan-out
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
 NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
-                                                                os.environ.get("SDMATTE_REFINE_NODE") == "1")
+                                                                os.environ.get("SDMATTE_REFINE_NODE") == "1",
+                                                                os.environ.get("SDMATTE_CLEAN_NODE") == "1")

@@ -176,6 +176,31 @@ int sdm_apply_matte_node(sdm_ctx* ctx, const float* image_bhwc, const float* tri
 #define SDM_TRIMAP_MAX_RADIUS 255
 int sdm_make_trimap(sdm_ctx* ctx, const float* mask_bhw, int B, int H, int W, float threshold, int erode_px, int dilate_px,
                     float* trimap_bhw, int ptr_kind, void* stream);
+/* Mask clean-up on the GPU, in front of sdm_make_trimap (beyond the reference): masks from a segmenter carry stray islands, pin-holes and second
+ * objects, and the trimap turns each of them into definite foreground or background.  mask fp32 [B,H,W] -> out fp32 [B,H,W].
+ *   F        = { p : mask[p] > threshold } (one fp32 compare, so NaN is background).  Images of a batch are independent; rows do not wrap.
+ *   stage A  label F with 8-connectivity; a component's area is its pixel count.  With keep_largest = 1 only the component of largest area survives
+ *            (on a tie the one that contains the smallest pixel index y*W + x); a survivor must also have area >= min_area (0 and 1 remove nothing).
+ *            The survivors form F1.
+ *   stage B  label the complement of F1 with 4-connectivity.  A hole is a component without a pixel of the image border (row 0, row H-1, column 0,
+ *            column W-1); holes with area <= max_hole_area join the foreground: F2.  max_hole_area = 0 fills nothing.
+ *   The stages are sequential: holes are holes of the mask after island removal, so a removed island inside a hole enlarges that hole before its area
+ *   is compared.
+ *   out[p]   = mask[p] where the class of p did not change (1.0 / 0.0 everywhere when binarize != 0), 0.0 for a removed pixel, 1.0 for a filled one:
+ *            out > threshold is exactly F2, and a soft mask stays soft where it was right.
+ *   stats_b4 (may be NULL) int32 [B][SDM_CLEAN_STATS], of the same pointer kind as the planes: per image {components of F, components removed,
+ *            holes filled, pixels whose class changed}.
+ * threshold finite in [0, 1) (so that the written 0.0 and 1.0 lie on the right side of it), min_area and max_hole_area in 0 .. SDM_FG_MAX_PIXELS,
+ * keep_largest and binarize 0 or 1, B, H, W >= 1 within SDM_FG_MAX_SIDE / SDM_FG_MAX_PIXELS (global pixel indices are the labels): SDM_ERR_INVALID
+ * otherwise, and then nothing is queued or written.  Compares and counts only: GPU, emulator and sdmatte_nodes.clean_mask agree bit for bit.
+ * Stream contract and pointer kinds as sdm_make_trimap; sdm_last_forward_ms covers the launches.  Needs no weights.  The number of kernel launches
+ * depends only on which stages are on (stage A: min_area > 1 or keep_largest, 6 launches; stage B: max_hole_area > 0, 4 launches; stage A off: 1
+ * threshold / copy launch, plus 3 for the component count when stats_b4 is given), never on B, H, W or the content (csrc/k_cclabel.h); no host
+ * readback.  The three label planes (12 bytes per pixel) are part of the activation arena, host pointers go through the I/O staging
+ * (sdm_resident_bytes counts both, sdm_release_memory frees them). */
+#define SDM_CLEAN_STATS 4
+int sdm_clean_mask(sdm_ctx* ctx, const float* mask_bhw, int B, int H, int W, float threshold, int min_area, int keep_largest, int max_hole_area,
+                   int binarize, float* out_bhw, int32_t* stats_b4, int ptr_kind, void* stream);
 /* sdm_apply_matte_node with the trimap made from `mask` [B,mask_h,mask_w] on the device, in the same call: bit-identical, in alpha,
  * matted and trimap, to sdm_make_trimap followed by sdm_apply_matte_node.  The size rule is that call's, with the mask in the trimap's place.
  * trimap_out (may be NULL) receives the trimap [B,mask_h,mask_w]. */
@@ -267,7 +292,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_estimate_foreground / sdm_refine_alpha_guided: their launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_estimate_foreground / sdm_refine_alpha_guided: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
