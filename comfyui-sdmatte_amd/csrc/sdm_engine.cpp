@@ -21,6 +21,7 @@
 #include "k_cclabel.h"
 #include "k_foreground.h"
 #include "k_guided.h"
+#include "k_roi.h"
 #include "../../include/sdmatte.h"
 
 #include <algorithm>
@@ -2183,6 +2184,43 @@ static void op_trimap(sdm_ctx* e, const float* mask, int B, int H, int W, float 
 }
 
 // ------------------------------------------------------------------------------------------------
+// the subject's box (k_roi.h): plane fp32 [B,H,W] -> raw extrema int32 [B,4] -> roi int32 [B,4] = {y0, x0, h, w}
+// ------------------------------------------------------------------------------------------------
+static int roi_check(sdm_ctx* e, const char* what, int B, int H, int W, float roi_threshold, int margin_px, int margin_pct, int square) {
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "%s: bad plane size %dx%dx%d", what, B, H, W);
+  // pixel indices inside an image are ints
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "%s: %dx%dx%d is too large (sides up to %d, %d pixels in all)", what, B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  // at least 0, so that what the reduction reads beyond the image (-1) is outside U
+  if (!std::isfinite(roi_threshold) || !(roi_threshold >= 0.0f) || !(roi_threshold < 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "%s: roi_threshold = %g must be a finite number in [0, 1)", what, (double)roi_threshold);
+  if (margin_px < 0 || margin_px > SDM_ROI_MAX_MARGIN_PX) SDM_FAIL(e, SDM_ERR_INVALID, "%s: margin_px = %d outside 0 .. %d", what, margin_px, SDM_ROI_MAX_MARGIN_PX);
+  if (margin_pct < 0 || margin_pct > 100) SDM_FAIL(e, SDM_ERR_INVALID, "%s: margin_pct = %d outside 0 .. 100", what, margin_pct);
+  if (square != 0 && square != 1) SDM_FAIL(e, SDM_ERR_INVALID, "%s: square = %d must be 0 or 1", what, square);
+  return 0;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// three launches, whatever the arguments
+static void op_roi_box(sdm_ctx* e, const float* plane, int B, int H, int W, float roi_threshold, int margin_px, int margin_pct, int square, int* raw, int* roi) {
+  prof_begin(e, "roi_init", 0, (double)B * 16);
+  count_kernel("roi_init");
+  SDM_LAUNCH(roi_init_kernel, dim3((unsigned)sdm_cdiv(B * 4, 256)), dim3(256), 0, e->stream, raw, B);
+  prof_end(e);
+  const dim3 grid((unsigned)(B * sdm_cdiv(H * W, SDM_ROI_PX)));
+  prof_begin(e, "roi_reduce", 0, (double)B * H * W * 4);
+  count_kernel("roi_reduce");
+  if (W % 4 == 0 && aligned16(plane)) SDM_LAUNCH((roi_reduce_kernel<true>), grid, dim3(256), 0, e->stream, plane, raw, B, H, W, roi_threshold);
+  else SDM_LAUNCH((roi_reduce_kernel<false>), grid, dim3(256), 0, e->stream, plane, raw, B, H, W, roi_threshold);
+  prof_end(e);
+  prof_begin(e, "roi_finalize", 0, (double)B * 32);
+  count_kernel("roi_finalize");
+  SDM_LAUNCH(roi_finalize_kernel, dim3((unsigned)sdm_cdiv(B, 64)), dim3(64), 0, e->stream, (const int*)raw, roi, B, H, W, margin_px, margin_pct, square);
+  prof_end(e);
+}
+
+// ------------------------------------------------------------------------------------------------
 // top-level forward helpers
 // ------------------------------------------------------------------------------------------------
 static int ensure_buf(sdm_ctx* e, void** p, size_t* cap, size_t need) {
@@ -2202,6 +2240,8 @@ struct NodeTail {
   int output_mode = 0, mask_refine = 0; double c = 0.8; float* matted = nullptr; int TH = 0, TW = 0;
   // sdm_apply_matte_mask: the `trimap` argument of forward_impl is a mask, and the trimap is made from it on the device (op_trimap)
   bool from_mask = false; float threshold = 0.5f; int erode_px = 0, dilate_px = 0; float* trimap_out = nullptr;
+  // sdm_apply_matte_roi: the model sees the box of the trimap (op_roi_box) instead of the frame; the box stays on the device
+  bool roi = false; float roi_threshold = 0.0f; int margin_px = 0, margin_pct = 0, square = 0; int32_t* roi_out = nullptr;
   int channels() const { return output_mode == 1 ? 4 : 3; }
 };
 
@@ -2209,7 +2249,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_estimate_foreground, sdm_refine_alpha_guided) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -2272,16 +2312,18 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
   const int TH = (tail && tail->TH > 0) ? tail->TH : H, TW = (tail && tail->TW > 0) ? tail->TW : W;
   const size_t in_tri = (size_t)B * TH * TW * 4;
   const size_t alpha_bytes = (size_t)B * H * W * 4;
-  const bool from_mask = tail && tail->from_mask;
+  const bool from_mask = tail && tail->from_mask, roi = tail && tail->roi;
   IoSpan in[] = {{(void*)image, (size_t)B * H * W * 3 * 4},      // mode 0: [B,3,SH,SW]; mode 1: [B,H,W,3]
                  {(void*)trimap, in_tri}};
   IoSpan outs[] = {{out, alpha_bytes},                           // host hand-over: alpha, then the composed image
                    {tail ? tail->matted : nullptr, tail ? alpha_bytes * tail->channels() : 0},
                    // ... then the trimap made from the mask, if the caller wants it
-                   {from_mask ? tail->trimap_out : nullptr, (from_mask && tail->trimap_out) ? in_tri : 0}};
+                   {from_mask ? tail->trimap_out : nullptr, (from_mask && tail->trimap_out) ? in_tri : 0},
+                   // ... then the box
+                   {roi ? tail->roi_out : nullptr, (roi && tail->roi_out) ? (size_t)B * 16 : 0}};
   return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
     const float* d_img = (const float*)in[0].p; const float* d_tri = (const float*)in[1].p;
-    float* d_out = (float*)outs[0].p; float* d_matted = (float*)outs[1].p; float* d_tri_out = (float*)outs[2].p;
+    float* d_out = (float*)outs[0].p; float* d_matted = (float*)outs[1].p; float* d_tri_out = (float*)outs[2].p; int* d_roi_out = (int*)outs[3].p;
     if (e->dry) TRY(prepare_variants(e, B, is_trans, cond, cond_dim, cond_kind));      // once per call: behind the input copies, ahead of the launches
     T gtri;      // sdm_apply_matte_mask: the trimap of this call, made from the mask in d_tri; it stands in for d_tri from here on
     const float* tri_in = d_tri;
@@ -2295,6 +2337,16 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
       tfree(e, dist);
       tri_in = (const float*)gtri.p;
     }
+    T box;       // sdm_apply_matte_roi: {y0, x0, h, w} per image, from the trimap of this call (TH x TW = H x W); read by the three resampling launches
+    if (roi) {
+      T raw = talloc(e, B, 1, 1, 4, 1);
+      box = talloc(e, B, 1, 1, 4, 1);
+      if (!e->dry) {
+        op_roi_box(e, tri_in, B, H, W, tail->roi_threshold, tail->margin_px, tail->margin_pct, tail->square, (int*)raw.p, (int*)box.p);
+        if (d_roi_out) SDM_CHECK_DEV(e, dev_memcpy_d2d(d_roi_out, box.p, (size_t)B * 16, e->stream));
+      }
+      tfree(e, raw);
+    }
     T x16 = talloc(e, 2 * B, SH, SW, 16, e->act_f32);
     T plane = talloc(e, B, SH, SW, 1, 1);
     if (!e->dry) {
@@ -2303,6 +2355,16 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
       void* tri16 = (unsigned char*)x16.p + (size_t)B * SH * SW * 16 * fmt_bytes(x16.f32);
       if (mode == 0) {
         SDM_LAUNCH(prep_nchw_kernel, dim3(nb), dim3(256), 0, e->stream, d_img, d_tri, img16, tri16, x16.f32, (float*)plane.p, B, SH, SW);
+      } else if (roi) {
+        // (an upper bound of the bytes: what is read depends on the box)
+        prof_begin(e, "roi_prep_image", 0, (double)B * H * W * 12 + (double)B * S * S * 16 * fmt_bytes(x16.f32));
+        count_kernel("roi_prep_image");
+        SDM_LAUNCH(roi_prep_image_kernel, dim3(nb), dim3(256), 0, e->stream, d_img, (const int*)box.p, img16, x16.f32, B, H, W, S);
+        prof_end(e);
+        prof_begin(e, "roi_prep_trimap", 0, (double)B * H * W * 4 + (double)B * S * S * (16 * fmt_bytes(x16.f32) + 4));
+        count_kernel("roi_prep_trimap");
+        SDM_LAUNCH(roi_prep_trimap_kernel, dim3(nb), dim3(256), 0, e->stream, tri_in, (const int*)box.p, tri16, x16.f32, (float*)plane.p, B, H, W, S);
+        prof_end(e);
       } else {
         SDM_LAUNCH(prep_image_kernel, dim3(nb), dim3(256), 0, e->stream, d_img, img16, x16.f32, B, H, W, S);
         SDM_LAUNCH(prep_trimap_kernel, dim3(nb), dim3(256), 0, e->stream, tri_in, tri16, x16.f32, (float*)plane.p, B, TH, TW, S);
@@ -2314,14 +2376,22 @@ static int forward_impl(sdm_ctx* e, int mode, const float* image, const float* t
       if (mode == 0) {
         SDM_CHECK_DEV(e, dev_memcpy_d2d(d_out, alpha.p, (size_t)B * SH * SW * 4, e->stream));
       } else {
-        SDM_LAUNCH(resize_planes_kernel, dim3((unsigned)(((long)B * H * W + 255) / 256)), dim3(256), 0, e->stream, (const float*)alpha.p, d_out, B,
-                   S, S, H, W, 1);
+        if (roi) {
+          prof_begin(e, "roi_paste", 0, (double)B * H * W * 4 + (double)B * S * S * 4);
+          count_kernel("roi_paste");
+          SDM_LAUNCH(roi_paste_kernel, dim3((unsigned)(((long)B * H * W + 255) / 256)), dim3(256), 0, e->stream, (const float*)alpha.p, (const int*)box.p, d_out,
+                     B, H, W, S);
+          prof_end(e);
+        } else {
+          SDM_LAUNCH(resize_planes_kernel, dim3((unsigned)(((long)B * H * W + 255) / 256)), dim3(256), 0, e->stream, (const float*)alpha.p, d_out, B,
+                     S, S, H, W, 1);
+        }
         if (tail)
           SDM_LAUNCH(refine_compose_kernel, dim3((unsigned)(((long)B * H * W + 255) / 256)), dim3(256), 0, e->stream, d_img, tri_in, d_out, d_matted,
                      (long)B * H * W, tail->output_mode, tail->mask_refine, (float)tail->c, (float)(1.0 - tail->c));
       }
     }
-    tfree(e, alpha); tfree(e, plane); tfree(e, x16); tfree(e, gtri);
+    tfree(e, alpha); tfree(e, plane); tfree(e, x16); tfree(e, box); tfree(e, gtri);
     return 0;
   });
 }
@@ -2837,6 +2907,41 @@ int sdm_apply_matte_mask(sdm_ctx* e, const float* image, const float* mask, int 
   return forward_impl(e, 1, image, mask, B, H, W, S, it.data(), nullptr, 4, 0, true, alpha, ptr_kind, stream, &tail);
 }
 
+/* sdm_apply_matte_node / sdm_apply_matte_mask on the box of the trimap (k_roi.h): the box is an arena tensor of both passes and the model's input is
+ * S x S whatever the box is, so the sizing pass never sees a data-dependent size. */
+int sdm_apply_matte_roi(sdm_ctx* e, const float* image, const float* aux, int B, int H, int W, int S, int is_transparent, int aux_is_mask, float threshold,
+                        int erode_px, int dilate_px, float roi_threshold, int margin_px, int margin_pct, int square, int output_mode, int mask_refine,
+                        double trimap_constraint, float* alpha, float* matted, float* trimap_out, int32_t* roi_out, int ptr_kind, void* stream) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !aux || !alpha || !matted) return SDM_ERR_INVALID;
+  if (output_mode < 0 || output_mode > 2) SDM_FAIL(e, SDM_ERR_INVALID, "unknown output mode %d", output_mode);
+  if (aux_is_mask != 0 && aux_is_mask != 1) SDM_FAIL(e, SDM_ERR_INVALID, "apply matte roi: aux_is_mask = %d must be 0 or 1", aux_is_mask);
+  if (!aux_is_mask && trimap_out) SDM_FAIL(e, SDM_ERR_INVALID, "apply matte roi: trimap_out is written only with aux_is_mask = 1");
+  TRY(roi_check(e, "apply matte roi", B, H, W, roi_threshold, margin_px, margin_pct, square));
+  if (aux_is_mask) TRY(trimap_check(e, B, H, W, erode_px, dilate_px));
+  std::vector<int32_t> it((size_t)B, is_transparent ? 1 : 0);
+  NodeTail tail; tail.output_mode = output_mode; tail.mask_refine = mask_refine ? 1 : 0; tail.c = trimap_constraint; tail.matted = matted;
+  tail.TH = H; tail.TW = W;
+  if (aux_is_mask) { tail.from_mask = true; tail.threshold = threshold; tail.erode_px = erode_px; tail.dilate_px = dilate_px; tail.trimap_out = trimap_out; }
+  tail.roi = true; tail.roi_threshold = roi_threshold; tail.margin_px = margin_px; tail.margin_pct = margin_pct; tail.square = square; tail.roi_out = roi_out;
+  return forward_impl(e, 1, image, aux, B, H, W, S, it.data(), nullptr, 4, 0, true, alpha, ptr_kind, stream, &tail);
+}
+
+/* The box on its own (k_roi.h).  The raw extrema live in the activation arena.  Three launches, whatever the arguments. */
+int sdm_subject_roi(sdm_ctx* e, const float* plane, int B, int H, int W, float roi_threshold, int margin_px, int margin_pct, int square, int32_t* roi,
+                    int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !plane || !roi) return SDM_ERR_INVALID;
+  TRY(roi_check(e, "subject roi", B, H, W, roi_threshold, margin_px, margin_pct, square));
+  IoSpan in[] = {{(void*)plane, (size_t)B * H * W * 4}}, out[] = {{roi, (size_t)B * 16}};
+  return product_call(e, ptr_kind, stream_arg, in, out, [&]() -> int {
+    T raw = talloc(e, B, 1, 1, 4, 1);
+    if (!e->dry) op_roi_box(e, (const float*)in[0].p, B, H, W, roi_threshold, margin_px, margin_pct, square, (int*)raw.p, (int*)out[0].p);
+    tfree(e, raw);
+    return 0;
+  });
+}
+
 /* Trimap from a mask on its own (k_trimap.h).  The distance plane lives in the activation arena. */
 int sdm_make_trimap(sdm_ctx* e, const float* mask, int B, int H, int W, float threshold, int erode_px, int dilate_px, float* trimap, int ptr_kind,
                     void* stream_arg) {
@@ -2922,8 +3027,6 @@ int sdm_estimate_foreground(sdm_ctx* e, const float* image, const float* alpha, 
 // ------------------------------------------------------------------------------------------------
 // alpha refinement at full resolution: the subsampled colour guided filter (k_guided.h)
 // ------------------------------------------------------------------------------------------------
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 /* The three coarse planes live in the activation arena.  Four launches, whatever the arguments. */
 int sdm_refine_alpha_guided(sdm_ctx* e, const float* image, const float* alpha, int B, int H, int W, int subsample, int radius, float eps, float* out,
                             int ptr_kind, void* stream_arg) {

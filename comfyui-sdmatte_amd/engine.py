@@ -82,7 +82,7 @@ EXPORTS = [
     "sdm_default_config", "sdm_create", "sdm_destroy", "sdm_last_error", "sdm_load_tensor", "sdm_finalize_weights",
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
-    "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_estimate_foreground", "sdm_refine_alpha_guided",
+    "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_estimate_foreground", "sdm_refine_alpha_guided",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias",
@@ -119,6 +119,8 @@ class Bindings:
             "sdm_make_trimap": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, vp, i32, vp]),
             "sdm_clean_mask": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, vp, vp, i32, vp]),
             "sdm_apply_matte_mask": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, C.c_double, vp, vp, vp, i32, vp]),
+            "sdm_subject_roi": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, i32, vp, i32, vp]),
+            "sdm_apply_matte_roi": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, f32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, i32, vp]),
             "sdm_estimate_foreground": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
             "sdm_refine_alpha_guided": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
@@ -482,6 +484,79 @@ class Engine:
         if sync:
             self.synchronize()
         return alpha, matted, trimap
+
+    ROI_MAX_MARGIN_PX = 4096     # SDM_ROI_MAX_MARGIN_PX (include/sdmatte.h)
+
+    @classmethod
+    def _check_roi_params(cls, what, roi_threshold, margin_px, margin_pct):
+        roi_threshold = float(roi_threshold)
+        if not (0.0 <= roi_threshold < 1.0) or float(np.float32(roi_threshold)) >= 1.0:
+            raise ValueError(f"{what}: roi_threshold must be in [0, 1), got {roi_threshold!r}")
+        for name, v, hi in (("margin_px", margin_px, cls.ROI_MAX_MARGIN_PX), ("margin_pct", margin_pct, 100)):
+            if int(v) != v or not 0 <= int(v) <= hi:
+                raise ValueError(f"{what}: {name} must be an integer in 0 .. {hi}, got {v!r}")
+        return roi_threshold, int(margin_px), int(margin_pct)
+
+    def subject_roi(self, plane, roi_threshold=0.0, margin_px=16, margin_pct=10, square=True, out=None, sync=True):
+        """The subject's box on the GPU (sdm_subject_roi): plane [B,H,W] (a trimap, a mask, an alpha) -> int32 [B,4] = per image {y0, x0, h, w}, the
+        bounding box of `plane > roi_threshold` with a margin of margin_px + margin_pct % of its extent per side, clipped to the frame and, with `square`,
+        grown to a square where the frame allows; the whole frame for an image without such a pixel.  Needs no loaded weights.
+        `sdmatte_nodes.subject_roi` is the same function on CPU tensors, exactly."""
+        if plane.dim() != 3 or plane.numel() == 0:
+            raise ValueError(f"subject_roi: plane must be a non-empty [B,H,W], got {tuple(plane.shape)}")
+        roi_threshold, margin_px, margin_pct = self._check_roi_params("subject_roi", roi_threshold, margin_px, margin_pct)
+        B, H, W = (int(v) for v in plane.shape)
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"subject_roi: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        plane = plane.float().contiguous()
+        if out is None:
+            out = torch.empty(B, 4, dtype=torch.int32, device=plane.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (B, 4):
+            raise ValueError("subject_roi: out must be a contiguous int32 tensor [B,4]")
+        stream = self._check_io("subject_roi", plane, out)
+        self._check(self.lib.sdm_subject_roi(self.h, _ptr(plane), B, H, W, roi_threshold, margin_px, margin_pct, 1 if square else 0, _ptr(out),
+                                             self._kind(plane), stream), "sdm_subject_roi")
+        if sync:
+            self.synchronize()
+        return out
+
+    def apply_matte_roi(self, image_bhwc, aux_bhw, S, is_transparent, output_mode, mask_refine, trimap_constraint, aux_is_mask=False, threshold=0.5,
+                        erode_px=10, dilate_px=10, roi_threshold=0.0, margin_px=16, margin_pct=10, square=True, sync=True):
+        """`apply_matte_node` (or, with aux_is_mask, `apply_matte_mask`) on the subject instead of the frame, in one C-ABI call (sdm_apply_matte_roi): the
+        model sees the box of the trimap (`subject_roi` with the four box arguments) at S x S, its alpha goes back into the box and is 0 outside,
+        mask_refine and the composition run on the whole frame.  `aux_bhw` has the image's size.  Returns (alpha [B,H,W], matted [B,H,W,3|4],
+        trimap [B,H,W] with aux_is_mask or None, roi int32 [B,4] = {y0, x0, h, w}); the box is never read by the host on the way."""
+        if output_mode not in self.OUTPUT_MODES:
+            raise ValueError(f"unknown output_mode {output_mode!r}")
+        if image_bhwc.dim() != 4 or image_bhwc.shape[-1] != 3 or image_bhwc.numel() == 0:
+            raise ValueError(f"apply_matte_roi: image must be a non-empty [B,H,W,3], got {tuple(image_bhwc.shape)}")
+        B, H, W, _ = (int(v) for v in image_bhwc.shape)
+        roi_threshold, margin_px, margin_pct = self._check_roi_params("apply_matte_roi", roi_threshold, margin_px, margin_pct)
+        if aux_is_mask:
+            erode_px, dilate_px = self._check_radii("apply_matte_roi", erode_px, dilate_px)
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"apply_matte_roi: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        if aux_bhw.dim() != 3 or aux_bhw.shape[0] != B:
+            raise ValueError(f"apply_matte_roi: aux must be [B,H,W] with B = {B}, got {tuple(aux_bhw.shape)}")
+        if tuple(aux_bhw.shape) != (B, H, W):
+            # the box is a box of the image: there is no trimap of another size here
+            raise IndexError(f"apply_matte_roi: aux {tuple(aux_bhw.shape[1:])} must match the image {(H, W)}")
+        image_bhwc = image_bhwc.float().contiguous()
+        aux_bhw = aux_bhw.float().contiguous()
+        mode = self.OUTPUT_MODES[output_mode]
+        dev = image_bhwc.device
+        alpha = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+        matted = torch.empty(B, H, W, 4 if mode == 1 else 3, dtype=torch.float32, device=dev)
+        trimap = torch.empty(B, H, W, dtype=torch.float32, device=dev) if aux_is_mask else None
+        roi = torch.empty(B, 4, dtype=torch.int32, device=dev)
+        stream = self._check_io("apply_matte_roi", image_bhwc, aux_bhw, alpha, matted, trimap, roi)
+        self._check(self.lib.sdm_apply_matte_roi(self.h, _ptr(image_bhwc), _ptr(aux_bhw), B, H, W, int(S), 1 if is_transparent else 0, 1 if aux_is_mask else 0,
+                                                 float(threshold), int(erode_px), int(dilate_px), roi_threshold, margin_px, margin_pct, 1 if square else 0,
+                                                 mode, 1 if mask_refine else 0, float(trimap_constraint), _ptr(alpha), _ptr(matted), _ptr(trimap), _ptr(roi),
+                                                 self._kind(image_bhwc), stream), "sdm_apply_matte_roi")
+        if sync:
+            self.synchronize()
+        return alpha, matted, trimap, roi
 
     # SDM_FG_* (include/sdmatte.h)
     FG_DEFAULTS = {"regularization": 1e-5, "gradient_weight": 1.0, "n_small_iters": 10, "n_big_iters": 2}

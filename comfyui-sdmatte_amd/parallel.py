@@ -322,5 +322,35 @@ class MultiGpuEngine:
         self._fan(B, call)
         return alpha, matted, trimap
 
+    def subject_roi(self, plane_bhw, roi_threshold=0.0, margin_px=16, margin_pct=10, square=True):
+        """The subject's box (no model involved): on the first engine; plane [B,H,W] (host or any device) -> int32 [B,4] on the HOST."""
+        return self.engines[0].subject_roi(self._to_host(plane_bhw), roi_threshold, margin_px, margin_pct, square)
+
+    def apply_matte_roi(self, image_bhwc, aux_bhw, S, is_transparent, output_mode, mask_refine, trimap_constraint, aux_is_mask=False, threshold=0.5,
+                        erode_px=10, dilate_px=10, roi_threshold=0.0, margin_px=16, margin_pct=10, square=True):
+        """`Engine.apply_matte_roi` for a batch split over the devices (every image has its own box, found on the GPU that mattes it); returns
+        (alpha [B,H,W], matted [B,H,W,3|4], trimap [B,H,W] or None, roi int32 [B,4]) on the HOST."""
+        from .engine import Engine
+        B, H, W, _ = image_bhwc.shape
+        ch = 4 if Engine.OUTPUT_MODES[output_mode] == 1 else 3
+        alpha = self._host(B, H, W)
+        matted = self._host(B, H, W, ch)
+        img = self._to_host(image_bhwc)
+        aux = self._to_host(aux_bhw)
+        trimap = self._host(*aux.shape) if aux_is_mask else None
+        roi = torch.empty(B, 4, dtype=torch.int32, pin_memory=self._on_device)
+
+        def call(eng, dev, lo, hi):
+            a, m, t, r = eng.apply_matte_roi(img[lo:hi], aux[lo:hi], S, is_transparent, output_mode, mask_refine, trimap_constraint, aux_is_mask, threshold,
+                                             erode_px, dilate_px, roi_threshold, margin_px, margin_pct, square)
+            alpha[lo:hi].copy_(a)
+            matted[lo:hi].copy_(m)
+            roi[lo:hi].copy_(r)
+            if t is not None:
+                trimap[lo:hi].copy_(t)
+
+        self._fan(B, call)
+        return alpha, matted, trimap, roi
+
     def last_forward_ms(self):
         return max(e.last_forward_ms() for e in self.engines)

@@ -19,6 +19,9 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
   * and one registered only with SDMATTE_REFINE_NODE=1: `SDMatteRefineAlpha` refines the alpha at the image's own resolution with the subsampled
     colour guided filter on the GPU (the model never sees more than `inference_size` pixels per side); `guided_refine_alpha` below is its torch
     restatement;
+  * and one registered only with SDMATTE_ROI_NODE=1: `SDMatteApplyROI` is `SDMatteApplyMask` on the subject instead of the frame: the model is shown
+    the box of the trimap at `inference_size` and its alpha is put back into the frame, all inside one engine call; `subject_roi` and `paste_roi`
+    below are the exact CPU restatements of the box and of the way back;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -432,6 +435,60 @@ def clean_mask(mask, threshold=0.5, min_area=64, keep_largest=False, max_hole_ar
     return (out, torch.from_numpy(stats)) if return_stats else out
 
 
+def subject_roi(plane, roi_threshold=0.0, margin_px=16, margin_pct=10, square=True):
+    """`Engine.subject_roi` on CPU tensors, exactly (integers only; the definition is in include/sdmatte.h, sdm_subject_roi): plane [B,H,W] -> int32 [B,4]
+    = per image {y0, x0, h, w}, the bounding box of `plane > roi_threshold` with its margin, clipped, optionally squared; the whole frame if empty."""
+    import numpy as np
+    from .engine import Engine
+    if plane.dim() != 3 or plane.numel() == 0:
+        raise ValueError(f"subject_roi: plane must be a non-empty [B,H,W], got {tuple(plane.shape)}")
+    roi_threshold, margin_px, margin_pct = Engine._check_roi_params("subject_roi", roi_threshold, margin_px, margin_pct)
+    p = plane.detach().cpu().float().contiguous().numpy()
+    B, H, W = p.shape
+    out = np.zeros((B, 4), np.int32)
+
+    def axis(lo, hi, n):
+        m = margin_px + ((hi - lo + 1) * margin_pct) // 100
+        a = max(0, lo - m)
+        return a, min(n, hi + 1 + m) - a
+
+    def grow(a, ext, L, n):
+        a -= (L - ext) // 2
+        a = max(a, 0)
+        if a + L > n:
+            a = max(0, n - L)
+        return a, min(L, n)
+
+    for b in range(B):
+        with np.errstate(invalid="ignore"):
+            u = p[b] > np.float32(roi_threshold)
+        rows, cols = np.flatnonzero(u.any(axis=1)), np.flatnonzero(u.any(axis=0))
+        if rows.size == 0:
+            out[b] = (0, 0, H, W)
+            continue
+        (y0, h), (x0, w) = axis(int(rows[0]), int(rows[-1]), H), axis(int(cols[0]), int(cols[-1]), W)
+        if square:
+            L = max(h, w)
+            (y0, h), (x0, w) = grow(y0, h, L, H), grow(x0, w, L, W)
+        out[b] = (y0, x0, h, w)
+    return torch.from_numpy(out)
+
+
+def paste_roi(crop_bhw, roi, H, W):
+    """The way back of `Engine.apply_matte_roi` on CPU tensors: crop_bhw[b] ([h,w] of roi[b]; a tensor [B,h,w] or a list of planes) -> fp32 [B,H,W] that holds
+    it at (y0, x0) and 0.0 everywhere else."""
+    roi = torch.as_tensor(roi).reshape(-1, 4)
+    if len(crop_bhw) != roi.shape[0]:
+        raise ValueError(f"paste_roi: {len(crop_bhw)} crops for {roi.shape[0]} boxes")
+    out = torch.zeros(roi.shape[0], int(H), int(W), dtype=torch.float32)
+    for b, crop in enumerate(crop_bhw):
+        y0, x0, h, w = (int(v) for v in roi[b])
+        if tuple(crop.shape) != (h, w) or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+            raise ValueError(f"paste_roi: crop {tuple(crop.shape)} does not fit the box {(y0, x0, h, w)} of a {(int(H), int(W))} frame")
+        out[b, y0:y0 + h, x0:x0 + w] = crop.detach().cpu().float()
+    return out
+
+
 def _nearest_index(n_dst, n_src):
     """src = min(n_src - 1, (i * n_src) // n_dst) for i = 0 .. n_dst - 1 (integers only)."""
     return torch.clamp((torch.arange(n_dst, dtype=torch.int64) * n_src) // n_dst, max=n_src - 1)
@@ -706,6 +763,56 @@ class SDMatteApplyMask:
         return (out, matted, trimap)
 
 
+_ROI_INPUTS = {
+    "roi_threshold": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 0.99, "step": 0.01, "tooltip": "trimap values above this belong to the subject (0 = everything but definite background)"}),
+    "margin_px": ("INT", {"default": 16, "min": 0, "max": 4096, "step": 1, "tooltip": "context around the subject's box, in pixels per side"}),
+    "margin_pct": ("INT", {"default": 10, "min": 0, "max": 100, "step": 1, "tooltip": "... plus this many percent of the box's extent per side"}),
+    "square": ("BOOLEAN", {"default": True, "tooltip": "grow the box to a square where the frame allows (the model's input is square)"}),
+}
+
+
+class SDMatteApplyROI:
+    """`Apply SDMatte (Mask)` on the subject instead of the frame: the model sees the box of the trimap at `inference_size`, the alpha outside the box
+    is 0 (exact: the trimap is definite background there).  Returns the box as well: one (x, y, width, height) per image."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        base = SDMatteApplyMask.INPUT_TYPES()
+        required = {}
+        for key, spec in base["required"].items():
+            required[key] = spec
+            if key == "dilate_px":
+                required.update(_ROI_INPUTS)
+        return {"required": required, "optional": base["optional"]}
+
+    RETURN_TYPES = ("MASK", "IMAGE", "MASK", "BBOX")
+    RETURN_NAMES = ("alpha_mask", "matted_image", "trimap", "roi")
+    FUNCTION = "apply_matte"
+    CATEGORY = "Matting/SDMatte"
+
+    def apply_matte(self, ckpt_name, image, mask, threshold, erode_px, dilate_px, roi_threshold, margin_px, margin_pct, square, inference_size,
+                    is_transparent, output_mode, mask_refine, trimap_constraint, force_cpu=False):
+        from .engine import Engine
+        if force_cpu:
+            raise RuntimeError("[SDMatte] force_cpu=True is not available: this node runs hand-written gfx950 kernels only "
+                               "(no CPU path).  Use the reference plugin for CPU inference.")
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        if mask.dim() != 3 or tuple(mask.shape) != tuple(image.shape[:3]):
+            raise ValueError(f"[SDMatte] mask must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(mask.shape)}")
+        Engine._check_roi_params("[SDMatte] apply_matte", roi_threshold, margin_px, margin_pct)
+        model = get_model(ckpt_name, _torch_device())
+        fan = _fan_out(model, image.shape[0])
+        runner = fan if fan is not None else model.engine
+        out, matted, trimap, roi = runner.apply_matte_roi(image, mask, int(inference_size), bool(is_transparent), output_mode, bool(mask_refine),
+                                                          float(trimap_constraint), True, float(threshold), int(erode_px), int(dilate_px),
+                                                          float(roi_threshold), int(margin_px), int(margin_pct), bool(square))
+        out, matted, trimap = out.detach().cpu(), matted.detach().cpu(), trimap.detach().cpu()
+        boxes = [(int(x0), int(y0), int(w), int(h)) for y0, x0, h, w in roi.detach().cpu().tolist()]
+        _trim_engine_memory(model)
+        return (out, matted, trimap, boxes)
+
+
 _FOREGROUND_INPUTS = {
     "regularization": ("FLOAT", {"default": 1e-5, "min": 1e-9, "max": 1.0, "step": 1e-6, "tooltip": "smoothness weight between all neighbours (must be above 0)"}),
     "gradient_weight": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 100.0, "step": 0.01, "tooltip": "extra smoothness weight across alpha edges"}),
@@ -775,9 +882,9 @@ class SDMatteRefineAlpha:
         return (eng.refine_alpha_guided(image.detach().cpu(), alpha.detach().cpu(), int(subsample), int(radius), float(eps)), )
 
 
-def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False):
+def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
-    node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`."""
+    node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`, plus the subject-box node when `roi`."""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
@@ -792,12 +899,16 @@ def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, c
     if clean:
         classes["SDMatteCleanMask"] = SDMatteCleanMask
         names["SDMatteCleanMask"] = "SDMatte Clean Mask"
+    if roi:
+        classes["SDMatteApplyROI"] = SDMatteApplyROI
+        names["SDMatteApplyROI"] = "Apply SDMatte (Subject Box)"
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1), like the multi-GPU fan-out
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
 NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
                                                                 os.environ.get("SDMATTE_REFINE_NODE") == "1",
-                                                                os.environ.get("SDMATTE_CLEAN_NODE") == "1")
+                                                                os.environ.get("SDMATTE_CLEAN_NODE") == "1",
+                                                                os.environ.get("SDMATTE_ROI_NODE") == "1")

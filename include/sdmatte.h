@@ -208,6 +208,41 @@ int sdm_apply_matte_mask(sdm_ctx* ctx, const float* image_bhwc, const float* mas
                          int is_transparent, float threshold, int erode_px, int dilate_px, int output_mode, int mask_refine,
                          double trimap_constraint, float* alpha_bhw, float* matted_bhwc, float* trimap_out, int ptr_kind, void* stream);
 
+/* The subject's box, on the GPU (beyond the reference, which shows the model the whole frame at `inference_size`: a subject that fills a quarter of a 4K
+ * photo reaches the model at 256 pixels).  plane fp32 [B,H,W] -> roi_b4 int32 [B][4] = {y0, x0, h, w}, of the same pointer kind as the plane.
+ *   U        = { p : plane[p] > roi_threshold } (one fp32 compare, so NaN is outside U); [ymin, ymax] x [xmin, xmax] is its bounding box, per image.
+ *   margin   bh = ymax - ymin + 1, my = margin_px + (bh * margin_pct) / 100 (integer division); y0 = max(0, ymin - my), y1 = min(H, ymax + 1 + my),
+ *            h = y1 - y0; x0 and w likewise from bw and W.
+ *   square   (square != 0) L = max(h, w); per axis, shown for y: y0 = y0 - (L - h) / 2, then y0 = 0 if y0 < 0, then y0 = max(0, H - L) if y0 + L > H,
+ *            and h = min(L, H): the shorter axis grows around its middle, is shifted back into the frame, and ends at the frame where that is shorter.
+ *   An empty U gives the whole frame {0, 0, H, W}, square or not.
+ * Integer arithmetic only: GPU, emulator and sdmatte_nodes.subject_roi agree exactly.  roi_threshold finite in [0, 1), margin_px in
+ * 0 .. SDM_ROI_MAX_MARGIN_PX, margin_pct in 0 .. 100, square 0 or 1, B, H, W >= 1 within SDM_FG_MAX_SIDE / SDM_FG_MAX_PIXELS: SDM_ERR_INVALID
+ * otherwise, and then nothing is queued or written.  Stream contract and pointer kinds as sdm_make_trimap; sdm_last_forward_ms covers the launches.
+ * Needs no weights.  Three kernel launches (initialise, reduce, finalise; csrc/k_roi.h), whatever B, H, W and the content: one read of the plane, no host
+ * readback.  The raw extrema are part of the activation arena, host pointers go through the I/O staging (sdm_resident_bytes counts both,
+ * sdm_release_memory frees them). */
+#define SDM_ROI_MAX_MARGIN_PX 4096
+int sdm_subject_roi(sdm_ctx* ctx, const float* plane_bhw, int B, int H, int W, float roi_threshold, int margin_px, int margin_pct, int square,
+                    int32_t* roi_b4, int ptr_kind, void* stream);
+/* sdm_apply_matte_node on the subject instead of the frame: the box of the trimap (sdm_subject_roi with the four box arguments) is resized to SxS in the
+ * frame's place, and the model's alpha is resized back into the box; outside the box the alpha is 0.0, which is exact, not an approximation: every
+ * pixel there has trimap <= roi_threshold.  mask_refine and the output composition then run over the whole frame as in sdm_apply_matte_node.
+ * Bit-identical to: box on the host, sdm_apply_matte_node (alpha_only, no refine) on the cropped image and trimap, the alpha pasted into zeros,
+ * and the node's tail on the frame.  The box never leaves the device: no host readback, a fixed number of launches, and the model's input is SxS
+ * whatever the box is.  One box per image; the model still sees one image with global attention, and its box conditioning stays [0, 0, 1, 1].
+ *   aux      [B,H,W], the image's size (there is no size of its own here): the trimap (aux_is_mask = 0), or a mask (aux_is_mask = 1) that becomes the
+ *            trimap on the whole frame first, exactly as in sdm_apply_matte_mask (threshold, erode_px, dilate_px: read with aux_is_mask = 1 only).
+ *   trimap_out (may be NULL) receives that trimap; passing it with aux_is_mask = 0 is SDM_ERR_INVALID.
+ *   roi_out  (may be NULL) int32 [B][4] = {y0, x0, h, w}, of the same pointer kind as the other arguments.
+ * An empty U makes the call equal to sdm_apply_matte_node / sdm_apply_matte_mask.  Argument limits as sdm_subject_roi and sdm_apply_matte_mask.  The
+ * box and its scratch are part of the activation arena.  Six launches beyond the model's, each once per call: roi_init, roi_reduce, roi_finalize,
+ * roi_prep_image, roi_prep_trimap, roi_paste in sdm_kernel_counts and the per-launch profile. */
+int sdm_apply_matte_roi(sdm_ctx* ctx, const float* image_bhwc, const float* aux_bhw, int B, int H, int W, int S, int is_transparent, int aux_is_mask,
+                        float threshold, int erode_px, int dilate_px, float roi_threshold, int margin_px, int margin_pct, int square,
+                        int output_mode, int mask_refine, double trimap_constraint, float* alpha_bhw, float* matted_bhwc, float* trimap_out,
+                        int32_t* roi_out, int ptr_kind, void* stream);
+
 /* Foreground / background colours from an image and its alpha, on the GPU (beyond the reference: its matted_rgba keeps the composite
  * a*F + (1-a)*B in every semi-transparent pixel, and with it a halo of the old background).  A multi-level estimator in the style of Germer et al.,
  * "Fast Multi-Level Foreground Estimation"; it uses the image and the alpha only.
@@ -292,7 +327,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_estimate_foreground / sdm_refine_alpha_guided: their launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
