@@ -22,6 +22,7 @@
 #include "k_foreground.h"
 #include "k_guided.h"
 #include "k_roi.h"
+#include "k_canvas.h"
 #include "../../include/sdmatte.h"
 
 #include <algorithm>
@@ -2249,7 +2250,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -3161,6 +3162,114 @@ int sdm_clean_mask(sdm_ctx* e, const float* mask, int B, int H, int W, float thr
       }
     }
     if (label_a || stage_b) { tfree(e, sel); tfree(e, area); tfree(e, root); tfree(e, label); }
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// the cut-out on a canvas (k_canvas.h)
+// ------------------------------------------------------------------------------------------------
+/* The raw extrema, the box and the placements live in the activation arena, and with a shadow the layer (16 bytes per canvas pixel) and one blur plane (4).
+ * Five launches without a shadow, seven with one, whatever else the arguments are. */
+int sdm_compose_canvas(sdm_ctx* e, const float* fg, const float* alpha, int B, int H, int W, float roi_threshold, int canvas_h, int canvas_w, int fill_pct,
+                       int valign, int bg_mode, const float* bg_rgb3, const float* bg_image, int bg_batch, float shadow_opacity, float shadow_sigma,
+                       int shadow_dy, int shadow_dx, float* out, int out_channels, int32_t* place_out, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !fg || !alpha || !out) return SDM_ERR_INVALID;
+  TRY(roi_check(e, "compose canvas", B, H, W, roi_threshold, 0, 0, 0));
+  if (canvas_h < 1 || canvas_w < 1 || canvas_h > SDM_FG_MAX_SIDE || canvas_w > SDM_FG_MAX_SIDE || (double)B * canvas_h * canvas_w > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: canvas %dx%dx%d outside sides 1 .. %d, %d pixels in all", B, canvas_h, canvas_w, SDM_FG_MAX_SIDE,
+             SDM_FG_MAX_PIXELS);
+  if (fill_pct < 1 || fill_pct > 100) SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: fill_pct = %d outside 1 .. 100", fill_pct);
+  if (valign < 0 || valign > 2) SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: valign = %d outside 0 .. 2", valign);
+  if (bg_mode < 0 || bg_mode > 2) SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: bg_mode = %d outside 0 .. 2", bg_mode);
+  if (out_channels != 3 && out_channels != 4) SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: out_channels = %d, must be 3 or 4", out_channels);
+  if (bg_mode == 0 && out_channels != 4) SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: out_channels = 3 needs a background (bg_mode 1 or 2)");
+  if (bg_mode == 1 && !bg_rgb3) SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: bg_mode 1 needs bg_rgb3");
+  if (bg_mode == 2 && (!bg_image || (bg_batch != 1 && bg_batch != B)))
+    SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: bg_mode 2 needs bg_image with bg_batch = 1 or %d (got %d)", B, bg_batch);
+  if (!std::isfinite(shadow_opacity) || !(shadow_opacity >= 0.0f) || !(shadow_opacity <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: shadow_opacity = %g must be a finite number in [0, 1]", (double)shadow_opacity);
+  const bool shadow = shadow_opacity > 0.0f;
+  if (shadow && (!std::isfinite(shadow_sigma) || !(shadow_sigma > 0.0f) || !(shadow_sigma <= (float)SDM_CANVAS_MAX_SHADOW_SIGMA)))
+    SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: shadow_sigma = %g must be a finite number in (0, %d]", (double)shadow_sigma, SDM_CANVAS_MAX_SHADOW_SIGMA);
+  if (shadow_dy < -SDM_CANVAS_MAX_SHADOW_OFFSET || shadow_dy > SDM_CANVAS_MAX_SHADOW_OFFSET || shadow_dx < -SDM_CANVAS_MAX_SHADOW_OFFSET ||
+      shadow_dx > SDM_CANVAS_MAX_SHADOW_OFFSET)
+    SDM_FAIL(e, SDM_ERR_INVALID, "compose canvas: shadow offset (%d, %d) outside -%d .. %d", shadow_dy, shadow_dx, SDM_CANVAS_MAX_SHADOW_OFFSET,
+             SDM_CANVAS_MAX_SHADOW_OFFSET);
+  static_assert(SDM_CANVAS_R == SDM_CANVAS_MAX_SHADOW_RADIUS && 3 * SDM_CANVAS_MAX_SHADOW_SIGMA <= SDM_CANVAS_MAX_SHADOW_RADIUS, "shadow limits");
+  CanvasBlur blur;
+  memset(&blur, 0, sizeof(blur));
+  if (shadow) {      // w_i = exp(-i^2 / (2 sigma^2)) / sum, in double, rounded to fp32
+    const double s = (double)shadow_sigma;
+    blur.r = std::min(SDM_CANVAS_R, std::max(1, (int)std::ceil(3.0 * s)));
+    double g[2 * SDM_CANVAS_R + 1], sum = 0.0;
+    for (int k = 0; k <= 2 * blur.r; ++k) { const double i = (double)(k - blur.r); g[k] = std::exp(-(i * i) / (2.0 * s * s)); sum += g[k]; }
+    for (int k = 0; k <= 2 * blur.r; ++k) blur.w[k] = (float)(g[k] / sum);
+  }
+  CanvasBg bg;
+  bg.mode = bg_mode; bg.batch = bg_batch; bg.image = nullptr;
+  for (int c = 0; c < 3; ++c) bg.rgb[c] = bg_mode == 1 ? bg_rgb3[c] : 0.0f;
+  const size_t px = (size_t)B * H * W, cpx = (size_t)B * canvas_h * canvas_w;
+  // (an absent background image is an empty span behind a valid pointer: the staging copies 0 bytes of it)
+  IoSpan in[] = {{(void*)fg, px * 12}, {(void*)alpha, px * 4}, {(void*)(bg_mode == 2 ? bg_image : fg), bg_mode == 2 ? (size_t)bg_batch * canvas_h * canvas_w * 12 : 0}};
+  IoSpan outs[] = {{out, cpx * 4 * out_channels}, {place_out, place_out ? (size_t)B * 32 : 0}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_fg = (const float*)in[0].p; const float* d_alpha = (const float*)in[1].p;
+    float* d_out = (float*)outs[0].p; int* d_place_out = (int*)outs[1].p;
+    CanvasBg dbg = bg;
+    if (bg_mode == 2) dbg.image = (const float*)in[2].p;
+    T raw = talloc(e, B, 1, 1, 4, 1), box = talloc(e, B, 1, 1, 4, 1), place = talloc(e, B, 1, 1, 8, 1);
+    T layer, tplane;
+    if (shadow) { layer = talloc(e, B, canvas_h, canvas_w, 4, 1); tplane = talloc(e, B, canvas_h, canvas_w, 1, 1); }
+    if (!e->dry) {
+      op_roi_box(e, d_alpha, B, H, W, roi_threshold, 0, 0, 0, (int*)raw.p, (int*)box.p);
+      prof_begin(e, "canvas_fit", 0, (double)B * 48);
+      count_kernel("canvas_fit");
+      SDM_LAUNCH(canvas_fit_kernel, dim3((unsigned)sdm_cdiv(B, 64)), dim3(64), 0, e->stream, (const int*)box.p, (int*)place.p, d_place_out, B, canvas_h, canvas_w,
+                 fill_pct, valign);
+      prof_end(e);
+      const dim3 blk(256);
+      const double bg_bytes = bg_mode == 2 ? 12.0 : 0.0, out_bytes = 4.0 * out_channels;
+      if (!shadow) {
+        // per canvas pixel: the store and the background; the box (at most 16 bytes per source pixel) comes through L1 / L2
+        prof_begin(e, "canvas_compose", 0, (double)cpx * (out_bytes + bg_bytes) + (double)px * 16);
+        count_kernel("canvas_compose");
+        const int vec = aligned16(d_out) ? 1 : 0;
+        if (out_channels == 4)
+          SDM_LAUNCH((canvas_compose_kernel<4>), dim3((unsigned)sdm_cdiv((int)cpx, 256)), blk, 0, e->stream, d_fg, d_alpha, (const int*)place.p, B, H, W, canvas_h,
+                     canvas_w, dbg, vec, d_out);
+        else
+          SDM_LAUNCH((canvas_compose_kernel<3>), dim3((unsigned)sdm_cdiv((int)((cpx + 3) / 4), 256)), blk, 0, e->stream, d_fg, d_alpha, (const int*)place.p, B, H, W,
+                     canvas_h, canvas_w, dbg, vec, d_out);
+        prof_end(e);
+      } else {
+        prof_begin(e, "canvas_place", 0, (double)cpx * 16 + (double)px * 16);
+        count_kernel("canvas_place");
+        SDM_LAUNCH(canvas_place_kernel, dim3((unsigned)sdm_cdiv((int)cpx, 256)), blk, 0, e->stream, d_fg, d_alpha, (const int*)place.p, B, H, W, canvas_h, canvas_w,
+                   (float*)layer.p);
+        prof_end(e);
+        prof_begin(e, "canvas_blur_rows", 0, (double)cpx * 20);      // A_s arrives in 16-byte pixels
+        count_kernel("canvas_blur_rows");
+        SDM_LAUNCH(canvas_blur_rows_kernel, dim3((unsigned)(B * canvas_h * sdm_cdiv(canvas_w, SDM_CANVAS_ROW_W))), blk, 0, e->stream, (const float*)layer.p, B,
+                   canvas_h, canvas_w, shadow_dx, blur, (float*)tplane.p);
+        prof_end(e);
+        const int th = canvas_tile_h(blur.r);
+        const dim3 grid((unsigned)(B * sdm_cdiv(canvas_h, th) * sdm_cdiv(canvas_w, SDM_CANVAS_TW)));
+        prof_begin(e, "canvas_blur_compose", 0, (double)cpx * (16 + 4.0 * (th + 2 * blur.r) / th + out_bytes + bg_bytes));
+        count_kernel("canvas_blur_compose");
+        const int vec = (aligned16(d_out) && (out_channels == 4 || canvas_w % 4 == 0)) ? 1 : 0;
+        if (out_channels == 4)
+          SDM_LAUNCH((canvas_blur_compose_kernel<4>), grid, blk, canvas_blur_smem(blur.r), e->stream, (const float*)layer.p, (const float*)tplane.p, B, canvas_h,
+                     canvas_w, shadow_dy, shadow_opacity, blur, dbg, vec, d_out);
+        else
+          SDM_LAUNCH((canvas_blur_compose_kernel<3>), grid, blk, canvas_blur_smem(blur.r), e->stream, (const float*)layer.p, (const float*)tplane.p, B, canvas_h,
+                     canvas_w, shadow_dy, shadow_opacity, blur, dbg, vec, d_out);
+        prof_end(e);
+      }
+    }
+    if (shadow) { tfree(e, tplane); tfree(e, layer); }
+    tfree(e, place); tfree(e, box); tfree(e, raw);
     return 0;
   });
 }

@@ -82,7 +82,7 @@ EXPORTS = [
     "sdm_default_config", "sdm_create", "sdm_destroy", "sdm_last_error", "sdm_load_tensor", "sdm_finalize_weights",
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
-    "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_estimate_foreground", "sdm_refine_alpha_guided",
+    "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias",
@@ -123,6 +123,7 @@ class Bindings:
             "sdm_apply_matte_roi": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, f32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, i32, vp]),
             "sdm_estimate_foreground": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
             "sdm_refine_alpha_guided": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp]),
+            "sdm_compose_canvas": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
             "sdm_resident_bytes": (i64, [vp]),
@@ -644,6 +645,82 @@ class Engine:
         if sync:
             self.synchronize()
         return out
+
+    # SDM_CANVAS_* (include/sdmatte.h)
+    CANVAS_MAX_SHADOW_SIGMA = 32
+    CANVAS_MAX_SHADOW_RADIUS = 96
+    CANVAS_MAX_SHADOW_OFFSET = 4096
+    CANVAS_VALIGN = {"top": 0, "center": 1, "bottom": 2}
+
+    @classmethod
+    def _check_canvas_params(cls, what, B, canvas_h, canvas_w, fill_pct, valign, shadow_opacity, shadow_sigma, shadow_dy, shadow_dx):
+        """The argument limits of sdm_compose_canvas; returns the values that cross the C ABI (valign as 0 .. 2, the floats rounded to fp32)."""
+        import math
+        valign = cls.CANVAS_VALIGN.get(valign, valign)
+        for name, v, lo, hi in (("canvas_h", canvas_h, 1, cls.FG_MAX_SIDE), ("canvas_w", canvas_w, 1, cls.FG_MAX_SIDE), ("fill_pct", fill_pct, 1, 100),
+                                ("valign", valign, 0, 2), ("shadow_dy", shadow_dy, -cls.CANVAS_MAX_SHADOW_OFFSET, cls.CANVAS_MAX_SHADOW_OFFSET),
+                                ("shadow_dx", shadow_dx, -cls.CANVAS_MAX_SHADOW_OFFSET, cls.CANVAS_MAX_SHADOW_OFFSET)):
+            if isinstance(v, str) or int(v) != v or not lo <= int(v) <= hi:
+                raise ValueError(f"{what}: {name} must be an integer in {lo} .. {hi}, got {v!r}")
+        if B * int(canvas_h) * int(canvas_w) > cls.FG_MAX_PIXELS:
+            raise ValueError(f"{what}: a canvas of {(B, int(canvas_h), int(canvas_w))} is too large ({cls.FG_MAX_PIXELS} pixels in all)")
+        shadow_opacity, shadow_sigma = C.c_float(float(shadow_opacity)).value, C.c_float(float(shadow_sigma)).value
+        if not (math.isfinite(shadow_opacity) and 0.0 <= shadow_opacity <= 1.0):
+            raise ValueError(f"{what}: shadow_opacity must be a finite number in [0, 1], got {shadow_opacity!r}")
+        if shadow_opacity > 0.0 and not (math.isfinite(shadow_sigma) and 0.0 < shadow_sigma <= cls.CANVAS_MAX_SHADOW_SIGMA):
+            raise ValueError(f"{what}: shadow_sigma must be a finite number in (0, {cls.CANVAS_MAX_SHADOW_SIGMA}], got {shadow_sigma!r}")
+        return int(canvas_h), int(canvas_w), int(fill_pct), int(valign), shadow_opacity, shadow_sigma, int(shadow_dy), int(shadow_dx)
+
+    def compose_canvas(self, fg_bhw3, alpha_bhw, canvas_h, canvas_w, fill_pct=80, valign="center", bg_color=None, bg_image=None, shadow_opacity=0.0,
+                       shadow_sigma=8.0, shadow_dy=0, shadow_dx=0, roi_threshold=0.0, out_channels=None, out=None, sync=True, return_placement=False):
+        """The cut-out on a canvas on the GPU (sdm_compose_canvas, defined in include/sdmatte.h): the box of `alpha_bhw > roi_threshold` of the straight-alpha
+        cut-out (fg [B,H,W,3], alpha [B,H,W]) is resampled premultiplied to fill `fill_pct` % of a canvas_h x canvas_w canvas (valign "top", "center",
+        "bottom" or 0 .. 2), over `bg_image` ([1 or B,canvas_h,canvas_w,3]), else the colour `bg_color` (3 floats), else transparency, with a black shadow
+        (opacity, Gaussian sigma, offset) between the two.  Returns fp32 [B,canvas_h,canvas_w,out_channels]: 3 channels = the composite (needs a background),
+        4 = straight RGBA; the default is 3 with a background and 4 without.  return_placement: also int32 [B,8] = per image {y0, x0, h, w, dy0, dx0, dh, dw}.
+        The box is never read by the host on the way.  Needs no loaded weights.  `sdmatte_nodes.compose_canvas` is the same function in torch, equal to fp32
+        rounding; `sdmatte_nodes.canvas_fit` gives the same placements exactly."""
+        if fg_bhw3.dim() != 4 or fg_bhw3.shape[-1] != 3 or fg_bhw3.numel() == 0:
+            raise ValueError(f"compose_canvas: fg must be a non-empty [B,H,W,3], got {tuple(fg_bhw3.shape)}")
+        B, H, W, _ = (int(v) for v in fg_bhw3.shape)
+        if tuple(alpha_bhw.shape) != (B, H, W):
+            raise ValueError(f"compose_canvas: alpha must be [B,H,W] = {(B, H, W)}, got {tuple(alpha_bhw.shape)}")
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"compose_canvas: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        roi_threshold, _, _ = self._check_roi_params("compose_canvas", roi_threshold, 0, 0)
+        canvas_h, canvas_w, fill_pct, valign, shadow_opacity, shadow_sigma, shadow_dy, shadow_dx = self._check_canvas_params(
+            "compose_canvas", B, canvas_h, canvas_w, fill_pct, valign, shadow_opacity, shadow_sigma, shadow_dy, shadow_dx)
+        bg_mode = 2 if bg_image is not None else (1 if bg_color is not None else 0)
+        if out_channels is None:
+            out_channels = 3 if bg_mode else 4
+        if out_channels not in (3, 4) or (bg_mode == 0 and out_channels != 4):
+            raise ValueError(f"compose_canvas: out_channels must be 4, or 3 with a background, got {out_channels!r}")
+        rgb, bg_batch = None, 0
+        if bg_mode == 1:
+            rgb = np.ascontiguousarray(np.asarray(bg_color, np.float32).reshape(-1))
+            if rgb.shape != (3, ):
+                raise ValueError(f"compose_canvas: bg_color must be 3 numbers, got {bg_color!r}")
+        fg_bhw3 = fg_bhw3.float().contiguous()
+        alpha_bhw = alpha_bhw.float().contiguous()
+        if bg_mode == 2:
+            if bg_image.dim() != 4 or tuple(bg_image.shape[1:]) != (canvas_h, canvas_w, 3) or int(bg_image.shape[0]) not in (1, B):
+                raise ValueError(f"compose_canvas: bg_image must be [1 or {B},{canvas_h},{canvas_w},3], got {tuple(bg_image.shape)}")
+            bg_image = bg_image.float().contiguous()
+            bg_batch = int(bg_image.shape[0])
+        dev = fg_bhw3.device
+        if out is None:
+            out = torch.empty(B, canvas_h, canvas_w, out_channels, dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (B, canvas_h, canvas_w, out_channels):
+            raise ValueError(f"compose_canvas: out must be a contiguous fp32 tensor {(B, canvas_h, canvas_w, out_channels)}")
+        place = torch.empty(B, 8, dtype=torch.int32, device=dev) if return_placement else None
+        stream = self._check_io("compose_canvas", fg_bhw3, alpha_bhw, bg_image, out, place)
+        self._check(self.lib.sdm_compose_canvas(self.h, _ptr(fg_bhw3), _ptr(alpha_bhw), B, H, W, roi_threshold, canvas_h, canvas_w, fill_pct, valign, bg_mode,
+                                                rgb.ctypes.data_as(C.c_void_p) if rgb is not None else None, _ptr(bg_image), bg_batch, shadow_opacity,
+                                                shadow_sigma, shadow_dy, shadow_dx, _ptr(out), out_channels, _ptr(place), self._kind(fg_bhw3), stream),
+                    "sdm_compose_canvas")
+        if sync:
+            self.synchronize()
+        return (out, place) if return_placement else out
 
     def synchronize(self):
         self._check(self.lib.sdm_synchronize(self.h), "sdm_synchronize")

@@ -352,5 +352,13 @@ class MultiGpuEngine:
         self._fan(B, call)
         return alpha, matted, trimap, roi
 
+    def compose_canvas(self, fg_bhw3, alpha_bhw, canvas_h, canvas_w, fill_pct=80, valign="center", bg_color=None, bg_image=None, shadow_opacity=0.0,
+                       shadow_sigma=8.0, shadow_dy=0, shadow_dx=0, roi_threshold=0.0, out_channels=None, return_placement=False):
+        """The cut-out on a canvas (no model involved): on the first engine; inputs on the host or any device -> canvas (and placements) on the HOST."""
+        bg = self._to_host(bg_image) if bg_image is not None else None
+        return self.engines[0].compose_canvas(self._to_host(fg_bhw3), self._to_host(alpha_bhw), canvas_h, canvas_w, fill_pct, valign, bg_color, bg,
+                                              shadow_opacity, shadow_sigma, shadow_dy, shadow_dx, roi_threshold, out_channels,
+                                              return_placement=return_placement)
+
     def last_forward_ms(self):
         return max(e.last_forward_ms() for e in self.engines)

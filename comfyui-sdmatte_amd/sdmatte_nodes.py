@@ -22,6 +22,9 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
   * and one registered only with SDMATTE_ROI_NODE=1: `SDMatteApplyROI` is `SDMatteApplyMask` on the subject instead of the frame: the model is shown
     the box of the trimap at `inference_size` and its alpha is put back into the frame, all inside one engine call; `subject_roi` and `paste_roi`
     below are the exact CPU restatements of the box and of the way back;
+  * and one registered only with SDMATTE_CANVAS_NODE=1: `SDMatteCanvas` frames a straight-alpha cut-out on a canvas of a given size (scaled, aligned,
+    over a colour, an image or transparency, with an optional soft shadow), resampled premultiplied, in one engine call; `canvas_fit` is the exact
+    restatement of its placement and `compose_canvas` its torch restatement;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -489,6 +492,106 @@ def paste_roi(crop_bhw, roi, H, W):
     return out
 
 
+def canvas_fit(roi, canvas_h, canvas_w, fill_pct=80, valign="center"):
+    """The placements of `Engine.compose_canvas` in exact integers (the definition is in include/sdmatte.h, sdm_compose_canvas): roi int [B,4] = {y0, x0, h, w}
+    -> int32 [B,8] = {y0, x0, h, w, dy0, dx0, dh, dw}, the box scaled to fill `fill_pct` % of the canvas and aligned in it."""
+    from .engine import Engine
+    canvas_h, canvas_w, fill_pct, valign, *_ = Engine._check_canvas_params("canvas_fit", 1, canvas_h, canvas_w, fill_pct, valign, 0.0, 1.0, 0, 0)
+    roi = torch.as_tensor(roi).reshape(-1, 4)
+    th, tw = max(1, canvas_h * fill_pct // 100), max(1, canvas_w * fill_pct // 100)
+    mv = (canvas_h - th) // 2
+    out = []
+    for y0, x0, h, w in roi.tolist():
+        if h < 1 or w < 1:
+            raise ValueError(f"canvas_fit: empty box {(y0, x0, h, w)}")
+        if th * w <= tw * h:
+            dh, dw = th, max(1, (w * th + h // 2) // h)
+        else:
+            dw, dh = tw, max(1, (h * tw + w // 2) // w)
+        dy0 = (mv, (canvas_h - dh) // 2, canvas_h - mv - dh)[valign]
+        out.append((y0, x0, h, w, dy0, (canvas_w - dw) // 2, dh, dw))
+    return torch.tensor(out, dtype=torch.int32).reshape(-1, 8)
+
+
+def _shadow_weights(shadow_sigma):
+    """(r, the 2r + 1 weights of offsets -r .. r as float32 values): exp(-i^2 / (2 sigma^2)) / sum in double from the fp32 sigma."""
+    import math
+    import numpy as np
+    s = float(np.float32(shadow_sigma))
+    r = max(1, math.ceil(3.0 * s))
+    g = [math.exp(-(i * i) / (2.0 * s * s)) for i in range(-r, r + 1)]
+    total = 0.0
+    for v in g:
+        total += v
+    return r, [float(np.float32(v / total)) for v in g]
+
+
+def compose_canvas(fg, alpha, canvas_h, canvas_w, fill_pct=80, valign="center", bg_color=None, bg_image=None, shadow_opacity=0.0, shadow_sigma=8.0,
+                   shadow_dy=0, shadow_dx=0, roi_threshold=0.0, out_channels=None, dtype=torch.float32, return_placement=False):
+    """`Engine.compose_canvas` in torch (the definition is in include/sdmatte.h, sdm_compose_canvas), evaluated in `dtype` (float32: equal to the GPU call up to
+    fp32 rounding; float64: the reference the tests measure both against).  Built on `subject_roi`, `canvas_fit` and
+    torch.nn.functional.interpolate(mode="bilinear", antialias=True) of the premultiplied box.  Runs on the device of `fg`."""
+    import torch.nn.functional as F
+    from .engine import Engine
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"compose_canvas: dtype must be torch.float32 or torch.float64, got {dtype!r}")
+    if fg.dim() != 4 or fg.shape[-1] != 3 or fg.numel() == 0:
+        raise ValueError(f"compose_canvas: fg must be a non-empty [B,H,W,3], got {tuple(fg.shape)}")
+    B, H, W, _ = (int(v) for v in fg.shape)
+    if tuple(alpha.shape) != (B, H, W):
+        raise ValueError(f"compose_canvas: alpha must be [B,H,W] = {(B, H, W)}, got {tuple(alpha.shape)}")
+    canvas_h, canvas_w, fill_pct, valign, shadow_opacity, shadow_sigma, shadow_dy, shadow_dx = Engine._check_canvas_params(
+        "compose_canvas", B, canvas_h, canvas_w, fill_pct, valign, shadow_opacity, shadow_sigma, shadow_dy, shadow_dx)
+    bg_mode = 2 if bg_image is not None else (1 if bg_color is not None else 0)
+    if out_channels is None:
+        out_channels = 3 if bg_mode else 4
+    if out_channels not in (3, 4) or (bg_mode == 0 and out_channels != 4):
+        raise ValueError(f"compose_canvas: out_channels must be 4, or 3 with a background, got {out_channels!r}")
+    dev = fg.device
+    alpha = alpha.detach().float()
+    place = canvas_fit(subject_roi(alpha, roi_threshold, 0, 0, False), canvas_h, canvas_w, fill_pct, valign)
+    a = torch.nan_to_num(alpha.to(dtype), nan=0.0).clamp(0.0, 1.0)
+    prem = torch.cat([a.unsqueeze(1) * fg.detach().float().to(dtype).permute(0, 3, 1, 2), a.unsqueeze(1)], 1)          # [B,4,H,W] = (a F, a)
+    layer = torch.zeros(B, 4, canvas_h, canvas_w, dtype=dtype, device=dev)
+    for b, (y0, x0, h, w, dy0, dx0, dh, dw) in enumerate(place.tolist()):
+        crop = prem[b:b + 1, :, y0:y0 + h, x0:x0 + w]
+        if (dh, dw) != (h, w):
+            crop = F.interpolate(crop, size=(dh, dw), mode="bilinear", align_corners=False, antialias=True)
+        layer[b, :, dy0:dy0 + dh, dx0:dx0 + dw] = crop[0]
+    Ps, As = layer[:, :3], layer[:, 3:]
+    S = torch.zeros_like(As)
+    if shadow_opacity > 0.0:
+        r, wts = _shadow_weights(shadow_sigma)
+        px, py = r + abs(shadow_dx), r + abs(shadow_dy)
+        src = F.pad(As, (px, px, 0, 0))
+        T = torch.zeros_like(As)
+        for k, wk in enumerate(wts):                        # rows first, i ascending
+            o = px - shadow_dx + k - r
+            T = T + wk * src[..., o:o + canvas_w]
+        src = F.pad(T, (0, 0, py, py))
+        for k, wk in enumerate(wts):
+            o = py - shadow_dy + k - r
+            S = S + wk * src[:, :, o:o + canvas_h, :]
+        S = shadow_opacity * S
+    if bg_mode == 2:
+        if bg_image.dim() != 4 or tuple(bg_image.shape[1:]) != (canvas_h, canvas_w, 3) or int(bg_image.shape[0]) not in (1, B):
+            raise ValueError(f"compose_canvas: bg_image must be [1 or {B},{canvas_h},{canvas_w},3], got {tuple(bg_image.shape)}")
+        C = bg_image.detach().float().to(dtype).to(dev).permute(0, 3, 1, 2)
+    elif bg_mode == 1:
+        rgb = [float(v) for v in bg_color]
+        if len(rgb) != 3:
+            raise ValueError(f"compose_canvas: bg_color must be 3 numbers, got {bg_color!r}")
+        C = torch.tensor(rgb, dtype=torch.float32, device=dev).to(dtype).reshape(1, 3, 1, 1)
+    else:
+        C = torch.zeros(1, 3, 1, 1, dtype=dtype, device=dev)
+    P = Ps + (1.0 - As) * ((1.0 - S) * C)
+    A = torch.ones_like(As) if bg_mode else As + (1.0 - As) * S
+    if out_channels == 4:
+        P = torch.cat([torch.where(A > 0, P / torch.where(A > 0, A, torch.ones_like(A)), torch.zeros_like(P)), A], 1)
+    out = P.permute(0, 2, 3, 1).contiguous()
+    return (out, place) if return_placement else out
+
+
 def _nearest_index(n_dst, n_src):
     """src = min(n_src - 1, (i * n_src) // n_dst) for i = 0 .. n_dst - 1 (integers only)."""
     return torch.clamp((torch.arange(n_dst, dtype=torch.int64) * n_src) // n_dst, max=n_src - 1)
@@ -882,9 +985,68 @@ class SDMatteRefineAlpha:
         return (eng.refine_alpha_guided(image.detach().cpu(), alpha.detach().cpu(), int(subsample), int(radius), float(eps)), )
 
 
-def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False):
+_CANVAS_INPUTS = {
+    "fill_pct": ("INT", {"default": 80, "min": 1, "max": 100, "step": 1, "tooltip": "share of the canvas (per side) the subject's box is scaled to fill"}),
+    "valign": (["center", "top", "bottom"], {"default": "center", "tooltip": "bottom: the subject stands on the lower edge of the fill area"}),
+    "background": (["color", "transparent"], {"default": "color", "tooltip": "ignored when a background image is connected"}),
+    "bg_red": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.01}),
+    "bg_green": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.01}),
+    "bg_blue": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.01}),
+    "shadow_opacity": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 1.0, "step": 0.01, "tooltip": "0 = no shadow"}),
+    "shadow_sigma": ("FLOAT", {"default": 8.0, "min": 0.1, "max": 32.0, "step": 0.1, "tooltip": "softness of the shadow, in canvas pixels"}),
+    "shadow_dy": ("INT", {"default": 0, "min": -4096, "max": 4096, "step": 1, "tooltip": "shadow offset downwards, in canvas pixels"}),
+    "shadow_dx": ("INT", {"default": 0, "min": -4096, "max": 4096, "step": 1, "tooltip": "shadow offset to the right, in canvas pixels"}),
+}
+
+
+class SDMatteCanvas:
+    """Foreground + alpha -> the subject on a canvas of a given size on the GPU: scaled to fill a share of it, centred or on a baseline, over a colour, an
+    image or transparency (RGBA), with an optional soft shadow.  Colours are resampled premultiplied, so no fringe.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"foreground": ("IMAGE", {"tooltip": "foreground colours of the cut-out (foreground of SDMatte Foreground Colours, or the image)"}),
+                             "alpha": ("MASK", {"tooltip": "alpha matte of the foreground"}),
+                             "canvas_width": ("INT", {"default": 1024, "min": 1, "max": 32768, "step": 1}),
+                             "canvas_height": ("INT", {"default": 1024, "min": 1, "max": 32768, "step": 1})},
+                "optional": dict(_CANVAS_INPUTS, background_image=("IMAGE", {"tooltip": "opaque background at canvas size (one image, or one per foreground)"}),
+                                 force_cpu=("BOOLEAN", {"default": False, "tooltip": "evaluate the torch restatement on the CPU instead of the GPU call"}))}
+
+    RETURN_TYPES = ("IMAGE", )
+    RETURN_NAMES = ("image", )
+    FUNCTION = "compose"
+    CATEGORY = "Matting/SDMatte"
+
+    def compose(self, foreground, alpha, canvas_width, canvas_height, fill_pct=80, valign="center", background="color", bg_red=1.0, bg_green=1.0,
+                bg_blue=1.0, shadow_opacity=0.0, shadow_sigma=8.0, shadow_dy=0, shadow_dx=0, background_image=None, force_cpu=False):
+        from .engine import Engine
+        if foreground.dim() != 4 or foreground.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] foreground must be [B,H,W,3], got {tuple(foreground.shape)}")
+        if alpha.dim() == 2:
+            alpha = alpha.unsqueeze(0)
+        if tuple(alpha.shape) != tuple(foreground.shape[:3]):
+            raise ValueError(f"[SDMatte] alpha must be [B,H,W] of the foreground {tuple(foreground.shape[:3])}, got {tuple(alpha.shape)}")
+        if background not in ("color", "transparent"):
+            raise ValueError(f"[SDMatte] unknown background {background!r}")
+        B = int(foreground.shape[0])
+        Engine._check_canvas_params("[SDMatte] canvas", B, canvas_height, canvas_width, fill_pct, valign, shadow_opacity, shadow_sigma, shadow_dy, shadow_dx)
+        if background_image is not None and (background_image.dim() != 4 or tuple(background_image.shape[1:]) != (int(canvas_height), int(canvas_width), 3) or
+                                             int(background_image.shape[0]) not in (1, B)):
+            raise ValueError(f"[SDMatte] background_image must be [1 or {B},{int(canvas_height)},{int(canvas_width)},3] (it is not resized), "
+                             f"got {tuple(background_image.shape)}")
+        color = (float(bg_red), float(bg_green), float(bg_blue)) if background == "color" and background_image is None else None
+        args = (foreground.detach().cpu(), alpha.detach().cpu(), int(canvas_height), int(canvas_width), int(fill_pct), valign, color,
+                background_image.detach().cpu() if background_image is not None else None, float(shadow_opacity), float(shadow_sigma), int(shadow_dy),
+                int(shadow_dx))
+        if force_cpu:      # an explicit request, never a silent substitute: the same function in torch
+            return (compose_canvas(*args), )
+        return (_trimap_engine(_torch_device()).compose_canvas(*args), )
+
+
+def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False, canvas: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
-    node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`, plus the subject-box node when `roi`."""
+    node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`, plus the subject-box node when `roi`,
+    plus the canvas node when `canvas`."""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
@@ -902,13 +1064,17 @@ def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, c
     if roi:
         classes["SDMatteApplyROI"] = SDMatteApplyROI
         names["SDMatteApplyROI"] = "Apply SDMatte (Subject Box)"
+    if canvas:
+        classes["SDMatteCanvas"] = SDMatteCanvas
+        names["SDMatteCanvas"] = "SDMatte Canvas"
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1), like the multi-GPU fan-out
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
 NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
                                                                 os.environ.get("SDMATTE_REFINE_NODE") == "1",
                                                                 os.environ.get("SDMATTE_CLEAN_NODE") == "1",
-                                                                os.environ.get("SDMATTE_ROI_NODE") == "1")
+                                                                os.environ.get("SDMATTE_ROI_NODE") == "1",
+                                                                os.environ.get("SDMATTE_CANVAS_NODE") == "1")

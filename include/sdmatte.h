@@ -302,6 +302,51 @@ int sdm_estimate_foreground(sdm_ctx* ctx, const float* image_bhwc, const float* 
 int sdm_refine_alpha_guided(sdm_ctx* ctx, const float* image_bhwc, const float* alpha_bhw, int B, int H, int W, int subsample, int radius, float eps,
                             float* out_bhw, int ptr_kind, void* stream);
 
+/* The cut-out on a canvas, on the GPU (beyond the reference): the subject of a straight-alpha cut-out - found by its alpha - scaled to fill a share of a
+ * canvas of a given size, centred or on a baseline, over transparency, a colour or an image, with an optional soft shadow.  Colours are resampled
+ * premultiplied: resampling straight colours lets the invisible colour of alpha-0 pixels bleed into every soft edge.  Everything is fp32.
+ *   fg fp32 [B,H,W,3] (values used as they are), alpha fp32 [B,H,W] (a = alpha with NaN -> 0, then clamped to [0,1]),
+ *   out fp32 [B,canvas_h,canvas_w,out_channels], place_out (may be NULL) int32 [B][8], of the same pointer kind as the planes.
+ *   box      {y0, x0, h, w} of sdm_subject_roi with the RAW alpha, roi_threshold, margin_px 0, margin_pct 0 and square 0 (one fp32 compare per pixel, so NaN is
+ *            outside; an empty set gives the whole frame).
+ *   fit      integers only, the products 64-bit, every division truncating: th = max(1, canvas_h*fill_pct/100), tw = max(1, canvas_w*fill_pct/100).
+ *            If th*w <= tw*h: dh = th, dw = max(1, (w*th + h/2)/h); otherwise dw = tw, dh = max(1, (h*tw + w/2)/w).  dx0 = (canvas_w - dw)/2.  With
+ *            mv = (canvas_h - th)/2: dy0 = mv for valign 0 (top), (canvas_h - dh)/2 for valign 1 (centre), canvas_h - mv - dh for valign 2 (bottom: the subject
+ *            stands on the lower edge of the fill area).  The destination rectangle [dy0, dy0+dh) x [dx0, dx0+dw) lies inside the canvas.
+ *            place_out[b] = {y0, x0, h, w, dy0, dx0, dh, dw}.  GPU, emulator and sdmatte_nodes.canvas_fit agree exactly.
+ *   place    inside the destination rectangle the four planes (a*F.r, a*F.g, a*F.b, a) of the box are resampled from (h,w) to (dh,dw) with the antialiased
+ *            bilinear filter of the node (torchvision Resize = interpolate(bilinear, align_corners=False, antialias=True); the plain copy when
+ *            (dh,dw) == (h,w)).  Pixels outside the box do not exist: the result is that of crop, premultiply, resize.  Outside the rectangle the layer is 0.
+ *            This is the premultiplied subject layer (P_s, A_s) on the canvas.
+ *   shadow   skipped entirely when shadow_opacity == 0 (sigma and offsets are then not looked at).  r = ceil(3*shadow_sigma); w_i = exp(-i*i/(2*sigma*sigma))
+ *            for i = -r .. r, divided by their sum: computed on the host in double from the fp32 sigma, rounded to fp32, at most
+ *            2*SDM_CANVAS_MAX_SHADOW_RADIUS + 1 of them.  With A_s = 0 beyond the canvas,
+ *              T(y,x) = sum over i = -r .. r (ascending) of w_i * A_s(y, x - shadow_dx + i)      (rows first; T of a row beyond the canvas is 0)
+ *              S(y,x) = shadow_opacity * sum over j = -r .. r (ascending) of w_j * T(y - shadow_dy + j, x)
+ *            i.e. S = shadow_opacity * (G * A_s)(y - shadow_dy, x - shadow_dx), the separable Gaussian with zero padding.  The colour is black.
+ *   compose  "over" on premultiplied layers from bottom to top: the background (bg_mode 0: none; 1: the opaque colour bg_rgb3, 3 floats, ALWAYS a HOST
+ *            pointer; 2: the opaque image bg_image [bg_batch,canvas_h,canvas_w,3] with bg_batch 1 or B, at canvas size), the shadow layer (0, S), the subject
+ *            layer.  With C the background colour (0 without one) and S = 0 without a shadow: P = P_s + (1 - A_s) * ((1 - S) * C);
+ *            A = 1 with a background, A_s + (1 - A_s) * S without one.
+ *   out      out_channels 3: P (needs bg_mode 1 or 2).  out_channels 4: straight RGBA (P / A where A > 0, else 0; A).
+ * Limits: B, H, W and roi_threshold as sdm_subject_roi; canvas sides in 1 .. SDM_FG_MAX_SIDE and B*canvas_h*canvas_w <= SDM_FG_MAX_PIXELS; fill_pct in 1 .. 100;
+ * valign in 0 .. 2; bg_mode in 0 .. 2 (bg_rgb3 given with 1, bg_image given with 2), out_channels 4 with bg_mode 0; shadow_opacity finite in [0, 1];
+ * shadow_sigma finite in (0, SDM_CANVAS_MAX_SHADOW_SIGMA] when the opacity is above 0; |shadow_dy| and |shadow_dx| at most SDM_CANVAS_MAX_SHADOW_OFFSET:
+ * SDM_ERR_INVALID otherwise, and then nothing is queued or written.  Stream contract and pointer kinds as sdm_make_trimap; sdm_last_forward_ms covers the
+ * launches.  Needs no weights.  sdmatte_nodes.compose_canvas is the same function in torch (equal to fp32 rounding, not bit for bit).
+ * The number of launches depends only on whether the shadow is on, never on B, the sizes or the content (csrc/k_canvas.h); no host readback.
+ *   without a shadow 5: roi_init, roi_reduce, roi_finalize, canvas_fit, canvas_compose (the canvas is written once; no canvas-sized intermediate exists)
+ *   with a shadow    7: roi_init, roi_reduce, roi_finalize, canvas_fit, canvas_place (the layer, 16 bytes per canvas pixel), canvas_blur_rows (T, 4 bytes per
+ *                       canvas pixel), canvas_blur_compose (the column sums fused with the composition)
+ * These are the names in sdm_kernel_counts and the per-launch profile.  The raw extrema, the box, the placements, the layer and T are part of the activation
+ * arena, host pointers go through the I/O staging (sdm_resident_bytes counts both, sdm_release_memory frees them). */
+#define SDM_CANVAS_MAX_SHADOW_SIGMA 32
+#define SDM_CANVAS_MAX_SHADOW_RADIUS 96
+#define SDM_CANVAS_MAX_SHADOW_OFFSET 4096
+int sdm_compose_canvas(sdm_ctx* ctx, const float* fg_bhw3, const float* alpha_bhw, int B, int H, int W, float roi_threshold, int canvas_h, int canvas_w,
+                       int fill_pct, int valign, int bg_mode, const float* bg_rgb3, const float* bg_image, int bg_batch, float shadow_opacity,
+                       float shadow_sigma, int shadow_dy, int shadow_dx, float* out, int out_channels, int32_t* place_out, int ptr_kind, void* stream);
+
 /* Memory the engine holds outside any framework allocator: packed weights + activation arena (sized by the largest batch /
  * resolution seen) + I/O staging.  sdm_release_memory frees everything but the weights (the next forward re-allocates). */
 int64_t sdm_resident_bytes(sdm_ctx* ctx);
@@ -327,7 +372,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided: their launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
