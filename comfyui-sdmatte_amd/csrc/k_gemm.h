@@ -38,6 +38,16 @@
 //   EPI 0  fp32 [rows][ldo] (+bias, +fp32 residual); EPI 4 = 0 + the GroupNorm statistics of the consumer (partial rows, k_conv.h ConvParams::stats)
 //   EPI 1  GEGLU u * gelu(g) -> P3          EPI 3  linear (+bias, +residual) -> P3
 //   EPI 2  q | k | v operand planes of the split-precision attention (fp16 hi + e5m2 pair plane, ConvParams::out_f32 == 3)
+//
+// UP = 1 (EPI 0 / 4): nearest x2 up-sample + 3x3 conv (Upsample2D) as FOUR 2x2-tap convs over the low-resolution image, one per output phase (py, px).
+// Output pixel (2y + py, 2x + px) reads source rows y + py - 1, y + py and columns x + px - 1, x + px only; the 3x3 taps that fall on the same source
+// pixel are summed once, when the weights are derived (derive_gemm_w3_kernel<1>): 16 tap-products per source pixel instead of 36, zero padding included.
+// The operand is ONE P3 plane over the zero-bordered grid [N][H + 2][W + 2] (to_p3_pad_kernel), so a tap is a constant row shift of the flat pixel
+// index and a phase is a plain GEMM with K = 4 * Cin: chunk c of the K loop is (channels 32 * (c >> 2) .., tap c & 3), the four taps of a channel
+// chunk back to back (they read nearly the same cache lines).  The shifted rows do not start on a block boundary, so every lane of an A DMA computes
+// its own 16-byte source (p3_hi_off / p3_xl_off) behind a descriptor over the whole plane: rows outside it read 0 and feed border rows only, which are
+// neither stored nor counted.  Tile ids run over (M tile, phase, N tile) - GemmP3Params::tiles_n = 4 * N tiles - so the 16 shifted reads of a row band
+// follow each other on the XCD that owns the M tile.  Row (n, yp, xp) of phase (py, px) is output pixel (2 (yp - 1) + py, 2 (xp - 1) + px).
 #pragma once
 #include "sdm_common.h"
 
@@ -86,6 +96,10 @@ struct GemmP3Params {
   int sa, sb;                                         // E8M0 exponents of the fp8 operand scales (activations 2^-11, weights 2^-e8)
   int tiles_m, tiles_n, xcd_chunk, tiles_per_img;     // xcd_chunk > 0: XCD-aware order (block b -> XCD b % 8 owns M tiles [x*chunk, (x+1)*chunk))
   int ablate;                                         // bench only (sdm_bench_gemm_p3; results are garbage): 1 no MFMAs, 2 no DMAs behind the prologue, 4 no epilogue
+  // UP = 1: M = N * (up_H + 2) * (up_W + 2) rows of the zero-bordered low-resolution grid, rows_per_img = (up_H + 2) * (up_W + 2), K = Cin of the plane
+  // (the GEMM's K is 4 * Cin), w = four W3 matrices [4 * Cin][N], one per phase 2 * py + px; out = fp32 NHWC [N][2 up_H][2 up_W][ldo];
+  // stats: [imgs][tiles_per_img * 8][ldo][2], partial row (M tile, phase, wave row)
+  int up_H, up_W;
 };
 
 // 16 fp32 values of a 32-row x 32-channel accumulator block (register r = channel (r&3) + 8*(r>>2) + 4*(lane>>5) of row lane&31)
@@ -121,7 +135,7 @@ SDM_DEV_INLINE void p3_pack_block(const float (&v)[16], u32x4 (&hi)[2], u32x4& x
 
 // NS = LDS stages (ring): the DMAs of chunk c + NS - 1 are issued when chunk c starts - NS - 1 chunks of landing time.  2 stages of the 256 x 128 tile
 // leave room for two blocks per CU; deeper rings trade the second block for landing time (one block per CU from 3 stages of the 256-row tile).
-template <int MT, int NT, int EPI, int NS = 2>
+template <int MT, int NT, int EPI, int NS = 2, int UP = 0>
 __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 128) <= 80 * 1024) ? 2 : 1) gemm_p3_kernel(GemmP3Params p) {
   constexpr int BM = 2 * MT * 32, BN = 2 * NT * 32;
   constexpr int A_HI = BM * 64, A_XL = BM * 32, B_HI = BN * 64, B_F8 = BN * 64;
@@ -130,11 +144,14 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
   constexpr int PER = (BM / 16 + 3) / 4 + (BM / 32 + 3) / 4 + 2 * (BN / 16 / 4);
   static_assert(EPI != 1 || NT == 2, "GEGLU: a wave's 64 columns are one [u32 | g32] group");
   static_assert(NS >= 2 && NS * STAGE <= 160 * 1024 && (NS - 2) * PER <= 63, "LDS ring / vmcnt range");
+  static_assert(!UP || EPI == 0 || EPI == 4, "up-sampling phase convs store fp32 rows");
   SDM_DYN_SMEM(smem);
   const int tx = (int)threadIdx.x, lane = tx & 63, wave = SDM_UNIFORM_I(tx >> 6);
   const int wm = wave >> 1, wn = wave & 1, h = lane >> 5, l31 = lane & 31;
-  const int nch = p.K >> 5;
+  const int nch = UP ? (p.K >> 5) * 4 : (p.K >> 5);
   const unsigned int K = (unsigned int)p.K, N = (unsigned int)p.N;
+  const int up_wp = p.up_W + 2;                       // UP: row pitch of the bordered grid
+  const int up_tn = p.tiles_n >> 2;                   // UP: N tiles per phase (tile id nt = phase * up_tn + N tile)
   const long rows_pad = (long)p3_rows_pad((size_t)p.M);
   // Tiles of this block: the virtual ids blockIdx.x, + gridDim.x, ... (a persistent grid; gridDim.x % 8 == 0 keeps a block's tiles on its XCD's M range).
   // The block treats its (tile, chunk) pairs as ONE stream: the DMAs of a tile's first chunk are issued while the previous tile's last chunk is
@@ -165,31 +182,56 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
   const sdm_rsrc rs_w = sdm_make_rsrc(p.w, (unsigned int)nch * N * 128u);
   const unsigned int vo_w = (unsigned int)lane * 16u;
   // chunk c of the tile at row m0 (m0 % 32 == 0), channel n0: 16-row block i of HI at (i * K/32 + c) KB behind the tile's first block, 32-row block i of XL likewise
-  auto issue = [&](long m0, int n0, int c, unsigned char* st) {
-    const unsigned int rows_avail = (unsigned int)(rows_pad - m0 < (long)BM ? rows_pad - m0 : (long)BM);
-    const sdm_rsrc rs_ahi = sdm_make_rsrc((const unsigned char*)p.a_hi + (size_t)m0 * K * 2, rows_avail * K * 2u);
-    const sdm_rsrc rs_axl = sdm_make_rsrc(p.a_xl + (size_t)m0 * K, rows_avail * K);
-    // (a region of fewer than 4 pieces is copied redundantly by the surplus waves - same source, same destination - so that every wave's count is PER)
+  auto issue = [&](long m0, int n0, int ph, int c, unsigned char* st) {
+    sdm_rsrc rs_wc = rs_w;
+    if (UP) {
+      // tap (a, b) = (c >> 1 & 1, c & 1) of phase ph = 2 py + px: source row = row + (py - 1 + a) * (W + 2) + (px - 1 + b), channels 32 * (c >> 2) ..
+      const int tap = c & 3, cc = c >> 2;
+      const long shift = (long)((ph >> 1) - 1 + (tap >> 1)) * up_wp + ((ph & 1) - 1 + (tap & 1));
+      const sdm_rsrc rs_ahi = sdm_make_rsrc(p.a_hi, (unsigned int)rows_pad * K * 2u);
+      const sdm_rsrc rs_axl = sdm_make_rsrc(p.a_xl, (unsigned int)rows_pad * K);
+      // lane -> its 16 bytes of the LDS image: HI [granule lane >> 4][row lane & 15], XL [half lane >> 5][row lane & 31]
 #pragma unroll
-    for (int i0 = 0; i0 < BM / 16; i0 += 4) {
-      const int i = (i0 + wave) % (BM / 16);
-      sdm_glds16_buf(rs_ahi, vo_w, ((unsigned int)i * (K >> 5) + (unsigned int)c) << 10, st + i * 1024);
-    }
+      for (int i0 = 0; i0 < BM / 16; i0 += 4) {
+        const int i = (i0 + wave) % (BM / 16);
+        const long row = m0 + i * 16 + (lane & 15) + shift;
+        const unsigned int vo = (row >= 0 && row < rows_pad) ? (unsigned int)p3_hi_off((size_t)row, (int)K, cc * 32 + (lane >> 4) * 8) : SDM_BUF_INVALID;
+        sdm_glds16_buf(rs_ahi, vo, 0u, st + i * 1024);
+      }
 #pragma unroll
-    for (int i0 = 0; i0 < BM / 32; i0 += 4) {
-      const int i = (i0 + wave) % (BM / 32);
-      sdm_glds16_buf(rs_axl, vo_w, ((unsigned int)i * (K >> 5) + (unsigned int)c) << 10, st + OFF_AXL + i * 1024);
+      for (int i0 = 0; i0 < BM / 32; i0 += 4) {
+        const int i = (i0 + wave) % (BM / 32);
+        const long row = m0 + i * 32 + l31 + shift;
+        const unsigned int vo = (row >= 0 && row < rows_pad) ? (unsigned int)p3_xl_off((size_t)row, (int)K, cc * 32 + h * 8) : SDM_BUF_INVALID;
+        sdm_glds16_buf(rs_axl, vo, 0u, st + OFF_AXL + i * 1024);
+      }
+      rs_wc = sdm_make_rsrc(p.w + (size_t)ph * ((size_t)nch * N * 128u), (unsigned int)nch * N * 128u);
+    } else {
+      const unsigned int rows_avail = (unsigned int)(rows_pad - m0 < (long)BM ? rows_pad - m0 : (long)BM);
+      const sdm_rsrc rs_ahi = sdm_make_rsrc((const unsigned char*)p.a_hi + (size_t)m0 * K * 2, rows_avail * K * 2u);
+      const sdm_rsrc rs_axl = sdm_make_rsrc(p.a_xl + (size_t)m0 * K, rows_avail * K);
+      // (a region of fewer than 4 pieces is copied redundantly by the surplus waves - same source, same destination - so that every wave's count is PER)
+#pragma unroll
+      for (int i0 = 0; i0 < BM / 16; i0 += 4) {
+        const int i = (i0 + wave) % (BM / 16);
+        sdm_glds16_buf(rs_ahi, vo_w, ((unsigned int)i * (K >> 5) + (unsigned int)c) << 10, st + i * 1024);
+      }
+#pragma unroll
+      for (int i0 = 0; i0 < BM / 32; i0 += 4) {
+        const int i = (i0 + wave) % (BM / 32);
+        sdm_glds16_buf(rs_axl, vo_w, ((unsigned int)i * (K >> 5) + (unsigned int)c) << 10, st + OFF_AXL + i * 1024);
+      }
     }
     const unsigned int wb = (unsigned int)c * N * 128u + (unsigned int)n0 * 64u;
 #pragma unroll
     for (int i0 = 0; i0 < BN / 16; i0 += 4) {
       const int i = i0 + wave;
-      sdm_glds16_buf(rs_w, vo_w, wb + (unsigned int)i * 1024u, st + OFF_BHI + i * 1024);
+      sdm_glds16_buf(rs_wc, vo_w, wb + (unsigned int)i * 1024u, st + OFF_BHI + i * 1024);
     }
 #pragma unroll
     for (int i0 = 0; i0 < BN / 16; i0 += 4) {
       const int i = i0 + wave;
-      sdm_glds16_buf(rs_w, vo_w, wb + N * 64u + (unsigned int)i * 1024u, st + OFF_BF8 + i * 1024);
+      sdm_glds16_buf(rs_wc, vo_w, wb + N * 64u + (unsigned int)i * 1024u, st + OFF_BF8 + i * 1024);
     }
   };
 
@@ -215,19 +257,22 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
   // the issue side of the stream: tile v_iss (row m0_i, channel n0_i), next chunk ic
   int mt_c, nt_c, v_cur = next_tile((int)blockIdx.x, mt_c, nt_c);
   if (v_cur < 0) return;
-  int v_iss = v_cur, ic = 0, st_cur = 0, st_nxt = 0, ahead = 0, n0_i = nt_c * BN;
+  // (UP: the tile id's N part is phase * up_tn + N tile)
+  auto nt_phase = [&](int nt) -> int { return UP ? nt / up_tn : 0; };
+  auto nt_col0 = [&](int nt) -> int { return (UP ? nt % up_tn : nt) * BN; };
+  int v_iss = v_cur, ic = 0, st_cur = 0, st_nxt = 0, ahead = 0, n0_i = nt_col0(nt_c), ph_i = nt_phase(nt_c);
   long m0_i;
   { int im, ti; long me; m0_i = tile_rows(mt_c, im, ti, me); }
   auto stream_issue = [&]() {
     if (v_iss < 0) return;
-    issue(m0_i, n0_i, ic, smem + st_nxt * STAGE);
+    issue(m0_i, n0_i, ph_i, ic, smem + st_nxt * STAGE);
     st_nxt = (st_nxt + 1 == NS) ? 0 : st_nxt + 1;
     ++ahead;
     if (++ic == nch) {
       int mt, nt;
       ic = 0;
       v_iss = next_tile(v_iss + (int)gridDim.x, mt, nt);
-      if (v_iss >= 0) { int im, ti; long me; m0_i = tile_rows(mt, im, ti, me); n0_i = nt * BN; }
+      if (v_iss >= 0) { int im, ti; long me; m0_i = tile_rows(mt, im, ti, me); n0_i = nt_col0(nt); ph_i = nt_phase(nt); }
     }
   };
 #pragma unroll
@@ -237,7 +282,7 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
   int img, mti;
   long m_end;
   const long m0 = tile_rows(mt_c, img, mti, m_end);
-  const int n0 = nt_c * BN;
+  const int n0 = nt_col0(nt_c), phase = nt_phase(nt_c);
   const unsigned int rows_left = (unsigned int)((m_end - m0) < (long)BM ? (m_end - m0) : (long)BM);
   // the accumulators start from the fp32 residual (register quad = four consecutive channels of a row = one 16-byte load; rows / channels beyond the end
   // read 0): the loads fly while the tile's first chunk lands, and no epilogue waits for memory
@@ -339,11 +384,33 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
       bq[j][g] = (bias && ch < p.N) ? *(const f32x4*)(bias + ch) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
   if (EPI == 0 || EPI == 4) {
-    const sdm_rsrc rs_out = sdm_make_rsrc((float*)p.out + (size_t)m0 * p.ldo, rows_left * (unsigned int)p.ldo * 4u);
+    // UP: the descriptor spans the output row pairs of the tile's own interior grid rows yb .. yl and nothing else (an image may exceed 4 GB, and a
+    // descriptor of 2 GB or more would take the offset SDM_BUF_INVALID for a valid one); ro[i] = byte offset of this lane's output pixel of row block i
+    // behind it, SDM_BUF_INVALID for border rows and rows of the next image
+    unsigned int ro[MT];
+    const float* obase = (const float*)p.out + (size_t)m0 * p.ldo;
+    size_t obytes = (size_t)rows_left * (unsigned int)p.ldo * 4u;
+    if (UP) {
+      const unsigned int q0 = (unsigned int)(m0 - (long)img * p.rows_per_img), wp = (unsigned int)up_wp;
+      const unsigned int yf = q0 / wp, yb = yf > 1u ? yf : 1u;
+      const int py = phase >> 1, px = phase & 1;
+      const size_t img_rows = (size_t)2 * p.up_H, orow = (size_t)2 * p.up_W * p.ldo;      // output rows per image, floats per output row
+      obase = (const float*)p.out + ((size_t)img * img_rows + 2 * (size_t)(yb - 1u)) * orow;
+      const unsigned int ye = (q0 + (unsigned int)BM - 1u) / wp, yl = ye < (unsigned int)p.up_H ? ye : (unsigned int)p.up_H;      // last interior grid row
+      obytes = yl >= yb ? 2 * (size_t)(yl - yb + 1u) * orow * 4 : 0;                      // (the launcher keeps this below SDM_BUF_INVALID)
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const unsigned int row = (unsigned int)((wm * MT + i) * 32 + l31), q = q0 + row;
+        const unsigned int yp = q / wp, xp = q - yp * wp;
+        const bool inside = row < rows_left && yp >= 1u && yp <= (unsigned int)p.up_H && xp >= 1u && xp <= (unsigned int)p.up_W;
+        ro[i] = inside ? (((2u * (yp - yb) + (unsigned int)py) * 2u * (unsigned int)p.up_W + 2u * (xp - 1u) + (unsigned int)px) * (unsigned int)p.ldo) * 4u : SDM_BUF_INVALID;
+      }
+    }
+    const sdm_rsrc rs_out = sdm_make_rsrc(obase, (unsigned int)obytes);
     constexpr bool do_stats = (EPI == 4);
     // channel quad by channel quad, the MT row blocks of a quad back to back: a quad's statistics (per channel over this wave's MT * 32 rows) are complete
     // after its MT stores and need 8 registers, not 64 (the residual is already in the accumulators)
-    const size_t prow = (size_t)img * (p.tiles_per_img * 2) + (size_t)mti * 2 + wm;
+    const size_t prow = UP ? (size_t)img * (p.tiles_per_img * 8) + ((size_t)mti * 4 + phase) * 2 + wm : (size_t)img * (p.tiles_per_img * 2) + (size_t)mti * 2 + wm;
 #pragma unroll
     for (int jg = 0; jg < NT * 4; ++jg) {
       const int j = jg >> 2, g = jg & 3;
@@ -355,8 +422,10 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * g + e] + bq[j][g][e];
-        sdm_buffer_store16(__builtin_bit_cast(u32x4, v), rs_out, ch < p.n_valid ? row * (unsigned int)p.ldo * 4u + (unsigned int)ch * 4u : SDM_BUF_INVALID, 0);
-        if (do_stats && row < rows_left) {
+        const bool live = UP ? ro[i] != SDM_BUF_INVALID : row < rows_left;
+        const unsigned int rbyte = UP ? ro[i] : row * (unsigned int)p.ldo * 4u;
+        sdm_buffer_store16(__builtin_bit_cast(u32x4, v), rs_out, (ch < p.n_valid && (!UP || live)) ? rbyte + (unsigned int)ch * 4u : SDM_BUF_INVALID, 0);
+        if (do_stats && live) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) { t1[e] += v[e]; t2[e] += v[e] * v[e]; }
         }
@@ -467,21 +536,70 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
 // ---- W3 layout of a Linear / 1x1 weight from its canonical K16 tensors (k_hi / k_lo: [Cin_pad/16][Cout_pad][16], w * 2^w_exp = hi + lo).
 //      One thread per 16-byte granule.  Value semantics as derive_conv_weight_f8_kernel (k_conv.h): fp16 high parts UNSCALED (inv_s = 2^-w_exp),
 //      fp8 parts scaled by the layer's own s8 = 2^e8 (largest power of two with max|w| * s8 <= 448). ----
+// UP = 1: the four phase matrices [4 * Cin_pad][Cout_pad] of an up-sampling 3x3 layer (gemm_p3_kernel, UP) from its K16 tensors [Cin_pad/16][9][Cout_pad][16].
+// Phase 2 py + px, tap 2 a + b: source row y + py - 1 + a takes the kernel rows ky with (py + ky - 1) >> 1 == py - 1 + a (py = 0: {0}, {1, 2};
+// py = 1: {0, 1}, {2}), columns alike; hi + lo of those taps are added in fp32 and the sum is split again (high part = fp16 of the sum).
+// K order of a matrix: chunk 4 * (c / 32) + tap, the order of the kernel's K loop.  s8 comes from the largest summed weight (up_phase_absmax_kernel).
+SDM_DEV_INLINE float up_phase_weight(const half_t* __restrict__ k_hi, const half_t* __restrict__ k_lo, int Cout_pad, int phase, int tap, int c, int co) {
+  const int py = phase >> 1, px = phase & 1, a = tap >> 1, b = tap & 1;
+  float s = 0.0f;
+  for (int ky = 0; ky < 3; ++ky) {
+    if (((py + ky + 1) >> 1) - 1 != py - 1 + a) continue;
+    for (int kx = 0; kx < 3; ++kx) {
+      if (((px + kx + 1) >> 1) - 1 != px - 1 + b) continue;
+      const size_t si = (((size_t)(c / 16) * 9 + ky * 3 + kx) * Cout_pad + co) * 16 + (c % 16);
+      s += (float)k_hi[si] + (float)k_lo[si];
+    }
+  }
+  return s;
+}
+// largest |summed weight| over the four phase matrices, in the K16 tensors' unit (w * 2^w_exp) -> *out (float bits, as absmax_f16_kernel)
+__global__ void up_phase_absmax_kernel(const half_t* __restrict__ k_hi, const half_t* __restrict__ k_lo, int Cin_pad, int Cout_pad, unsigned int* __restrict__ out) {
+  const size_t n = (size_t)16 * Cin_pad * Cout_pad;
+  float m = 0.0f;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int co = (int)(i % Cout_pad);
+    size_t t = i / Cout_pad;
+    const int c = (int)(t % Cin_pad);
+    const int pt = (int)(t / Cin_pad);
+    const float v = fabsf(up_phase_weight(k_hi, k_lo, Cout_pad, pt >> 2, pt & 3, c, co));
+    if (v == v && v > m) m = v;
+  }
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s));
+  if ((threadIdx.x & 63) == 0) atomicMax(out, __builtin_bit_cast(unsigned int, m));
+}
+
+template <int UP = 0>
 __global__ void derive_gemm_w3_kernel(const half_t* __restrict__ k_hi, const half_t* __restrict__ k_lo, unsigned char* __restrict__ wd, int Cin_pad, int Cout_pad,
                                       float inv_s, float s8) {
   const size_t per_chunk = (size_t)Cout_pad * 8;
-  const size_t total = (size_t)(Cin_pad / 32) * per_chunk;
+  const int nchunk = UP ? (Cin_pad / 32) * 4 : Cin_pad / 32;                     // chunks per matrix
+  const size_t total = (size_t)(UP ? 4 : 1) * nchunk * per_chunk;
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    const int chunk = (int)(idx / per_chunk);
-    const int rem = (int)(idx - (size_t)chunk * per_chunk);
+    const int gchunk = (int)(idx / per_chunk);
+    const int phase = UP ? gchunk / nchunk : 0, chunk = UP ? (gchunk % nchunk) >> 2 : gchunk, tap = UP ? gchunk & 3 : 0;
+    const int rem = (int)(idx - (size_t)gchunk * per_chunk);
     auto src = [&](int c, int co) { return ((size_t)(c / 16) * Cout_pad + co) * 16 + (c % 16); };
+    // the weight of channel c, column co (to 22 bits) and the fp16 high part the kernel multiplies
+    auto weight = [&](int c, int co, float& hp) -> float {
+      if (UP) {
+        const float w = up_phase_weight(k_hi, k_lo, Cout_pad, phase, tap, c, co) * inv_s;
+        hp = (float)(half_t)w;
+        return w;
+      }
+      const size_t si = src(c, co);
+      const float hi = (float)k_hi[si];
+      hp = (float)(half_t)(hi * inv_s);
+      return (hi + (float)k_lo[si]) * inv_s;
+    };
     unsigned char* dst = wd + idx * 16;
     if (rem < Cout_pad * 4) {
       const int cb16 = rem >> 6, r2 = rem & 63, g = r2 >> 4, co = cb16 * 16 + (r2 & 15);
       const int c0 = chunk * 32 + (g >> 1) * 16 + (g & 1) * 8;
       f16x8 hv;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) hv[e] = (half_t)((float)k_hi[src(c0 + e, co)] * inv_s);
+      for (int e = 0; e < 8; ++e) { float hp; (void)weight(c0 + e, co, hp); hv[e] = (half_t)hp; }
       *(f16x8*)dst = hv;
     } else {
       const int rem2 = rem - Cout_pad * 4;
@@ -490,9 +608,8 @@ __global__ void derive_gemm_w3_kernel(const half_t* __restrict__ k_hi, const hal
 #pragma unroll
       for (int b = 0; b < 16; ++b) {
         const int c = chunk * 32 + (b < 8 ? hh * 8 + b : 16 + hh * 8 + (b - 8));
-        const size_t si = src(c, co);
-        const float hi = (float)k_hi[si], w = (hi + (float)k_lo[si]) * inv_s;
-        const float hp = (float)(half_t)(hi * inv_s);
+        float hp;
+        const float w = weight(c, co, hp);
         const float r = ((part == 0) ? w : (w - hp) * (2048.0f * P3_X8_TRUNC_GAIN)) * s8;
         v[b] = fminf(fmaxf(r, -448.0f), 448.0f);
       }
@@ -529,7 +646,10 @@ SDM_DEV_INLINE void p3_store8(const float (&y)[8], unsigned char* hi_base, unsig
 // fp32 [rows][C] -> P3 (sources whose producer does not emit planes itself).  One wave per 32 rows x 32 channels: lane (row l & 31, half l >> 5) reads its two
 // 8-channel runs (whole 128-byte lines per row over the wave's loads) and writes two hi granules - per store instruction four 256-byte runs - and its 16
 // XL bytes - one contiguous KB per instruction.  Rows beyond `rows` (padding of the last block) are written as zeros.
-__global__ void __launch_bounds__(256) to_p3_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, long rows, int C) {
+// PAD = 1: x is NHWC [N][H][W][C] and the rows are the zero-bordered grid [N][H + 2][W + 2] (the operand of the up-sampling phase convs, gemm_p3_kernel
+// UP): border rows are written as zeros on every call, like the padding rows.
+template <int PAD>
+SDM_DEV_INLINE void to_p3_body(const float* __restrict__ x, unsigned char* __restrict__ out, long rows, int C, int H, int W) {
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
   const long rb = (long)((rows + 31) >> 5), units = rb * (C >> 5);
   unsigned char* xlp = out + p3_rows_pad((size_t)rows) * (size_t)C * 2;
@@ -537,12 +657,19 @@ __global__ void __launch_bounds__(256) to_p3_kernel(const float* __restrict__ x,
     const long b = u / (C >> 5);
     const int ck = (int)(u - b * (C >> 5));
     const long row = b * 32 + r;
+    long srow = row;                             // source row; -1: zeros
+    if (row >= rows) srow = -1;
+    else if (PAD) {
+      const long per = (long)(H + 2) * (W + 2), n = row / per;
+      const int q = (int)(row - n * per), yp = q / (W + 2), xp = q - yp * (W + 2);
+      srow = (yp >= 1 && yp <= H && xp >= 1 && xp <= W) ? (n * H + (yp - 1)) * W + (xp - 1) : -1;
+    }
     float y[2][8];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       f32x4 a = {0.0f, 0.0f, 0.0f, 0.0f}, bq = a;
-      if (row < rows) {
-        const float* src = x + (size_t)row * C + ck * 32 + k * 16 + h * 8;
+      if (srow >= 0) {
+        const float* src = x + (size_t)srow * C + ck * 32 + k * 16 + h * 8;
         a = *(const f32x4*)src; bq = *(const f32x4*)(src + 4);
       }
       y[k][0] = a[0]; y[k][1] = a[1]; y[k][2] = a[2]; y[k][3] = a[3]; y[k][4] = bq[0]; y[k][5] = bq[1]; y[k][6] = bq[2]; y[k][7] = bq[3];
@@ -565,6 +692,11 @@ __global__ void __launch_bounds__(256) to_p3_kernel(const float* __restrict__ x,
     }
     *(u32x4*)(xlp + (((size_t)b * (C >> 5) + ck) << 10) + (h << 9) + (r << 4)) = xo;
   }
+}
+__global__ void __launch_bounds__(256) to_p3_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, long rows, int C) { to_p3_body<0>(x, out, rows, C, 0, 0); }
+// rows = N * (H + 2) * (W + 2)
+__global__ void __launch_bounds__(256) to_p3_pad_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, long rows, int C, int H, int W) {
+  to_p3_body<1>(x, out, rows, C, H, W);
 }
 
 // P3 -> fp32 (tests: what the GEMM's split operands represent, hi + xl * 2^-11)

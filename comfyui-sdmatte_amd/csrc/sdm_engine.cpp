@@ -106,6 +106,7 @@ static OptEntry g_opts[] = {
   {"gemm_p3_attn", 1, 1, "d=64 attention cores write the operand planes of to_out themselves (0: fp32 result + one conversion pass)"},
   {"gemm_p3_persist", 1, 1, "plane-fed GEMM: persistent blocks that prefetch the next tile's first chunk underneath the epilogue (0: one block per tile, n > 1: a grid of n blocks - tests)"},
   {"gemm_p3_ablate", 0, 0, "bench only: 1 no MFMAs, 2 no DMAs behind the prologue, 4 no epilogue (sdm_bench_gemm_p3)"},
+  {"conv_up_phase", 1, 1, "up-sampling 3x3 convs (Upsample2D) as four 2x2-tap phase convs on the plane-fed GEMM (k_gemm.h, UP): 0 off (the 3x3 kernels on the up-sampled image), 1 the launches with at least two 256-row tiles per CU (up_phase_wins: measured), 2 every eligible launch (tests).  0 / non-0 is read when a model is built: the phase matrices are a derived weight layout"},
   {"conv_epi", 4, 4, "F8 kernels' epilogue: 4 register-direct stores + residual as accumulator init, 3 residual init only, 0 LDS-staged"},
   {"conv_xtile", 1, 1, "F8 3x3: cross-tile prefetch by the producer waves"},
   {"conv_f8_tpb", 0, 0, "F8: tiles per block (0 = by queue depth)"},
@@ -396,13 +397,13 @@ static void launch_gemm_f8(const ConvParams& p_in, void* stream) {
 }
 
 // ---- plane-fed GEMM (k_gemm.h): tile = (64 * MT) rows x 128 channels, 4 waves; NS LDS stages (2 stages of the 256-row tile: two blocks per CU) ----
-template <int MT, int EPI>
+template <int MT, int EPI, int UP = 0>
 static void launch_gemm_p3_t(GemmP3Params p, void* stream) {
   constexpr int BM = 64 * MT, NS = 2, SMEM = NS * (BM * 96 + 128 * 128);
   const long rows = p.rows_per_img ? (long)p.rows_per_img : p.M;
   p.tiles_per_img = (int)((rows + BM - 1) / BM);
   p.tiles_m = p.tiles_per_img * (p.rows_per_img ? (int)(p.M / p.rows_per_img) : 1);
-  p.tiles_n = sdm_cdiv(p.N, 128);
+  p.tiles_n = sdm_cdiv(p.N, 128) * (UP ? 4 : 1);      // (UP: the tile id's N part is phase * N tiles + N tile, k_gemm.h)
   unsigned grid;
   if (p.tiles_m >= 8) { p.xcd_chunk = (p.tiles_m + 7) / 8; grid = (unsigned)(8L * p.xcd_chunk * p.tiles_n); }
   else { p.xcd_chunk = 0; grid = (unsigned)(p.tiles_m * p.tiles_n); }
@@ -412,7 +413,7 @@ static void launch_gemm_p3_t(GemmP3Params p, void* stream) {
     const unsigned slots = pp > 1 ? (unsigned)pp : ((unsigned)(device_cus() * ((SMEM <= 80 * 1024) ? 2 : 1)) & ~7u);      // (pp > 1: forced grid, tests)
     if (slots >= 1 && grid > slots) grid = slots;
   }
-  auto k = gemm_p3_kernel<MT, 2, EPI>;
+  auto k = gemm_p3_kernel<MT, 2, EPI, NS, UP>;
   SDM_SET_SMEM(k, SMEM);
 #ifndef SDM_EMU
   if (opt("gemm_p3_ablate") & 256) {      // lab: resident blocks per CU as the runtime sees them
@@ -430,10 +431,10 @@ static void launch_gemm_p3_e(const GemmP3Params& p, int bm, void* stream) {
   else launch_gemm_p3_t<1, EPI>(p, stream);
 }
 // row tile: the largest of 256 / 128 / 64 that still gives every CU a block (the option gemm_p3_tile forces one)
-static int gemm_p3_pick_bm(long M, int N, int rows_per_img) {
+static int gemm_p3_pick_bm(long M, int N, int rows_per_img, int phases = 1) {
   const int forced = opt("gemm_p3_tile");
   if (forced == 256 || forced == 128 || forced == 64) return forced;
-  const long tn = sdm_cdiv(N, 128);
+  const long tn = (long)sdm_cdiv(N, 128) * phases;
   const long imgs = rows_per_img ? M / rows_per_img : 1, rows = rows_per_img ? rows_per_img : M;
   const int cus = device_cus();
   for (int bm : {256, 128}) if (imgs * ((rows + bm - 1) / bm) * tn >= cus) return bm;
@@ -447,6 +448,15 @@ static void launch_gemm_p3(const GemmP3Params& p, int epi, void* stream) {
     case 2: launch_gemm_p3_e<2>(p, bm, stream); break;
     case 3: launch_gemm_p3_e<3>(p, bm, stream); break;
     default: launch_gemm_p3_e<4>(p, bm, stream); break;
+  }
+}
+
+// up-sampling phase convs (k_gemm.h, UP): epilogue 0 (fp32) or 4 (+ statistics)
+static void launch_gemm_p3_up(const GemmP3Params& p, int epi, int bm, void* stream) {
+  if (epi == 4) {
+    if (bm == 256) launch_gemm_p3_t<4, 4, 1>(p, stream); else if (bm == 128) launch_gemm_p3_t<2, 4, 1>(p, stream); else launch_gemm_p3_t<1, 4, 1>(p, stream);
+  } else {
+    if (bm == 256) launch_gemm_p3_t<4, 0, 1>(p, stream); else if (bm == 128) launch_gemm_p3_t<2, 0, 1>(p, stream); else launch_gemm_p3_t<1, 0, 1>(p, stream);
   }
 }
 
@@ -550,6 +560,12 @@ struct ConvL {
   // Linear layers of the split-precision stages also keep the W3 layout of the plane-fed GEMM (k_gemm.h; same f8_exp)
   size_t w3_off = 0, w3_bytes = 0;
   unsigned char* w3 = nullptr;
+  // 3x3 layers behind a nearest x2 up-sample (Upsample2D): the four phase matrices [4 * Cin_pad][Cout_pad] in the W3 layout (k_gemm.h, UP), with
+  // their own e4m3 scale 2^up_exp from the largest SUMMED weight
+  int up = 0;                 // the model runs the layer with ConvArgs::up = 1
+  size_t wup_off = 0, wup_bytes = 0;
+  unsigned char* wup = nullptr;
+  int up_exp = 8;
   size_t w_bytes() const { return (size_t)Cin_pad * ntaps * Cout_pad * 2; }      // K16: each of w and w_lo
   size_t b_bytes() const { return (size_t)Cout_pad * 4; }
 };
@@ -580,8 +596,24 @@ static bool layer_takes_gemm_f8(const ConvL& L) {
 }
 // Linear layers of a split-precision stage whose K splits into 32-channel chunks: W3 copy for the plane-fed GEMM (k_gemm.h)
 static bool layer_takes_w3(const ConvL& L) { return L.ntaps == 1 && L.split && L.Cin_pad % 32 == 0 && L.Cin_pad >= 32; }
+// 3x3 layers of a split-precision stage whose channels split into 32-channel chunks: phase matrices for the up-sampling path (k_gemm.h, UP)
+//   model: the Upsample2D layers, NEXT TO their stage-ordered copy - which of the two a launch takes depends on its size (up_phase_wins), and the
+//   same layer sees every size;  hooks: every eligible layer run with up = 1
+static bool layer_takes_up_phase(const ConvL& L) {
+  return L.ntaps == 9 && L.split && !L.geglu && L.Cin_pad % 32 == 0 && L.Cin_pad >= 32 && conv_f8_enabled() && opt("conv_up_phase") != 0;
+}
+// Which up-sampling launches take the phase path.  Measured per launch at 4 x 1024^2 (profiles/NOTES.md, "Up-sampling convs as phase convs"): launch +
+// plane pre-pass beat the F8 3x3 launch by 1.33 - 1.66x on the five layers with 800 ... 66 000 tiles of 256 rows x 128 channels and lose 13 % on the one
+// with 320 (1280 -> 1280 at 16^2 -> 32^2: 0.63 of one round of the chip's 512 resident blocks, half of its row tiles a quarter full; the 128- and
+// 64-row tiles measured slower still).  The line is drawn at one full round.
+static bool up_phase_wins(int N, int H, int W, int Cout_pad) {
+  if (opt("conv_up_phase") >= 2) return true;
+  const long tiles = (long)N * sdm_cdiv((H + 2) * (W + 2), 256) * 4 * sdm_cdiv(Cout_pad, 128);
+  return tiles >= 2L * device_cus();
+}
 // sizes of the derived copies the caller wants and the layer can carry (0: none), and which of the two layouts w_dma holds
-static void layer_choose_layouts(ConvL& L, bool want_dma3x3, bool want_gemm_f8, bool want_w3) {
+static void layer_choose_layouts(ConvL& L, bool want_dma3x3, bool want_gemm_f8, bool want_w3, bool want_up_phase = false) {
+  if (want_up_phase && layer_takes_up_phase(L)) L.wup_bytes = (size_t)16 * L.Cin_pad * L.Cout_pad * 4;
   if (want_dma3x3 && layer_takes_dma3x3(L)) {
     L.wdma_bytes = L.w_bytes() * (L.split ? 2 : 1);
     L.f8 = (L.split && L.Cin_pad % 32 == 0 && conv_f8_enabled()) ? 1 : 0;      // same bytes, fp8-residual layout
@@ -751,18 +783,19 @@ struct Builder {
   size_t doff = 0;         // derived region (behind the canonical one): DMA-ordered / fp8-residual copies, rebuilt by sdm_finalize_weights
   int stage = 0;           // sdm_precise_stage of the layers being built
   explicit Builder(sdm_ctx* c) : e(c) {}
-  int conv(const std::string& name, int ntaps, int I_pad16_src, int O, int geglu = 0) {
+  int conv(const std::string& name, int ntaps, int I_pad16_src, int O, int geglu = 0, int up = 0) {
     ConvL L = make_layer(name, ntaps, I_pad16_src, O, geglu, e->cfg.precise_mask & stage);
-    L.stage = stage;
+    L.stage = stage; L.up = up;
     L.w_off = woff; woff += rupz(L.w_bytes(), 256);
     L.b_off = woff; woff += rupz(L.b_bytes(), 256);
     if (L.split) { L.wlo_off = woff; woff += rupz(L.w_bytes(), 256); }
     // The model's own policy on top of what a layer can carry (layer_choose_layouts).  The fp8-residual GEMM copy has a threshold on K: a GEMM
     // has no operand reuse across taps, so the producer waves (one 32 KB activation tile converted per 1024 MFMA cycles) set the pace: measured
     // against the 4-wave kernel x1.2-1.5 for K = 1280 ... 5120, x0.84-1.0 for K <= 640 (profiles/r02_gemm_f8_ab.txt)
-    layer_choose_layouts(L, L.split || opt("conv_dma_all") != 0, L.Cin_pad >= gemm_f8_min_k(), conv_f8_enabled() && opt("gemm_p3") != 0);
+    layer_choose_layouts(L, L.split || opt("conv_dma_all") != 0, L.Cin_pad >= gemm_f8_min_k(), conv_f8_enabled() && opt("gemm_p3") != 0, up != 0);
     if (L.wdma_bytes) { L.wdma_off = doff; doff += rupz(L.wdma_bytes, 256); }
     if (L.w3_bytes) { L.w3_off = doff; doff += rupz(L.w3_bytes, 256); }
+    if (L.wup_bytes) { L.wup_off = doff; doff += rupz(L.wup_bytes, 256); }
     e->convs.push_back(L);
     return (int)e->convs.size() - 1;
   }
@@ -784,8 +817,8 @@ struct Builder {
     e->slot_order.push_back(key);
   }
   // plain conv / linear layer "<p>.weight"/"<p>.bias"
-  int conv_named(const std::string& p, int ntaps, int I, int O, bool bias = true, int ci_off = 0, int Ipad = 0) {
-    int id = conv(p, ntaps, Ipad ? Ipad : I, O);
+  int conv_named(const std::string& p, int ntaps, int I, int O, bool bias = true, int ci_off = 0, int Ipad = 0, int up = 0) {
+    int id = conv(p, ntaps, Ipad ? Ipad : I, O, 0, up);
     if (ntaps == 9) slot(p + ".weight", SLOT_CONV_W, id, {O, I, 3, 3}, 0, ci_off);
     else slot(p + ".weight", SLOT_CONV_W, id, {O, I}, 0, ci_off);
     if (bias) slot(p + ".bias", SLOT_CONV_B, id, {O});
@@ -908,7 +941,7 @@ static void build_model(sdm_ctx* e) {
     for (int j = 0; j < c.vae_layers_per_block + 1; ++j)
       e->dec_res[i].push_back(B.resnet("vae.decoder.up_blocks." + S(i) + ".resnets." + S(j), j == 0 ? cprev : co, co, 0));
     cprev = co;
-    if (i < 3) e->dec_up.push_back(B.conv_named("vae.decoder.up_blocks." + S(i) + ".upsamplers.0.conv", 9, co, co));
+    if (i < 3) e->dec_up.push_back(B.conv_named("vae.decoder.up_blocks." + S(i) + ".upsamplers.0.conv", 9, co, co, true, 0, 0, 1));
   }
   e->dec_norm_out = B.norm_named("vae.decoder.conv_norm_out", vc[0]);
   e->dec_conv_out = B.conv_named("vae.decoder.conv_out", 9, vc[0], 3);
@@ -962,7 +995,7 @@ static void build_model(sdm_ctx* e) {
       e->u_up_res[i].push_back(B.resnet("unet.up_blocks." + S(i) + ".resnets." + S(j), resnet_in + res_skip, output_channel, te));
       if (i > 0) e->u_up_tf[i].push_back(B.transformer("unet.up_blocks." + S(i) + ".attentions." + S(j), output_channel, c.unet_heads[3 - i], ctx));
     }
-    if (i < 3) e->u_up_us.push_back(B.conv_named("unet.up_blocks." + S(i) + ".upsamplers.0.conv", 9, output_channel, output_channel));
+    if (i < 3) e->u_up_us.push_back(B.conv_named("unet.up_blocks." + S(i) + ".upsamplers.0.conv", 9, output_channel, output_channel, true, 0, 0, 1));
   }
   e->u_norm_out = B.norm_named("unet.conv_norm_out", uc[0]);
   e->u_conv_out = B.conv_named("unet.conv_out", 9, uc[0], c.unet_out_channels);
@@ -1154,7 +1187,68 @@ static void conv_shape_params(ConvParams& p, const ConvL& L, const T& in0, const
   p.f8_hint = (L.f8 && L.w_dma && p.in_f32 && L.ntaps == 9 && stride == 1) ? 1 : 0;
 }
 
+// Upsample2D on the phase path (k_gemm.h, UP): the layer keeps phase matrices (ConvL::wup), fp32 in and out, nothing fused but bias and statistics
+static bool conv_up_phase_ok(const ConvL& L, const ConvArgs& a) {
+  if (!L.wup_bytes || a.up != 1 || a.stride != 1 || a.pad_mode != 0 || a.in1 || a.res || a.bias_sel || a.bias_override || a.gn_scale || a.force_cfg >= 0) return false;
+  if (a.in0->f32 != 1 || a.out->f32 != 1 || a.out_scale != 1.0f || a.out_ch_off != 0 || a.in0->C != L.Cin_pad || a.out->C % 4) return false;
+  const int nv = a.cout_valid >= 0 ? a.cout_valid : std::min(L.Cout_pad, a.out->C);
+  if (nv % 32 || nv > L.Cout_pad) return false;
+  if (!up_phase_wins(a.in0->N, a.in0->H, a.in0->W, L.Cout_pad)) return false;
+  const size_t rows = (size_t)a.in0->N * (a.in0->H + 2) * (a.in0->W + 2);
+  // one buffer descriptor over each operand plane, one over the output rows of a 256-row tile: both short of the offset that marks a dropped access
+  const size_t tile_out = (size_t)2 * (256 / (a.in0->W + 2) + 2) * 2 * a.in0->W * a.out->C * 4;
+  return p3_rows_pad(rows) * (size_t)L.Cin_pad * 2 < SDM_BUF_INVALID && tile_out < SDM_BUF_INVALID && rows < ((size_t)1 << 31);
+}
+static int op_conv_up_phase(sdm_ctx* e, const ConvL& L, const ConvArgs& a) {
+  const T& in = *a.in0;
+  T* out = a.out;
+  T xp = talloc(e, in.N, in.H + 2, in.W + 2, in.C, kFmtP3);
+  GemmP3Params p;
+  memset(&p, 0, sizeof(p));
+  p.M = xp.rows(); p.K = L.Cin_pad; p.rows_per_img = (in.H + 2) * (in.W + 2);
+  p.up_H = in.H; p.up_W = in.W;
+  p.a_hi = (const half_t*)xp.p; p.a_xl = (const unsigned char*)xp.p + p3_rows_pad((size_t)p.M) * p.K * 2;
+  p.w = L.wup; p.N = L.Cout_pad; p.bias = L.b;
+  p.out = out->p; p.ldo = out->C; p.n_valid = a.cout_valid >= 0 ? a.cout_valid : std::min(L.Cout_pad, out->C);
+  p.sa = 127 - 11; p.sb = 127 - L.up_exp;
+  const int bm = gemm_p3_pick_bm(p.M, p.N, p.rows_per_img, 4);
+  const int epi = out->want_stats ? 4 : 0;
+  if (epi == 4) {
+    out->srows = sdm_cdiv(p.rows_per_img, bm) * 8;                  // partial row (M tile, phase, wave row)
+    T sb = talloc(e, 1, 1, 1, (int)((size_t)in.N * out->srows * out->C * 2), 1);
+    out->soff = sb.off; out->sbytes = sb.bytes; out->stats = (float*)sb.p;
+    p.stats = out->stats;
+  }
+  if (e->dry) { tfree(e, xp); return 0; }
+  char d[256];
+  d[0] = 0;
+  if (e->prof_on) snprintf(d, sizeof(d), "%s N=%d H=%d W=%d C=%d bordered grid", L.name.c_str(), in.N, in.H, in.W, in.C);
+  prof_begin(e, "to_p3", 0, (double)in.rows() * in.C * 4 + (double)xp.rows() * in.C * 3, d);
+  const long units = ((xp.rows() + 31) / 32) * (in.C / 32);
+  SDM_LAUNCH(to_p3_pad_kernel, dim3((unsigned)std::min<long>((units + 3) / 4, 1 << 20)), dim3(256), 0, e->stream, (const float*)in.p, (unsigned char*)xp.p, xp.rows(), in.C,
+             in.H, in.W);
+  prof_end(e);
+  // EXECUTED flops: four taps per output pixel (the 3x3 form of the same layer counts nine)
+  const double flops = 2.0 * (double)out->rows() * L.O * L.I * 4;
+  const double bytes = (double)xp.rows() * p.K * 3 + (double)out->rows() * p.n_valid * 4 + (double)16 * p.K * p.N * 4;
+  if (e->prof_on) {
+    snprintf(d, sizeof(d), "%s N=%d Hout=%d Wout=%d Cin=%d Cout=%d up=1 phases epi=%d bm=%d", L.name.c_str(), in.N, out->H, out->W, L.Cin_pad, L.O, epi, bm);
+    prof_begin(e, "conv_up_phase", flops, bytes, d);
+  } else {
+    prof_begin(e, "conv", flops, bytes);
+  }
+  count_kernel("conv_up_phase");
+  launch_gemm_p3_up(p, epi, bm, e->stream);
+#ifndef SDM_EMU
+  { const hipError_t le = hipGetLastError(); if (le != hipSuccess) SDM_FAIL(e, SDM_ERR_HIP, "conv %s: launch failed: %s", L.name.c_str(), hipGetErrorString(le)); }
+#endif
+  prof_end(e);
+  tfree(e, xp);
+  return 0;
+}
+
 static int op_conv(sdm_ctx* e, const ConvL& L, const ConvArgs& a) {
+  if (conv_up_phase_ok(L, a)) return op_conv_up_phase(e, L, a);
   ConvParams p;
   memset(&p, 0, sizeof(p));
   conv_shape_params(p, L, *a.in0, a.in1, *a.out, a.stride);
@@ -2487,6 +2581,7 @@ int sdm_create(sdm_ctx** out, int device_id, const sdm_config* cfg) {
     if (L.split) L.w_lo = (half_t*)(e->warena + L.wlo_off);
     if (L.wdma_bytes) L.w_dma = (half_t*)(e->warena + e->canon_bytes + L.wdma_off);
     if (L.w3_bytes) L.w3 = e->warena + e->canon_bytes + L.w3_off;
+    if (L.wup_bytes) L.wup = e->warena + e->canon_bytes + L.wup_off;
   }
   for (auto& n : e->norms) { n.g = (float*)(e->warena + n.g_off); n.b = (float*)(e->warena + n.b_off); }
   for (auto& t : e->tembs) {
@@ -2668,12 +2763,19 @@ static int fold_cross_kv(sdm_ctx* e) {
 static int derive_layers(sdm_ctx* e, std::vector<ConvL*>& layers) {
   std::vector<ConvL*> f8;
   for (ConvL* L : layers) if ((L->w_dma && L->f8) || L->w3) f8.push_back(L);
+  const size_t n_own = f8.size();                                    // behind them: the layers with phase matrices, scaled by their largest summed weight
+  for (ConvL* L : layers) if (L->wup) f8.push_back(L);
   if (!f8.empty()) {
     const size_t tb = rupz(f8.size() * 4, 256);
     if (ensure_buf(e, &e->stage, &e->stage_bytes, std::max(tb, (size_t)1 << 20)) != 0) return SDM_ERR_NOMEM;
     SDM_CHECK_DEV(e, dev_memset(e->stage, 0, tb, e->stream));
     for (size_t i = 0; i < f8.size(); ++i) {
       const size_t n = (size_t)f8[i]->Cin_pad * f8[i]->ntaps * f8[i]->Cout_pad;
+      if (i >= n_own) {
+        SDM_LAUNCH(up_phase_absmax_kernel, dim3(2048), dim3(256), 0, e->stream, (const half_t*)f8[i]->w, (const half_t*)f8[i]->w_lo, f8[i]->Cin_pad, f8[i]->Cout_pad,
+                   (unsigned int*)e->stage + i);
+        continue;
+      }
       SDM_LAUNCH(absmax_f16_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, e->stream, (const half_t*)f8[i]->w, n,
                  (unsigned int*)e->stage + i);
     }
@@ -2688,13 +2790,16 @@ static int derive_layers(sdm_ctx* e, std::vector<ConvL*>& layers) {
         while (ldexpf(wmax, ex) > 448.0f) --ex;                   // guard the rounding of log2f
         ex = std::max(-60, std::min(60, ex));
       }
-      f8[i]->f8_exp = ex;
+      if (i >= n_own) f8[i]->up_exp = ex; else f8[i]->f8_exp = ex;
     }
   }
   for (ConvL* L : layers) {
     if (L->w3)
-      SDM_LAUNCH(derive_gemm_w3_kernel, dim3((unsigned)std::min<size_t>(((size_t)L->Cin_pad * L->Cout_pad / 4 + 255) / 256, 65535)), dim3(256), 0, e->stream,
+      SDM_LAUNCH(derive_gemm_w3_kernel<0>, dim3((unsigned)std::min<size_t>(((size_t)L->Cin_pad * L->Cout_pad / 4 + 255) / 256, 65535)), dim3(256), 0, e->stream,
                  (const half_t*)L->w, (const half_t*)L->w_lo, L->w3, L->Cin_pad, L->Cout_pad, ldexpf(1.0f, -L->w_exp), ldexpf(1.0f, L->f8_exp));
+    if (L->wup)
+      SDM_LAUNCH(derive_gemm_w3_kernel<1>, dim3((unsigned)std::min<size_t>(((size_t)L->Cin_pad * L->Cout_pad * 4 + 255) / 256, 65535)), dim3(256), 0, e->stream,
+                 (const half_t*)L->w, (const half_t*)L->w_lo, L->wup, L->Cin_pad, L->Cout_pad, ldexpf(1.0f, -L->w_exp), ldexpf(1.0f, L->up_exp));
     if (!L->w_dma) continue;
     const size_t total = (size_t)L->Cin_pad * L->ntaps * L->Cout_pad;
     if (L->f8)

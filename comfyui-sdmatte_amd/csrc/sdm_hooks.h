@@ -16,20 +16,22 @@ struct RestoreInt { int& s; int v; ~RestoreInt() { s = v; } };      // RestoreIn
 // A layer outside the model: shape and layouts by the rules of the model's layers (make_layer / layer_choose_layouts), buffers of its own (zeroed,
 // as the weight arena is), fp32 weights and bias (device) packed and derived by the model's path.  Released after the engine stream has drained.
 struct TempLayer {
-  enum { kDma = 1, kW3 = 2 };      // layouts wanted: the stage-ordered 3x3 / fp8-residual GEMM copy of an eligible layer; W3
+  enum { kDma = 1, kW3 = 2, kUp = 4 };      // layouts wanted: the stage-ordered 3x3 / fp8-residual GEMM copy of an eligible layer; W3; the phase matrices of an up-sampling 3x3 layer
   sdm_ctx* e;
   ConvL L;
-  DevBuf w, w_lo, b, w_dma, w3;
+  DevBuf w, w_lo, b, w_dma, w3, wup;
   explicit TempLayer(sdm_ctx* c) : e(c) {}
   ~TempLayer() { dev_sync(e->stream); }      // (then the buffers go)
   int init(const char* name, int ntaps, int I, int O, int geglu, int split, int layouts, const float* wsrc, const float* bias) {
     L = make_layer(name, ntaps, I, O, geglu, split);
-    layer_choose_layouts(L, layouts & kDma, layouts & kDma, layouts & kW3);
+    layer_choose_layouts(L, layouts & kDma, layouts & kDma, layouts & kW3, layouts & kUp);
     SDM_CHECK_DEV(e, w.alloc0(L.w_bytes(), e->stream));
     SDM_CHECK_DEV(e, b.alloc0(L.b_bytes(), e->stream));
     if (L.split) SDM_CHECK_DEV(e, w_lo.alloc0(L.w_bytes(), e->stream));
     if (L.wdma_bytes) SDM_CHECK_DEV(e, w_dma.alloc0(L.wdma_bytes, e->stream));
     if (L.w3_bytes) SDM_CHECK_DEV(e, w3.alloc0(L.w3_bytes, e->stream));
+    if (L.wup_bytes) SDM_CHECK_DEV(e, wup.alloc0(L.wup_bytes, e->stream));
+    L.wup = (unsigned char*)wup.p;
     L.w = (half_t*)w.p; L.b = (float*)b.p; L.w_lo = (half_t*)w_lo.p; L.w_dma = (half_t*)w_dma.p; L.w3 = (unsigned char*)w3.p;
     pack_layer_weight(e, L, wsrc, O, I, 0, 0, 1.0f);
     if (bias) pack_layer_bias(e, L, bias, O, 0);
@@ -76,7 +78,7 @@ int sdm_op_conv_ex(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1,
   if (C0 % 16 || C1 % 16) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv: channel counts must be multiples of 16");
   if (split && !in_f32) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv_ex: split precision takes fp32 activations");
   TempLayer tl(e);      // every layout a layer of this shape can carry but W3: the conv launchers never read it
-  TRY(tl.init("op", ntaps, C0 + C1, O, geglu, split, TempLayer::kDma, w, bias));
+  TRY(tl.init("op", ntaps, C0 + C1, O, geglu, split, TempLayer::kDma | (up ? TempLayer::kUp : 0), w, bias));
   const ConvL& L = tl.L;
   int Ho = Hin << up, Wo = Win << up;
   if (stride == 2) { Ho /= 2; Wo /= 2; }
@@ -148,6 +150,29 @@ int sdm_op_gemm_p3(sdm_ctx* e, const float* x, int N, int H, int W, int K, const
     if (planes) tfree(e, to);
     else if (to.sbytes) { tfree_raw(e, to.soff, to.sbytes); to.sbytes = 0; }
     tfree(e, xp);
+    return 0;
+  });
+}
+
+/* Upsample2D (nearest x2 + 3x3 conv, split precision, fp32 NHWC in and out) with the consumer's GroupNorm statistics, as the model's up-sampling layers run
+ * it: `out` [N][2H][2W][O], `stats` [N][*srows][O][2] partial {sum, sumsq} rows (at most 8 * ceil((H + 2)(W + 2) / 64) + 4 * ceil(H / 2) * ceil(W / 4) rows per image).  C % 32 == 0 and
+ * O % 32 == 0: the phase path (k_gemm.h, UP) where the model would take it (option conv_up_phase: 1 by launch size, 2 always, 0 never). */
+int sdm_op_conv_up_stats(sdm_ctx* e, const float* x, int N, int H, int W, int C, const float* w, const float* bias, int O, float* out, float* stats, int* srows) {
+  if (e) dev_use(e->device);
+  if (!e || !x || !w || !out || !stats || !srows) return SDM_ERR_INVALID;
+  if (C % 32 || O % 32) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv_up_stats: C %% 32 and O %% 32 required");
+  TempLayer tl(e);
+  TRY(tl.init("op_up", 9, C, O, 0, 1, TempLayer::kDma | TempLayer::kUp, w, bias));
+  return run_two_pass(e, [&]() -> int {
+    T tin = view(x, N, H, W, C, 1), to = view(out, N, 2 * H, 2 * W, O, 1);
+    to.want_stats = true;
+    ConvArgs a; a.in0 = &tin; a.out = &to; a.up = 1;
+    TRY(op_conv(e, tl.L, a));
+    if (!e->dry) {
+      SDM_CHECK_DEV(e, dev_memcpy_d2d(stats, to.stats, (size_t)N * to.srows * O * 2 * 4, e->stream));
+      *srows = to.srows;
+    }
+    if (to.sbytes) { tfree_raw(e, to.soff, to.sbytes); to.sbytes = 0; }
     return 0;
   });
 }

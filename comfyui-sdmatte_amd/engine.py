@@ -84,7 +84,7 @@ EXPORTS = [
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
-    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
+    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias",
     "sdm_set_option", "sdm_get_option", "sdm_reset_options", "sdm_option_name", "sdm_option_help", "sdm_kernel_counts", "sdm_kernel_counts_reset",
 ]
@@ -139,6 +139,7 @@ class Bindings:
             "sdm_op_conv_ex": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32,
                                      f32, i32, i32, vp, vp, f32, i32, i32]),
             "sdm_op_gemm_p3": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, f32, i32, vp, vp, C.POINTER(i32)]),
+            "sdm_op_conv_up_stats": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, C.POINTER(i32)]),
             "sdm_debug_run_layer": (i32, [vp, C.c_char_p, vp, i32, i32, i32, vp, i32]),
             "sdm_debug_set_input_cmask": (i32, [vp, vp]),
             "sdm_debug_temb_row": (i32, [vp, i32, i32, vp, vp, i32]),
@@ -784,6 +785,21 @@ class Engine:
                                             int(gn[3]) if gn is not None else 32, int(gn[4]) if gn is not None else 0),
                     "sdm_op_conv_ex")
         return out[..., :Creal]
+
+    def op_conv_up_stats(self, x, w, bias=None):
+        """Test hook: Upsample2D (nearest x2 + 3x3 conv, split precision) on x fp32 [N,H,W,C] with the consumer's GroupNorm statistics, as the model's
+        up-sampling layers run it -> (out fp32 [N,2H,2W,O], stats [N,srows,O,2] partial {sum, sumsq} rows)."""
+        N, H, W_, Cin = x.shape
+        O = w.shape[0]
+        x = x.float().contiguous(); w = w.float().contiguous()
+        b = bias.float().contiguous() if bias is not None else None
+        out = torch.empty(N, 2 * H, 2 * W_, O, dtype=torch.float32, device=x.device)
+        srows_max = 8 * (((H + 2) * (W_ + 2) + 63) // 64) + 4 * ((H + 1) // 2) * ((W_ + 3) // 4)      # phase path; any 3x3 tile (conv_up_phase = 0)
+        stats = torch.zeros(N * srows_max * O * 2, dtype=torch.float32, device=x.device)
+        srows = C.c_int(0)
+        self._check(self.lib.sdm_op_conv_up_stats(self.h, _ptr(x), N, H, W_, Cin, _ptr(w), _ptr(b), O, _ptr(out), _ptr(stats), C.byref(srows)),
+                    "sdm_op_conv_up_stats")
+        return out, stats[:N * srows.value * O * 2].view(N, srows.value, O, 2)
 
     def op_gemm_p3(self, x, w, bias=None, mode=0, res=None, ln=None, lo_cols=-1):
         """Test hook: the plane-fed GEMM (k_gemm.h) on x fp32 [N,H,W,K].  mode 0 fp32 (+res), 1 GEGLU, 3 planes (+res), 4 fp32 + statistics -> (out, stats[N,srows,O,2]),

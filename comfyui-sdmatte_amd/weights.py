@@ -217,3 +217,22 @@ def synthetic_state_dict(cfg: SDMatteConfig, seed: int = 0, gain: float = 1.0):
             t = torch.randn(shape, generator=g) * (gain / fan_in ** 0.5)
         sd[k] = t.contiguous()
     return sd
+
+
+def up_phase_weights(w):
+    """The four 2x2-tap phase kernels of an Upsample2D layer (nearest x2, then 3x3 conv with zero padding 1), as the engine derives them from
+    the layer's 3x3 weight (csrc/k_gemm.h, derive_gemm_w3_kernel<1>).  w: [O, I, 3, 3] -> [2, 2, O, I, 2, 2] indexed [py, px, o, i, a, b]:
+    output pixel (2y + py, 2x + px) = sum over a, b of  w2[py, px, :, :, a, b] . x[y + py - 1 + a, x + px - 1 + b]  (x zero outside the image).
+    Kernel row ky of output row 2y + py reads up-sampled row 2y + py + ky - 1 = source row y + floor((py + ky - 1) / 2): the taps that fall on
+    one source pixel are added."""
+    import torch
+    O, I = w.shape[:2]
+    w2 = torch.zeros(2, 2, O, I, 2, 2, dtype=w.dtype)
+    for py in range(2):
+        for px in range(2):
+            for ky in range(3):
+                for kx in range(3):
+                    a = (py + ky - 1) // 2 - (py - 1)
+                    b = (px + kx - 1) // 2 - (px - 1)
+                    w2[py, px, :, :, a, b] += w[:, :, ky, kx]
+    return w2

@@ -415,6 +415,11 @@ float sdm_bench_gemm_p3(sdm_ctx* ctx, long M, int K, int O, int epi_flags, int i
  * block, channel) {sum, sumsq} rows of the consumer's GroupNorm into `stats` ([N][*srows][O][2] floats; size it for 2 * ceil(H*W / 64) rows). */
 int sdm_op_gemm_p3(sdm_ctx* ctx, const float* x, int N, int H, int W, int K, const float* w, const float* bias, int O, int mode, const float* res,
                    const float* ln_gamma, const float* ln_beta, float ln_eps, int lo_cols, void* out, float* stats, int* srows);
+/* Test hook: Upsample2D (nearest x2 + 3x3 conv, split precision) on x fp32 NHWC [N][H][W][C] with the consumer's GroupNorm statistics, as the model's
+ * up-sampling layers run it: out fp32 [N][2H][2W][O], stats [N][*srows][O][2] partial {sum, sumsq} rows (room for 8 * ceil((H + 2)(W + 2) / 64) + 4 * ceil(H / 2) * ceil(W / 4)
+ * rows per image).  C % 32 == 0, O % 32 == 0.  Takes the phase path where the model would (option conv_up_phase: 1 by launch size, 2 always, 0 never: the 3x3 kernels). */
+int sdm_op_conv_up_stats(sdm_ctx* ctx, const float* x, int N, int H, int W, int C, const float* w, const float* bias, int O, float* out, float* stats,
+                         int* srows);
 /* Test hooks for the exact algebraic folds done at load time (cross-attention K|V fold of aux_conv_in, logit scale in to_q,
  * time/opacity/bbox embedding constants in the conv1 bias tables): run one packed layer by name on an fp32 NHWC input
  * (DEVICE pointers; channel count = the layer's padded input channels), and read one folded bias row (HOST output). */
