@@ -23,6 +23,7 @@
 #include "k_guided.h"
 #include "k_roi.h"
 #include "k_canvas.h"
+#include "k_boxes.h"
 #include "../../include/sdmatte.h"
 
 #include <algorithm>
@@ -3267,6 +3268,124 @@ int sdm_clean_mask(sdm_ctx* e, const float* mask, int B, int H, int W, float thr
       }
     }
     if (label_a || stage_b) { tfree(e, sel); tfree(e, area); tfree(e, root); tfree(e, label); }
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// a box per subject, and the node call over a list of boxes (k_boxes.h)
+// ------------------------------------------------------------------------------------------------
+static_assert(SDM_BX_SLOTS == SDM_BOXES_MAX - 1 && SDM_BX_LIST == SDM_BOXES_MAX_TOTAL, "box limits");
+
+/* The label, root and area planes (4 bytes per pixel each) and the state (SDM_BX_STRIDE ints per image) live in the activation arena.
+ * 8 + 2 (max_boxes - 1) launches, whatever else the arguments are. */
+int sdm_subject_boxes(sdm_ctx* e, const float* plane, int B, int H, int W, float roi_threshold, int min_area, int max_boxes, int margin_px, int margin_pct,
+                      int square, int32_t* boxes, int32_t* count, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !plane || !boxes) return SDM_ERR_INVALID;
+  TRY(roi_check(e, "subject boxes", B, H, W, roi_threshold, margin_px, margin_pct, square));
+  if (min_area < 0 || min_area > SDM_FG_MAX_PIXELS) SDM_FAIL(e, SDM_ERR_INVALID, "subject boxes: min_area = %d outside 0 .. %d", min_area, SDM_FG_MAX_PIXELS);
+  if (max_boxes < 1 || max_boxes > SDM_BOXES_MAX) SDM_FAIL(e, SDM_ERR_INVALID, "subject boxes: max_boxes = %d outside 1 .. %d", max_boxes, SDM_BOXES_MAX);
+  const size_t px = (size_t)B * H * W;
+  const int K = max_boxes;
+  IoSpan in[] = {{(void*)plane, px * 4}}, outs[] = {{boxes, (size_t)B * K * 20}, {count, count ? (size_t)B * 4 : 0}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_plane = (const float*)in[0].p; int* d_boxes = (int*)outs[0].p; int* d_count = (int*)outs[1].p;
+    T label = talloc(e, B, H, W, 1, 1), root = talloc(e, B, H, W, 1, 1), area = talloc(e, B, H, W, 1, 1), state = talloc(e, B, 1, 1, SDM_BX_STRIDE, 1);
+    if (!e->dry) {
+      const int chunks = B * sdm_cdiv(H * W, SDM_CC_PX);
+      const int vec = (H * W) % 4 == 0 ? 1 : 0;
+      const dim3 rgrid((unsigned)(B * sdm_cdiv(H * W, SDM_ROI_PX))), one((unsigned)sdm_cdiv(B, 64));
+      const int* d_root = (const int*)root.p; int* d_state = (int*)state.p;
+      op_cc_label(e, d_plane, B, H, W, roi_threshold, false, (int*)label.p, (int*)root.p, (int*)area.p, nullptr, nullptr);
+      prof_begin(e, "boxes_init", 0, (double)B * SDM_BX_STRIDE * 4);
+      count_kernel("boxes_init");
+      SDM_LAUNCH(boxes_init_kernel, dim3((unsigned)sdm_cdiv(B * SDM_BX_STRIDE, 256)), dim3(256), 0, e->stream, d_state, B);
+      prof_end(e);
+      for (int k = 0; k < K - 1; ++k)
+        for (int phase = 0; phase < 2; ++phase) {
+          prof_begin(e, "boxes_rank", 0, (double)px * 4);
+          count_kernel("boxes_rank");
+          SDM_LAUNCH(boxes_rank_kernel, dim3((unsigned)chunks), dim3(256), 0, e->stream, d_root, (const int*)area.p, B, H, W, k, phase, min_area, vec, d_state);
+          prof_end(e);
+        }
+      prof_begin(e, "boxes_reduce", 0, (double)px * 4);
+      count_kernel("boxes_reduce");
+      if (W % 4 == 0) SDM_LAUNCH((boxes_reduce_kernel<true>), rgrid, dim3(256), 0, e->stream, d_root, d_state, B, H, W);
+      else SDM_LAUNCH((boxes_reduce_kernel<false>), rgrid, dim3(256), 0, e->stream, d_root, d_state, B, H, W);
+      prof_end(e);
+      prof_begin(e, "boxes_own", 0, (double)B * SDM_BX_STRIDE * 4);
+      count_kernel("boxes_own");
+      SDM_LAUNCH(boxes_own_kernel, one, dim3(64), 0, e->stream, d_state, B, H, W, margin_px, margin_pct, square);
+      prof_end(e);
+      prof_begin(e, "boxes_rest", 0, (double)px * 4);
+      count_kernel("boxes_rest");
+      if (W % 4 == 0) SDM_LAUNCH((boxes_rest_kernel<true>), rgrid, dim3(256), 0, e->stream, d_root, d_state, B, H, W);
+      else SDM_LAUNCH((boxes_rest_kernel<false>), rgrid, dim3(256), 0, e->stream, d_root, d_state, B, H, W);
+      prof_end(e);
+      prof_begin(e, "boxes_finalize", 0, (double)B * (SDM_BX_STRIDE * 4 + K * 20 + 4));
+      count_kernel("boxes_finalize");
+      SDM_LAUNCH(boxes_finalize_kernel, one, dim3(64), 0, e->stream, (const int*)d_state, d_boxes, d_count, B, H, W, K, margin_px, margin_pct, square);
+      prof_end(e);
+    }
+    tfree(e, state); tfree(e, area); tfree(e, root); tfree(e, label);
+    return 0;
+  });
+}
+
+/* sdm_apply_matte_node with a model batch of N boxes instead of B frames: forward_impl's node path with the list (an arena tensor of both passes, sanitised
+ * on the device) in the place of the frame.  The host knows N, so the sizing pass never sees a data-dependent size. */
+int sdm_apply_matte_boxes(sdm_ctx* e, const float* image, const float* trimap, int B, int H, int W, int S, int is_transparent, const int32_t* boxes, int N,
+                          int output_mode, int mask_refine, double trimap_constraint, float* alpha, float* matted, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !trimap || !boxes || !alpha || !matted) return SDM_ERR_INVALID;
+  if (!e->finalized) SDM_FAIL(e, SDM_ERR_STATE, "weights not finalised: call sdm_load_tensor(...) and sdm_finalize_weights first");
+  if (output_mode < 0 || output_mode > 2) SDM_FAIL(e, SDM_ERR_INVALID, "unknown output mode %d", output_mode);
+  if (N < 1 || N > SDM_BOXES_MAX_TOTAL) SDM_FAIL(e, SDM_ERR_INVALID, "apply matte boxes: N = %d outside 1 .. %d", N, SDM_BOXES_MAX_TOTAL);
+  if (S <= 0 || S % 64) SDM_FAIL(e, SDM_ERR_INVALID, "inference size must be a positive multiple of 64 (got %dx%d)", S, S);
+  TRY(roi_check(e, "apply matte boxes", B, H, W, 0.0f, 0, 0, 0));
+  std::vector<int32_t> it((size_t)N, is_transparent ? 1 : 0);
+  NodeTail tail; tail.output_mode = output_mode; tail.mask_refine = mask_refine ? 1 : 0; tail.c = trimap_constraint;
+  const size_t px = (size_t)B * H * W;
+  IoSpan in[] = {{(void*)image, px * 12}, {(void*)trimap, px * 4}, {(void*)boxes, (size_t)N * 20}};
+  IoSpan outs[] = {{alpha, px * 4}, {matted, px * 4 * tail.channels()}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_img = (const float*)in[0].p; const float* d_tri = (const float*)in[1].p; const int* d_boxes = (const int*)in[2].p;
+    float* d_out = (float*)outs[0].p; float* d_matted = (float*)outs[1].p;
+    if (e->dry) TRY(prepare_variants(e, N, it.data(), nullptr, 4, 0));
+    T list = talloc(e, N, 1, 1, 5, 1);
+    T x16 = talloc(e, 2 * N, S, S, 16, e->act_f32);
+    T plane = talloc(e, N, S, S, 1, 1);
+    if (!e->dry) {
+      const unsigned nb = (unsigned)(((long)N * S * S + 255) / 256);
+      void* img16 = x16.p;
+      void* tri16 = (unsigned char*)x16.p + (size_t)N * S * S * 16 * fmt_bytes(x16.f32);
+      prof_begin(e, "boxes_sanitize", 0, (double)N * 40);
+      count_kernel("boxes_sanitize");
+      SDM_LAUNCH(boxes_sanitize_kernel, dim3(1), dim3(64), 0, e->stream, d_boxes, (int*)list.p, N, B, H, W);
+      prof_end(e);
+      // (an upper bound of the bytes: what is read depends on the boxes)
+      prof_begin(e, "boxes_prep_image", 0, (double)N * H * W * 12 + (double)N * S * S * 16 * fmt_bytes(x16.f32));
+      count_kernel("boxes_prep_image");
+      SDM_LAUNCH(boxes_prep_image_kernel, dim3(nb), dim3(256), 0, e->stream, d_img, (const int*)list.p, img16, x16.f32, N, H, W, S);
+      prof_end(e);
+      prof_begin(e, "boxes_prep_trimap", 0, (double)N * H * W * 4 + (double)N * S * S * (16 * fmt_bytes(x16.f32) + 4));
+      count_kernel("boxes_prep_trimap");
+      SDM_LAUNCH(boxes_prep_trimap_kernel, dim3(nb), dim3(256), 0, e->stream, d_tri, (const int*)list.p, tri16, x16.f32, (float*)plane.p, N, H, W, S);
+      prof_end(e);
+    }
+    T a;
+    TRY(run_model(e, x16, plane, N, S, S, true, &a));
+    if (!e->dry) {
+      const dim3 fgrid((unsigned)(((long)B * H * W + 255) / 256));
+      prof_begin(e, "boxes_paste", 0, (double)px * 4 + (double)N * S * S * 4);
+      count_kernel("boxes_paste");
+      SDM_LAUNCH(boxes_paste_kernel, fgrid, dim3(256), 0, e->stream, (const float*)a.p, (const int*)list.p, d_out, N, B, H, W, S);
+      prof_end(e);
+      SDM_LAUNCH(refine_compose_kernel, fgrid, dim3(256), 0, e->stream, d_img, d_tri, d_out, d_matted, (long)B * H * W, tail.output_mode, tail.mask_refine,
+                 (float)tail.c, (float)(1.0 - tail.c));
+    }
+    tfree(e, a); tfree(e, plane); tfree(e, x16); tfree(e, list);
     return 0;
   });
 }

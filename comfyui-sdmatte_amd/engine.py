@@ -82,7 +82,7 @@ EXPORTS = [
     "sdm_default_config", "sdm_create", "sdm_destroy", "sdm_last_error", "sdm_load_tensor", "sdm_finalize_weights",
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
-    "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
+    "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias",
@@ -121,6 +121,8 @@ class Bindings:
             "sdm_apply_matte_mask": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, C.c_double, vp, vp, vp, i32, vp]),
             "sdm_subject_roi": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, i32, vp, i32, vp]),
             "sdm_apply_matte_roi": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, f32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, i32, vp]),
+            "sdm_subject_boxes": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
+            "sdm_apply_matte_boxes": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, C.c_double, vp, vp, i32, vp]),
             "sdm_estimate_foreground": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
             "sdm_refine_alpha_guided": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp]),
             "sdm_compose_canvas": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
@@ -559,6 +561,79 @@ class Engine:
         if sync:
             self.synchronize()
         return alpha, matted, trimap, roi
+
+    BOXES_MAX = 8                # SDM_BOXES_MAX (include/sdmatte.h)
+    BOXES_MAX_TOTAL = 16         # SDM_BOXES_MAX_TOTAL
+
+    @classmethod
+    def _check_boxes_params(cls, what, min_area, max_boxes):
+        if int(min_area) != min_area or not 0 <= int(min_area) <= cls.CLEAN_MAX_AREA:
+            raise ValueError(f"{what}: min_area must be an integer in 0 .. {cls.CLEAN_MAX_AREA}, got {min_area!r}")
+        if int(max_boxes) != max_boxes or not 1 <= int(max_boxes) <= cls.BOXES_MAX:
+            raise ValueError(f"{what}: max_boxes must be an integer in 1 .. {cls.BOXES_MAX}, got {max_boxes!r}")
+        return int(min_area), int(max_boxes)
+
+    def subject_boxes(self, plane, roi_threshold=0.0, min_area=64, max_boxes=4, margin_px=16, margin_pct=10, square=True, out=None, sync=True,
+                      return_count=False):
+        """A box per subject on the GPU (sdm_subject_boxes, defined in include/sdmatte.h): plane [B,H,W] -> int32 [B,max_boxes,5] = per image the entries
+        {b, y0, x0, h, w}: the `subject_roi` boxes of the up to max_boxes - 1 largest 8-connected components of `plane > roi_threshold` with at least
+        min_area pixels (one that lies inside an earlier box gets none), then the box of whatever these leave uncovered; the whole frame for an image
+        without such a pixel; {-1, 0, 0, 0, 0} in every further entry.  return_count: also int32 [B], the entries per image.  Needs no loaded weights.
+        `sdmatte_nodes.subject_boxes` is the same function on CPU tensors, exactly."""
+        if plane.dim() != 3 or plane.numel() == 0:
+            raise ValueError(f"subject_boxes: plane must be a non-empty [B,H,W], got {tuple(plane.shape)}")
+        roi_threshold, margin_px, margin_pct = self._check_roi_params("subject_boxes", roi_threshold, margin_px, margin_pct)
+        min_area, max_boxes = self._check_boxes_params("subject_boxes", min_area, max_boxes)
+        B, H, W = (int(v) for v in plane.shape)
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"subject_boxes: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        plane = plane.float().contiguous()
+        if out is None:
+            out = torch.empty(B, max_boxes, 5, dtype=torch.int32, device=plane.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (B, max_boxes, 5):
+            raise ValueError("subject_boxes: out must be a contiguous int32 tensor [B,max_boxes,5]")
+        count = torch.empty(B, dtype=torch.int32, device=plane.device) if return_count else None
+        stream = self._check_io("subject_boxes", plane, out, count)
+        self._check(self.lib.sdm_subject_boxes(self.h, _ptr(plane), B, H, W, roi_threshold, min_area, max_boxes, margin_px, margin_pct, 1 if square else 0,
+                                               _ptr(out), _ptr(count), self._kind(plane), stream), "sdm_subject_boxes")
+        if sync:
+            self.synchronize()
+        return (out, count) if return_count else out
+
+    def apply_matte_boxes(self, image_bhwc, trimap_bhw, boxes, S, is_transparent, output_mode, mask_refine, trimap_constraint, sync=True):
+        """`apply_matte_node` over a list of boxes in one C-ABI call (sdm_apply_matte_boxes): boxes int32 [N,5] = {b, y0, x0, h, w}, N in 1 .. 16, on the
+        device of the planes; the model runs with batch N, one box per slot at S x S, and each frame pixel gets the maximum of the boxes that contain it,
+        0 outside all of them; mask_refine and the composition run on the whole frame.  An entry that does not lie inside its image is void (the void
+        entries of `subject_boxes` are): it is skipped, but still costs a model pass - `sdmatte_nodes.compact_boxes` drops them on the host.  Returns
+        (alpha [B,H,W], matted [B,H,W,3|4])."""
+        if output_mode not in self.OUTPUT_MODES:
+            raise ValueError(f"unknown output_mode {output_mode!r}")
+        if image_bhwc.dim() != 4 or image_bhwc.shape[-1] != 3 or image_bhwc.numel() == 0:
+            raise ValueError(f"apply_matte_boxes: image must be a non-empty [B,H,W,3], got {tuple(image_bhwc.shape)}")
+        B, H, W, _ = (int(v) for v in image_bhwc.shape)
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"apply_matte_boxes: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        if trimap_bhw.dim() != 3 or trimap_bhw.shape[0] != B:
+            raise ValueError(f"apply_matte_boxes: trimap must be [B,H,W] with B = {B}, got {tuple(trimap_bhw.shape)}")
+        if tuple(trimap_bhw.shape) != (B, H, W):
+            # the boxes are boxes of the image: there is no trimap of another size here
+            raise IndexError(f"apply_matte_boxes: trimap {tuple(trimap_bhw.shape[1:])} must match the image {(H, W)}")
+        if boxes.dim() != 2 or boxes.shape[1] != 5 or boxes.dtype != torch.int32 or not 1 <= boxes.shape[0] <= self.BOXES_MAX_TOTAL:
+            raise ValueError(f"apply_matte_boxes: boxes must be int32 [N,5] with N in 1 .. {self.BOXES_MAX_TOTAL}, got {boxes.dtype} {tuple(boxes.shape)}")
+        image_bhwc = image_bhwc.float().contiguous()
+        trimap_bhw = trimap_bhw.float().contiguous()
+        boxes = boxes.contiguous()
+        mode = self.OUTPUT_MODES[output_mode]
+        dev = image_bhwc.device
+        alpha = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+        matted = torch.empty(B, H, W, 4 if mode == 1 else 3, dtype=torch.float32, device=dev)
+        stream = self._check_io("apply_matte_boxes", image_bhwc, trimap_bhw, boxes, alpha, matted)
+        self._check(self.lib.sdm_apply_matte_boxes(self.h, _ptr(image_bhwc), _ptr(trimap_bhw), B, H, W, int(S), 1 if is_transparent else 0, _ptr(boxes),
+                                                   int(boxes.shape[0]), mode, 1 if mask_refine else 0, float(trimap_constraint), _ptr(alpha), _ptr(matted),
+                                                   self._kind(image_bhwc), stream), "sdm_apply_matte_boxes")
+        if sync:
+            self.synchronize()
+        return alpha, matted
 
     # SDM_FG_* (include/sdmatte.h)
     FG_DEFAULTS = {"regularization": 1e-5, "gradient_weight": 1.0, "n_small_iters": 10, "n_big_iters": 2}

@@ -352,6 +352,43 @@ class MultiGpuEngine:
         self._fan(B, call)
         return alpha, matted, trimap, roi
 
+    def subject_boxes(self, plane_bhw, roi_threshold=0.0, min_area=64, max_boxes=4, margin_px=16, margin_pct=10, square=True, return_count=False):
+        """A box per subject (no model involved): on the first engine; plane [B,H,W] (host or any device) -> int32 [B,max_boxes,5] (and counts) on the HOST."""
+        return self.engines[0].subject_boxes(self._to_host(plane_bhw), roi_threshold, min_area, max_boxes, margin_px, margin_pct, square,
+                                             return_count=return_count)
+
+    @staticmethod
+    def shard_boxes(boxes_n5, lo, hi):
+        """The entries of the images lo .. hi-1 in their order, with b rebased to the shard; one void entry if there is none (the call needs N >= 1, and
+        an image without a box gets alpha 0)."""
+        b = boxes_n5[:, 0]
+        part = boxes_n5[(b >= lo) & (b < hi)].clone()
+        part[:, 0] -= lo
+        if part.shape[0] == 0:
+            part = torch.tensor([[-1, 0, 0, 0, 0]], dtype=torch.int32)
+        return part.contiguous()
+
+    def apply_matte_boxes(self, image_bhwc, trimap_bhw, boxes_n5, S, is_transparent, output_mode, mask_refine, trimap_constraint):
+        """`Engine.apply_matte_boxes` for a batch split over the devices by image: every shard gets the entries of its images (`shard_boxes`); returns
+        (alpha [B,H,W], matted [B,H,W,3|4]) on the HOST."""
+        from .engine import Engine
+        B, H, W, _ = image_bhwc.shape
+        ch = 4 if Engine.OUTPUT_MODES[output_mode] == 1 else 3
+        alpha = self._host(B, H, W)
+        matted = self._host(B, H, W, ch)
+        img = self._to_host(image_bhwc)
+        tri = self._to_host(trimap_bhw)
+        boxes = boxes_n5.detach().cpu().to(torch.int32).reshape(-1, 5)
+
+        def call(eng, dev, lo, hi):
+            a, m = eng.apply_matte_boxes(img[lo:hi], tri[lo:hi], self.shard_boxes(boxes, lo, hi), S, is_transparent, output_mode, mask_refine,
+                                         trimap_constraint)
+            alpha[lo:hi].copy_(a)
+            matted[lo:hi].copy_(m)
+
+        self._fan(B, call)
+        return alpha, matted
+
     def compose_canvas(self, fg_bhw3, alpha_bhw, canvas_h, canvas_w, fill_pct=80, valign="center", bg_color=None, bg_image=None, shadow_opacity=0.0,
                        shadow_sigma=8.0, shadow_dy=0, shadow_dx=0, roi_threshold=0.0, out_channels=None, return_placement=False):
         """The cut-out on a canvas (no model involved): on the first engine; inputs on the host or any device -> canvas (and placements) on the HOST."""

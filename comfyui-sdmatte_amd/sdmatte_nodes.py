@@ -492,6 +492,80 @@ def paste_roi(crop_bhw, roi, H, W):
     return out
 
 
+def subject_boxes(plane, roi_threshold=0.0, min_area=64, max_boxes=4, margin_px=16, margin_pct=10, square=True, return_count=False):
+    """`Engine.subject_boxes` on CPU tensors, exactly (integers only; the definition is in include/sdmatte.h, sdm_subject_boxes): plane [B,H,W] -> int32
+    [B,max_boxes,5] = per image the entries {b, y0, x0, h, w}, void entries {-1, 0, 0, 0, 0} behind them; with return_count also int32 [B]."""
+    import numpy as np
+    from .engine import Engine
+    if plane.dim() != 3 or plane.numel() == 0:
+        raise ValueError(f"subject_boxes: plane must be a non-empty [B,H,W], got {tuple(plane.shape)}")
+    roi_threshold, margin_px, margin_pct = Engine._check_roi_params("subject_boxes", roi_threshold, margin_px, margin_pct)
+    min_area, max_boxes = Engine._check_boxes_params("subject_boxes", min_area, max_boxes)
+    p = plane.detach().cpu().float().contiguous().numpy()
+    B, H, W = p.shape
+    n = H * W
+    out = np.zeros((B, max_boxes, 5), np.int32)
+    out[:, :, 0] = -1
+    count = np.zeros(B, np.int32)
+
+    def box_of(u):
+        """subject_roi's rule on the extrema of the non-empty set u (bool [H,W])."""
+        return [int(v) for v in subject_roi(torch.from_numpy(u[None].astype(np.float32)), 0.0, margin_px, margin_pct, square)[0]]
+
+    for b in range(B):
+        with np.errstate(invalid="ignore"):
+            u = p[b] > np.float32(roi_threshold)
+        entries = []
+        if u.any():
+            roots = _component_roots(u, True)
+            area = np.bincount(roots.ravel(), minlength=n + 1)[:n]
+            ids = np.flatnonzero(area)
+            ids = ids[area[ids] >= min_area]
+            order = ids[np.argsort(-area[ids], kind="stable")][:max_boxes - 1]      # stable: equal areas stay in root order
+            covered = np.zeros((H, W), bool)
+            for r in order:
+                comp = roots == r
+                rows, cols = np.flatnonzero(comp.any(axis=1)), np.flatnonzero(comp.any(axis=0))
+                if any(y0 <= rows[0] and rows[-1] < y0 + h and x0 <= cols[0] and cols[-1] < x0 + w for y0, x0, h, w in entries):
+                    continue
+                y0, x0, h, w = box_of(comp)
+                entries.append((y0, x0, h, w))
+                covered[y0:y0 + h, x0:x0 + w] = True
+            rest = u & ~covered
+            if rest.any():
+                entries.append(tuple(box_of(rest)))
+        else:
+            entries.append((0, 0, H, W))
+        for i, e in enumerate(entries):
+            out[b, i] = (b, ) + tuple(e)
+        count[b] = len(entries)
+    out = torch.from_numpy(out)
+    return (out, torch.from_numpy(count)) if return_count else out
+
+
+def compact_boxes(boxes):
+    """The entries of a box list (int [..,5] = {b, y0, x0, h, w}) that are not void (b >= 0), in their order, as int32 [N,5] on the host."""
+    flat = torch.as_tensor(boxes).detach().cpu().reshape(-1, 5).to(torch.int32)
+    return flat[flat[:, 0] >= 0].contiguous()
+
+
+def paste_boxes(crops, boxes, B, H, W):
+    """The way back of `Engine.apply_matte_boxes` on CPU tensors: crops[n] ([h,w] of boxes[n] = {b, y0, x0, h, w}) -> fp32 [B,H,W], each crop pasted into
+    zeros at (y0, x0) of image b, the element-wise maximum where several meet.  A void entry (b < 0) is skipped."""
+    boxes = torch.as_tensor(boxes).reshape(-1, 5)
+    if len(crops) != boxes.shape[0]:
+        raise ValueError(f"paste_boxes: {len(crops)} crops for {boxes.shape[0]} boxes")
+    out = torch.zeros(int(B), int(H), int(W), dtype=torch.float32)
+    for n, crop in enumerate(crops):
+        b, y0, x0, h, w = (int(v) for v in boxes[n])
+        if b < 0:
+            continue
+        if b >= B or tuple(crop.shape) != (h, w) or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+            raise ValueError(f"paste_boxes: crop {tuple(crop.shape)} does not fit the box {(b, y0, x0, h, w)} of {int(B)} frames of {(int(H), int(W))}")
+        out[b] = torch.maximum(out[b], paste_roi(crop[None], [[y0, x0, h, w]], H, W)[0])
+    return out
+
+
 def canvas_fit(roi, canvas_h, canvas_w, fill_pct=80, valign="center"):
     """The placements of `Engine.compose_canvas` in exact integers (the definition is in include/sdmatte.h, sdm_compose_canvas): roi int [B,4] = {y0, x0, h, w}
     -> int32 [B,8] = {y0, x0, h, w, dy0, dx0, dh, dw}, the box scaled to fill `fill_pct` % of the canvas and aligned in it."""
@@ -916,6 +990,90 @@ class SDMatteApplyROI:
         return (out, matted, trimap, boxes)
 
 
+_SUBJECTS_INPUTS = {
+    "max_subjects": ("INT", {"default": 4, "min": 1, "max": 8, "step": 1, "tooltip": "boxes per image: the largest subjects get one each, the last one takes whatever is left"}),
+    "min_area": ("INT", {"default": 64, "min": 0, "max": 1 << 28, "step": 1, "tooltip": "a component of the trimap below this many pixels gets no box of its own"}),
+}
+
+
+def split_boxes(boxes, B, limit):
+    """Consecutive image ranges (lo, hi, entries) such that no range has more than `limit` entries: entries int32 [n,5] of the images lo .. hi-1 with b
+    rebased to the range.  `boxes` is a compacted list whose entries are grouped by image in ascending order."""
+    per = [boxes[boxes[:, 0] == b] for b in range(B)]
+    out, lo, n = [], 0, 0
+    for b in range(B):
+        if len(per[b]) > limit:
+            raise ValueError(f"split_boxes: image {b} has {len(per[b])} boxes, more than {limit}")
+        if n + len(per[b]) > limit:
+            out.append((lo, b))
+            lo, n = b, 0
+        n += len(per[b])
+    out.append((lo, B))
+    res = []
+    for lo, hi in out:
+        part = torch.cat(per[lo:hi]).clone()
+        part[:, 0] -= lo
+        res.append((lo, hi, part.contiguous()))
+    return res
+
+
+class SDMatteApplySubjects:
+    """`Apply SDMatte (Subject Box)` with a box per subject: every large component of the trimap is matted in a model pass of its own at `inference_size`,
+    and the passes are merged by their maximum.  Returns the boxes as well: a list of (x, y, width, height) per image."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        base = SDMatteApplyROI.INPUT_TYPES()
+        required = {}
+        for key, spec in base["required"].items():
+            required[key] = spec
+            if key == "square":
+                required.update(_SUBJECTS_INPUTS)
+        return {"required": required, "optional": base["optional"]}
+
+    RETURN_TYPES = ("MASK", "IMAGE", "MASK", "BBOX")
+    RETURN_NAMES = ("alpha_mask", "matted_image", "trimap", "boxes")
+    FUNCTION = "apply_matte"
+    CATEGORY = "Matting/SDMatte"
+
+    def apply_matte(self, ckpt_name, image, mask, threshold, erode_px, dilate_px, roi_threshold, margin_px, margin_pct, square, max_subjects, min_area,
+                    inference_size, is_transparent, output_mode, mask_refine, trimap_constraint, force_cpu=False):
+        from .engine import Engine
+        if force_cpu:
+            raise RuntimeError("[SDMatte] force_cpu=True is not available: this node runs hand-written gfx950 kernels only "
+                               "(no CPU path).  Use the reference plugin for CPU inference.")
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        if mask.dim() != 3 or tuple(mask.shape) != tuple(image.shape[:3]):
+            raise ValueError(f"[SDMatte] mask must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(mask.shape)}")
+        Engine._check_roi_params("[SDMatte] apply_matte", roi_threshold, margin_px, margin_pct)
+        Engine._check_boxes_params("[SDMatte] apply_matte", min_area, max_subjects)
+        return self._run(get_model(ckpt_name, _torch_device()), image, mask, float(threshold), int(erode_px), int(dilate_px), float(roi_threshold),
+                         int(margin_px), int(margin_pct), bool(square), int(max_subjects), int(min_area), int(inference_size), bool(is_transparent),
+                         output_mode, bool(mask_refine), float(trimap_constraint))
+
+    @staticmethod
+    def _run(model, image, mask, threshold, erode_px, dilate_px, roi_threshold, margin_px, margin_pct, square, max_subjects, min_area, inference_size,
+             is_transparent, output_mode, mask_refine, trimap_constraint):
+        """Trimap, boxes, a readback of the few hundred bytes of the list, then one apply_matte_boxes call per range of images with at most
+        SDM_BOXES_MAX_TOTAL entries."""
+        from .engine import Engine
+        eng = model.engine
+        B = int(image.shape[0])
+        trimap = eng.make_trimap(mask, threshold, erode_px, dilate_px)
+        boxes = compact_boxes(eng.subject_boxes(trimap, roi_threshold, min_area, max_subjects, margin_px, margin_pct, square))
+        alphas, matteds = [], []
+        for lo, hi, part in split_boxes(boxes, B, Engine.BOXES_MAX_TOTAL):
+            fan = _fan_out(model, hi - lo)
+            runner = fan if fan is not None else eng
+            a, m = runner.apply_matte_boxes(image[lo:hi], trimap[lo:hi], part, inference_size, is_transparent, output_mode, mask_refine, trimap_constraint)
+            alphas.append(a.detach().cpu())
+            matteds.append(m.detach().cpu())
+        out = [[(int(x0), int(y0), int(w), int(h)) for bb, y0, x0, h, w in boxes.tolist() if bb == b] for b in range(B)]
+        _trim_engine_memory(model)
+        return (torch.cat(alphas), torch.cat(matteds), trimap.detach().cpu(), out)
+
+
 _FOREGROUND_INPUTS = {
     "regularization": ("FLOAT", {"default": 1e-5, "min": 1e-9, "max": 1.0, "step": 1e-6, "tooltip": "smoothness weight between all neighbours (must be above 0)"}),
     "gradient_weight": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 100.0, "step": 0.01, "tooltip": "extra smoothness weight across alpha edges"}),
@@ -1043,10 +1201,11 @@ class SDMatteCanvas:
         return (_trimap_engine(_torch_device()).compose_canvas(*args), )
 
 
-def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False, canvas: bool = False):
+def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False, canvas: bool = False,
+                  subjects: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
     node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`, plus the subject-box node when `roi`,
-    plus the canvas node when `canvas`."""
+    plus the canvas node when `canvas`, plus the box-per-subject node when `subjects`."""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
@@ -1067,14 +1226,18 @@ def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, c
     if canvas:
         classes["SDMatteCanvas"] = SDMatteCanvas
         names["SDMatteCanvas"] = "SDMatte Canvas"
+    if subjects:
+        classes["SDMatteApplySubjects"] = SDMatteApplySubjects
+        names["SDMatteApplySubjects"] = "Apply SDMatte (Subjects)"
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1), like the multi-GPU fan-out
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
 NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
                                                                 os.environ.get("SDMATTE_REFINE_NODE") == "1",
                                                                 os.environ.get("SDMATTE_CLEAN_NODE") == "1",
                                                                 os.environ.get("SDMATTE_ROI_NODE") == "1",
-                                                                os.environ.get("SDMATTE_CANVAS_NODE") == "1")
+                                                                os.environ.get("SDMATTE_CANVAS_NODE") == "1",
+                                                                os.environ.get("SDMATTE_SUBJECTS_NODE") == "1")

@@ -243,6 +243,55 @@ int sdm_apply_matte_roi(sdm_ctx* ctx, const float* image_bhwc, const float* aux_
                         int output_mode, int mask_refine, double trimap_constraint, float* alpha_bhw, float* matted_bhwc, float* trimap_out,
                         int32_t* roi_out, int ptr_kind, void* stream);
 
+/* A box per subject, on the GPU (beyond the reference): two people at opposite ends of a group shot have a joint box that is nearly the frame, so
+ * sdm_subject_roi gives each of them a fraction of `inference_size`.  plane fp32 [B,H,W] -> boxes_bk5 int32 [B][max_boxes][5] = {b, y0, x0, h, w} and
+ * count_b (may be NULL) int32 [B], both of the same pointer kind as the plane.  Per image:
+ *   U, components  U = { p : plane[p] > roi_threshold } (one fp32 compare, so NaN is outside U); its components are 8-connected, a component's area is
+ *            its pixel count and its root its smallest pixel index y*W + x (stage A of sdm_clean_mask with roi_threshold as the threshold).
+ *   rank     the candidates are the components with area >= min_area, ordered by area descending, then root ascending; the own components
+ *            C_1 .. C_m are the first m = min(max_boxes - 1, number of candidates).
+ *   box(X)   for a pixel set X: the rule of sdm_subject_roi (margin, clip, optional square) applied to X's extrema.
+ *   containment  in rank order, C_i is kept unless its raw bounding box [ymin, ymax] x [xmin, xmax] lies inside box(C_j) of a kept C_j, j < i: a hand
+ *            or a strand of hair that the mask separated from its owner gets no pass of its own.  The kept boxes, in rank order, are entries
+ *            0 .. n_own-1.
+ *   rest     R = the pixels of U in none of the kept boxes; if R is not empty, entry n_own is box(R): candidates beyond the own ones and components
+ *            below min_area are never lost.
+ *   An empty U gives one entry, the whole frame {b, 0, 0, H, W}.  count_b[b] is the number of entries, in 1 .. max_boxes; every further entry is void:
+ *   {-1, 0, 0, 0, 0}.
+ * Hence every pixel of U lies in at least one box, and with max_boxes = 1 the single entry is sdm_subject_roi's box for the same arguments.
+ * Integer arithmetic only: GPU, emulator and sdmatte_nodes.subject_boxes agree exactly.  roi_threshold, margin_px, margin_pct, square, B, H, W as in
+ * sdm_subject_roi, min_area in 0 .. SDM_FG_MAX_PIXELS, max_boxes in 1 .. SDM_BOXES_MAX: SDM_ERR_INVALID otherwise, and then nothing is queued or
+ * written.  Stream contract and pointer kinds as sdm_subject_roi; sdm_last_forward_ms covers the launches.  Needs no weights.  8 + 2 (max_boxes - 1)
+ * kernel launches (csrc/k_boxes.h: cc_tile, cc_seam, cc_flatten, boxes_init, boxes_rank x 2 per own slot, boxes_reduce, boxes_own, boxes_rest,
+ * boxes_finalize), whatever B, H, W and the content; no host readback.  The three label planes (12 bytes per pixel) and the per-image state are part of
+ * the activation arena, host pointers go through the I/O staging (sdm_resident_bytes counts both, sdm_release_memory frees them). */
+#define SDM_BOXES_MAX 8
+int sdm_subject_boxes(sdm_ctx* ctx, const float* plane_bhw, int B, int H, int W, float roi_threshold, int min_area, int max_boxes, int margin_px,
+                      int margin_pct, int square, int32_t* boxes_bk5, int32_t* count_b, int ptr_kind, void* stream);
+/* sdm_apply_matte_node over a list of boxes: the model runs with batch N, slot n on the box of entry n = {b, y0, x0, h, w} of boxes_n5 (int32 [N][5], of
+ * the same pointer kind as the planes; N in 1 .. SDM_BOXES_MAX_TOTAL is known to the host, the list's content stays on the device), and the alphas go
+ * back into the frames.  The trimap [B,H,W] has the image's size.
+ *   sanitise an entry is valid iff 0 <= b < B, h >= 1, w >= 1, y0 >= 0, x0 >= 0, y0 + h <= H and x0 + w <= W (compared in 64 bits); every other entry is
+ *            void, the void entries of sdm_subject_boxes among them.  The same rule for host and device pointers; a void entry is not an error, and no
+ *            kernel of this call reads outside the planes whatever the list holds.
+ *   prepare  slot n is fed the box of image b and of its trimap, resized to SxS as in sdm_apply_matte_roi.  A void slot is fed the whole frame of image 0
+ *            and its result is discarded: it costs a model pass, so a caller who wants to avoid that compacts the list first.
+ *   paste    alpha[b][p] = the maximum, over the valid entries of image b whose box contains p, of the clamped resize of that slot's alpha
+ *            (sdm_apply_matte_roi's arithmetic); 0.0 if there is none.  A pixel in exactly one box gets that box's value unchanged; where boxes overlap,
+ *            the maximum is the order-independent choice that never lets one box's edge cut into a neighbour.
+ *   mask_refine and the output composition then run over the whole frame as in sdm_apply_matte_node.  The box conditioning stays [0, 0, 1, 1] and
+ *   is_transparent is one flag.
+ * "Outside every box = 0.0" is exact for a list from sdm_subject_boxes on the same trimap and threshold (every such pixel has trimap <= roi_threshold);
+ * for a caller's own list it is the caller's statement.  With the list {b, roi[b]} of sdm_subject_roi the call is bit-identical to sdm_apply_matte_roi
+ * (aux_is_mask = 0).  The model's kernels are chosen by launch size, so a slot's bits may depend on N.
+ * N outside its range, a bad output_mode, S or plane size: SDM_ERR_INVALID, and then nothing is queued or written.  The arena is that of a
+ * sdm_apply_matte_node call with batch N, plus the list.  Four launches beyond the model's, each once per call: boxes_sanitize, boxes_prep_image,
+ * boxes_prep_trimap, boxes_paste in sdm_kernel_counts and the per-launch profile. */
+#define SDM_BOXES_MAX_TOTAL 16
+int sdm_apply_matte_boxes(sdm_ctx* ctx, const float* image_bhwc, const float* trimap_bhw, int B, int H, int W, int S, int is_transparent,
+                          const int32_t* boxes_n5, int N, int output_mode, int mask_refine, double trimap_constraint, float* alpha_bhw,
+                          float* matted_bhwc, int ptr_kind, void* stream);
+
 /* Foreground / background colours from an image and its alpha, on the GPU (beyond the reference: its matted_rgba keeps the composite
  * a*F + (1-a)*B in every semi-transparent pixel, and with it a halo of the old background).  A multi-level estimator in the style of Germer et al.,
  * "Fast Multi-Level Foreground Estimation"; it uses the image and the alpha only.
