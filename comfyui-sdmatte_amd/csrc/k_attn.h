@@ -19,8 +19,9 @@
 
 struct AttnParams {
   const half_t* q; long q_bs; int ldq;                     // q [b][row][head*D + d]
-  const half_t* k; long k_bs; int ldk;                     // k [b][key][head*D + d]
-  const half_t* vt; long vt_bs; long vt_hs; int ldvt;      // vt[b][head][d][key]  (key padded to ldvt, zero filled)
+  const half_t* k; long k_bs; int ldk;                     // k [b][key][head*k_hs + d]
+  int k_hs;                                                // d = 64 kernels: elements between the heads of a key row (64), or 0: ONE [key][64] operand for every head
+  const half_t* vt; long vt_bs; long vt_hs; int ldvt;      // vt[b][head][d][key]  (key padded to ldvt, zero filled; vt_hs = 0: one V^T for every head)
   const float* bias; long bias_bs;                         // bias[b][key] * log2e, or null
   half_t* o; long o_bs; int ldo;                           // o [b][row][head*D + d]
   int o_f32;                                               // 1: o is fp32 (same indexing), 0: fp16
@@ -221,7 +222,7 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_d64_kernel(AttnParams p) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) ones[j] = (half_t)1.0f;
 
-  const half_t* kbase = p.k + (size_t)b * p.k_bs + head * 64;
+  const half_t* kbase = p.k + (size_t)b * p.k_bs + head * p.k_hs;
   const half_t* vbase = p.vt + (size_t)b * p.vt_bs + (size_t)head * p.vt_hs;
   const float* bbase = p.bias ? p.bias + (size_t)b * p.bias_bs : nullptr;
   const int ntiles = (p.Lk + 63) / 64;
@@ -607,7 +608,7 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_d64_pipe_kernel(AttnParams p)
 #pragma unroll
   for (int j = 0; j < 8; ++j) ones[j] = (half_t)1.0f;
 
-  const half_t* kbase = p.k + (size_t)b * p.k_bs + head * 64;
+  const half_t* kbase = p.k + (size_t)b * p.k_bs + head * p.k_hs;
   const half_t* vbase = p.vt + (size_t)b * p.vt_bs + (size_t)head * p.vt_hs;
   const float* bbase = p.bias ? p.bias + (size_t)b * p.bias_bs : nullptr;
   const float* bsrc = bbase ? bbase : (const float*)(p.k + (size_t)b * p.k_bs);
@@ -857,7 +858,7 @@ __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) ones[j] = (half_t)1.0f;
 
-  const half_t* kbase = p.k + (size_t)b * p.k_bs + head * 64;
+  const half_t* kbase = p.k + (size_t)b * p.k_bs + head * p.k_hs;
   const half_t* vbase = p.vt + (size_t)b * p.vt_bs + (size_t)head * p.vt_hs;
   const int ntiles = p.Lk / 64;                                        // (Lk % 64 == 0: launcher's condition)
   const int* tl = (LIST && p.tiles) ? p.tiles + (size_t)b * p.tiles_bs : nullptr;

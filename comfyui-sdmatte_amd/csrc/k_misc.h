@@ -170,31 +170,94 @@ __global__ void refine_compose_kernel(const float* __restrict__ img, const float
   }
 }
 
+// Four fp32 values -> their attention operand planes in the fp8-pair format (ConvParams::out_f32 == 3, the EPI 2 epilogue of k_gemm.h): clamped to the
+// largest finite e5m2, hi = fp16(y), pair word = [e5m2(y) x 4 | e5m2((y - hi) * 2^11) x 4].  The same statements as in those two epilogues.
+SDM_DEV_INLINE u32x2 sdm_pair_plane4(const float (&x)[4], f16x4& oh) {
+  float xx[4], xl[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float y = fminf(fmaxf(x[e], -57344.0f), 57344.0f);
+    oh[e] = (half_t)y; xx[e] = y; xl[e] = (y - (float)oh[e]) * 2048.0f;
+  }
+  int a = SDM_CVT_PK_BF8(xx[0], xx[1], 0, false), b = SDM_CVT_PK_BF8(xl[0], xl[1], 0, false);
+  a = SDM_CVT_PK_BF8(xx[2], xx[3], a, true); b = SDM_CVT_PK_BF8(xl[2], xl[3], b, true);
+  u32x2 pr;
+  pr[0] = (unsigned int)a; pr[1] = (unsigned int)b;
+  return pr;
+}
+
 // fp32 [n] -> the operand planes of the split-precision attention (what the producing GEMM's epilogue writes in the engine,
 // ConvParams::out_f32): hi = fp16(x * mult) and, behind it, either lo = fp16(x * mult - hi) (mode 2) or, per 4 values,
 // [e5m2(y) x 4 | e5m2((y - hi) * 2^11) x 4] (mode 3).  Test hook (sdm_op_attention_split).
 __global__ void split_planes_kernel(const float* __restrict__ x, half_t* __restrict__ hi, half_t* __restrict__ lo, long n, float mult, int mode) {
   const long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i4 >= n) return;
-  f16x4 oh, ol;
-  float xx[4], xl[4];
+  float y[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float y = (i4 + e < n) ? x[i4 + e] * mult : 0.0f;
-    if (mode == 3) y = fminf(fmaxf(y, -57344.0f), 57344.0f);
-    oh[e] = (half_t)y;
-    ol[e] = (half_t)(y - (float)oh[e]);
-    xx[e] = y; xl[e] = (y - (float)oh[e]) * 2048.0f;
-  }
-  *(f16x4*)(hi + i4) = oh;
+  for (int e = 0; e < 4; ++e) y[e] = (i4 + e < n) ? x[i4 + e] * mult : 0.0f;
+  f16x4 oh, ol;
   if (mode == 3) {
-    int a = SDM_CVT_PK_BF8(xx[0], xx[1], 0, false), b = SDM_CVT_PK_BF8(xl[0], xl[1], 0, false);
-    a = SDM_CVT_PK_BF8(xx[2], xx[3], a, true); b = SDM_CVT_PK_BF8(xl[2], xl[3], b, true);
-    u32x2 pr;
-    pr[0] = (unsigned int)a; pr[1] = (unsigned int)b;
+    const u32x2 pr = sdm_pair_plane4(y, oh);
+    *(f16x4*)(hi + i4) = oh;
     *(u32x2*)(lo + i4) = pr;
   } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { oh[e] = (half_t)y[e]; ol[e] = (half_t)(y[e] - (float)oh[e]); }
+    *(f16x4*)(hi + i4) = oh;
     *(f16x4*)(lo + i4) = ol;
+  }
+}
+
+// The ONE key / value operand of every cross-attention of a forward (sdm_engine.cpp, CrossPlanes): the im2col patch matrix P [Lk][36] of the 4-channel trimap
+// latent z (3x3, zero padding; column j = ci * 9 + ky * 3 + kx, the OIHW order of aux_conv_in.weight), padded to 64 columns.  z = channels 4..7 of the
+// fp32 NHWC U-Net input `uin` [B][H][W][16].  Per image:
+//   k_hi  [Lk][64] fp16, k_pair [Lk][64] pair words at the same element offsets (sdm_pair_plane4): the K operand of the d = 64 PREC = 3 kernels (k_attn.h);
+//   vt    [64][ldvt] fp16 = k_hi transposed, rows 36..63 and the key columns Lk .. ldvt - 1 zero: their V^T operand.
+// blockIdx.y = 0: thread = 8 columns of one key row (16-byte stores to both planes); 1: thread = 8 keys of one V^T row (one 16-byte store).
+SDM_DEV_INLINE float cross_patch_value(const float* __restrict__ uin, int H, int W, long b, int key, int j) {
+  if (j >= 36 || key >= H * W) return 0.0f;
+  const int ci = j / 9, tap = j - ci * 9, ky = tap / 3, kx = tap - ky * 3;
+  const int y = key / W + ky - 1, x = key - (key / W) * W + kx - 1;
+  if ((unsigned)y >= (unsigned)H || (unsigned)x >= (unsigned)W) return 0.0f;
+  return uin[((size_t)b * H * W + (size_t)y * W + x) * 16 + 4 + ci];
+}
+__global__ void __launch_bounds__(256) cross_patch_planes_kernel(const float* __restrict__ uin, int B, int H, int W, half_t* __restrict__ k_hi,
+                                                                 half_t* __restrict__ k_pair, half_t* __restrict__ vt, int ldvt) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int Lk = H * W;
+  if (blockIdx.y == 0) {
+    if (t >= (long)B * Lk * 8) return;
+    const int oct = (int)(t & 7), key = (int)((t >> 3) % Lk);
+    const long b = (t >> 3) / Lk;
+    u32x4 hv, pv;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      float x[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) x[e] = cross_patch_value(uin, H, W, b, key, oct * 8 + g * 4 + e);
+      f16x4 oh;
+      const u32x2 pr = sdm_pair_plane4(x, oh);
+      const u32x2 hw = __builtin_bit_cast(u32x2, oh);
+      hv[2 * g] = hw[0]; hv[2 * g + 1] = hw[1]; pv[2 * g] = pr[0]; pv[2 * g + 1] = pr[1];
+    }
+    const size_t o = ((size_t)b * Lk + key) * 64 + oct * 8;
+    *(u32x4*)(k_hi + o) = hv;
+    *(u32x4*)(k_pair + o) = pv;
+  } else {
+    const int cpr = ldvt / 8;      // 8-key chunks per V^T row
+    if (t >= (long)B * 64 * cpr) return;
+    const int chunk = (int)(t % cpr), j = (int)((t / cpr) & 63);
+    const long b = t / cpr / 64;
+    u32x4 hv;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      f16x4 oh;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) oh[e] = (half_t)fminf(fmaxf(cross_patch_value(uin, H, W, b, chunk * 8 + g * 4 + e, j), -57344.0f), 57344.0f);
+      const u32x2 hw = __builtin_bit_cast(u32x2, oh);
+      hv[2 * g] = hw[0]; hv[2 * g + 1] = hw[1];
+    }
+    *(u32x4*)(vt + ((size_t)b * 64 + j) * ldvt + chunk * 8) = hv;
   }
 }
 

@@ -36,6 +36,7 @@
 #include <mutex>
 #include <shared_mutex>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -132,6 +133,7 @@ static OptEntry g_opts[] = {
   {"attn_pp", 1, 1, "split-precision d=64 attention with fp32 output as a ping-pong of the block's wave halves (attn_d64_pp_kernel, 256 query rows per block): 0 off, 1 on, 2 on without the static priority of the younger half, 3 on with per-segment priority flips"},
   {"attn_pp_min_blocks", 128, 128, "attn_pp: launches with fewer 256-row blocks than this keep the 4-wave pipelines (0 in tests: the ping-pong kernel at any size)"},
   {"attn_ksplit", 0, 0, "key split of the d=64 split-precision attention: 0 by launch size (blocks that do not fill the chip's block slots a whole number of times), 1 off, 2 / 4 forced, 3 forced on the ping-pong kernel (ignored elsewhere: those launches run unsplit)"},
+  {"cross_shared", 1, 1, "cross-attention on ONE key / value operand per forward, the patch matrix of the trimap latent (cross_patch_planes_kernel), with the K|V fold moved into q_shared / out_shared: 0 = every block's own kv_folded conv + transpose.  Read per forward"},
   {"precise_mask", -1, -1, "stages in split precision (-1 = the config's own mask; per-stage attribution experiments; read at sdm_create)"},
 #ifdef SDM_EMU
   {"emu_arena_extra", 0, 0, "emulator build only, self-test of the arena check: the launch pass of a stand-alone op allocates one block its sizing pass did not"},
@@ -634,11 +636,13 @@ struct Slot {
   float w_scale = 1.0f;    // SLOT_CONV_W: constant folded into the weight before the fp16 rounding (attention logit scale in to_q)
   std::vector<int64_t> shape;
   size_t host_off = 0;     // SLOT_HOST: float offset in the host blob
+  bool host_too = false;   // a packed slot whose fp32 tensor is ALSO kept in the host blob at host_off (a finalize-time fold reads it)
   bool loaded = false;
 };
 struct ResB { int norm1 = -1, conv1 = -1, norm2 = -1, conv2 = -1, sc = -1, temb = -1, cin = 0, cout = 0; };
 struct VaeAttnB { int gn = -1, qkv = -1, out = -1, C = 0; };
-struct TfB { int gn, proj_in, ln1, qkv1, o1, ln2, q2, kv2, o2, ln3, ff1, ff2, proj_out, C, heads; size_t k_hoff, v_hoff; };
+struct TfB { int gn, proj_in, ln1, qkv1, o1, ln2, q2, kv2, o2, ln3, ff1, ff2, proj_out, C, heads; size_t k_hoff, v_hoff;
+             int q2s, o2s; size_t q_hoff, o_hoff, ob_hoff; };      // shared-operand form of the cross-attention (fold_cross_shared)
 struct TembL { size_t w_hoff = 0, b_hoff = 0, cb_hoff = 0; int cout = 0, cout_pad = 0; float* table = nullptr; };
 
 struct T {  // NHWC activation tensor living in the arena
@@ -817,6 +821,14 @@ struct Builder {
     e->slots[key] = s;
     e->slot_order.push_back(key);
   }
+  // the fp32 tensor of a packed slot is kept on the host as well -> its offset in the host blob
+  size_t keep_host(const std::string& key) {
+    Slot& s = e->slots[key];
+    size_t n = 1; for (auto d : s.shape) n *= (size_t)d;
+    s.host_too = true; s.host_off = e->hostblob.size();
+    e->hostblob.resize(e->hostblob.size() + n, 0.0f);
+    return s.host_off;
+  }
   // plain conv / linear layer "<p>.weight"/"<p>.bias"
   int conv_named(const std::string& p, int ntaps, int I, int O, bool bias = true, int ci_off = 0, int Ipad = 0, int up = 0) {
     int id = conv(p, ntaps, Ipad ? Ipad : I, O, 0, up);
@@ -894,6 +906,13 @@ struct Builder {
     slot(b + ".attn2.to_k.weight", SLOT_HOST, -1, {C, ctx}); t.k_hoff = e->slots[b + ".attn2.to_k.weight"].host_off;
     slot(b + ".attn2.to_v.weight", SLOT_HOST, -1, {C, ctx}); t.v_hoff = e->slots[b + ".attn2.to_v.weight"].host_off;
     t.o2 = conv_named(b + ".attn2.to_out.0", 1, C, C);
+    // the same cross-attention on the key / value operand that all blocks share (fold_cross_shared): per head the folded K / V weights move into to_q /
+    // to_out.0.  Two more C -> C Linears with host-folded weights; to_q / to_out.0 stay packed for the option cross_shared = 0 and keep host copies
+    t.q2s = conv(b + ".attn2.q_shared", 1, C, C);
+    t.o2s = conv(b + ".attn2.out_shared", 1, C, C);
+    t.q_hoff = keep_host(b + ".attn2.to_q.weight");
+    t.o_hoff = keep_host(b + ".attn2.to_out.0.weight");
+    t.ob_hoff = keep_host(b + ".attn2.to_out.0.bias");
     t.ff1 = conv(b + ".ff.net.0.proj", 1, C, 8 * C, 1);
     slot(b + ".ff.net.0.proj.weight", SLOT_CONV_W, t.ff1, {8 * C, C});
     slot(b + ".ff.net.0.proj.bias", SLOT_CONV_B, t.ff1, {8 * C});
@@ -1362,6 +1381,7 @@ static int op_conv(sdm_ctx* e, const ConvL& L, const ConvArgs& a) {
   } else {
     prof_begin(e, "conv", flops, bytes);
   }
+  if (L.ntaps == 9 && (L.I <= 16 || L.O <= 16)) count_kernel("conv3x3_thin");
   int rc = 0;
   // GEMMs that emit per-image GroupNorm statistics for a batch: row tiles aligned to images inside ONE launch
   if (L.ntaps == 1 && p.stats && p.N > 1) p.rows_per_img = p.Hout * p.Wout;
@@ -1497,7 +1517,9 @@ static int op_ln(sdm_ctx* e, const NormL& n, const T& x, float eps, T* out, int 
 // prec: 0 fp16 operands; 1 q / k / v as fp16 planes hi | lo; 2 q / k as fp16 plane + e5m2 pair plane (ConvParams::out_f32 == 3), v hi only
 // has_bias / has_tiles: whether a key bias / a caller's tile list comes with the call.  Stated by the caller, never read off bias_l2 / tiles: those
 // pointers exist only outside the dry pass, and the launch plan must be the same in both passes.
-struct AttnPrec { int prec = 0; long q_lo = 0, k_lo = 0, v_lo = 0; int out_f32 = 0; int out_p3 = 0; bool has_bias = false, has_tiles = false; };      // out_p3 (with out_f32 = 1): `out` is a P3 tensor (k_gemm.h)
+// shared_kv (d = 64, no residual terms of P.V): ONE key / value operand for every head - `k` is [b][key][64] (ldk = 64, head stride 0) and `v` is the READY
+// V^T [b][64][rup(Lk, 64)] (zero filled behind Lk; ldv is not read): no V^T scratch, no transpose_v launch
+struct AttnPrec { int prec = 0; long q_lo = 0, k_lo = 0, v_lo = 0; int out_f32 = 0; int out_p3 = 0; bool has_bias = false, has_tiles = false; bool shared_kv = false; };      // out_p3 (with out_f32 = 1): `out` is a P3 tensor (k_gemm.h)
 
 // Everything op_attention_raw decides about a launch, decided once: the sizing pass allocates from it, the launch pass launches from it.
 enum AttnKernel { kAttnPP, kAttnPPBias, kAttnPPTiles, kAttnPipe8, kAttnPipe4, kAttnP3W8, kAttnP3W4, kAttnP1W8, kAttnP1W4, kAttnP2W8, kAttnP2W4,
@@ -1612,7 +1634,9 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
   const AttnKernelInfo& ki = kAttnKernels[pl.kernel];
   const int nsplit = pl.nsplit;
   const int ldvt = rup(Lk, 64);
-  T vt = talloc(e, (ap.prec ? 2 : 1) * B, heads, D, ldvt, 0);      // precise: V^T_hi planes of all images, then V^T_lo
+  if (ap.shared_kv && (D != 64 || pl.pv_split || ldk != 64)) SDM_FAIL(e, SDM_ERR_INVALID, "attention: a shared key / value operand is [key][64] at head dim 64, without the residual terms of P.V");
+  T vt;
+  if (!ap.shared_kv) vt = talloc(e, (ap.prec ? 2 : 1) * B, heads, D, ldvt, 0);      // precise: V^T_hi planes of all images, then V^T_lo
   const int ntiles64 = sdm_cdiv(Lk, 64);
   T tl_own, part_o, part_ml;
   if (pl.own_list) tl_own = talloc(e, B, 1, 1, ntiles64 + 1, 1);
@@ -1626,19 +1650,22 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
       tiles = (const int*)tl_own.p;
     }
     if (!pl.walk_tiles) tiles = nullptr;
-    const long vt_hs = (long)D * ldvt, vt_bs = (long)heads * vt_hs;
-    prof_begin(e, "transpose_v", 0, (double)B * Lk * heads * D * 4);
-    SDM_LAUNCH(transpose_v_kernel, dim3(ldvt / 64, heads * (D / 64), B), dim3(256), 0, e->stream, v, (long)Lk * ldv, ldv, (half_t*)vt.p, vt_bs,
-               vt_hs, ldvt, Lk, D);
-    if (pl.pv_split)
-      SDM_LAUNCH(transpose_v_kernel, dim3(ldvt / 64, heads * (D / 64), B), dim3(256), 0, e->stream, v + ap.v_lo, (long)Lk * ldv, ldv,
-                 (half_t*)vt.p + (size_t)B * vt_bs, vt_bs, vt_hs, ldvt, Lk, D);
-    prof_end(e);
+    const long vt_hs = ap.shared_kv ? 0 : (long)D * ldvt, vt_bs = ap.shared_kv ? (long)D * ldvt : (long)heads * vt_hs;
+    if (!ap.shared_kv) {
+      prof_begin(e, "transpose_v", 0, (double)B * Lk * heads * D * 4);
+      count_kernel("transpose_v");
+      SDM_LAUNCH(transpose_v_kernel, dim3(ldvt / 64, heads * (D / 64), B), dim3(256), 0, e->stream, v, (long)Lk * ldv, ldv, (half_t*)vt.p, vt_bs,
+                 vt_hs, ldvt, Lk, D);
+      if (pl.pv_split)
+        SDM_LAUNCH(transpose_v_kernel, dim3(ldvt / 64, heads * (D / 64), B), dim3(256), 0, e->stream, v + ap.v_lo, (long)Lk * ldv, ldv,
+                   (half_t*)vt.p + (size_t)B * vt_bs, vt_bs, vt_hs, ldvt, Lk, D);
+      prof_end(e);
+    }
     AttnParams p;
     memset(&p, 0, sizeof(p));
     p.q = q; p.q_bs = (long)Lq * ldq; p.ldq = ldq;
-    p.k = k; p.k_bs = (long)Lk * ldk; p.ldk = ldk;
-    p.vt = (const half_t*)vt.p; p.vt_bs = vt_bs; p.vt_hs = vt_hs; p.ldvt = ldvt;
+    p.k = k; p.k_bs = (long)Lk * ldk; p.ldk = ldk; p.k_hs = ap.shared_kv ? 0 : 64;
+    p.vt = ap.shared_kv ? v : (const half_t*)vt.p; p.vt_bs = vt_bs; p.vt_hs = vt_hs; p.ldvt = ldvt;
     p.bias = bias_l2; p.bias_bs = Lk;
     p.tiles = tiles; p.tiles_bs = ntiles64 + 1;
     p.o = (half_t*)out; p.o_bs = (long)Lq * ldo; p.ldo = ldo; p.o_f32 = ap.out_f32;
@@ -1694,7 +1721,7 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
   }
   if (nsplit > 1) { tfree(e, part_ml); tfree(e, part_o); }
   if (pl.own_list) tfree(e, tl_own);
-  tfree(e, vt);
+  if (!ap.shared_kv) tfree(e, vt);
   return 0;
 }
 
@@ -1883,17 +1910,89 @@ static int vae_attention(sdm_ctx* e, const VaeAttnB& a, const T& x, T* out) {
 
 // Transformer2DModel + BasicTransformerBlock (Appendix A.7); masked: the self-attention takes the level's key bias [N][L] (log2 domain) and its list of
 // active key tiles (bias / tiles: null in the sizing pass, which has no memory)
-static int transformer(sdm_ctx* e, const TfB& t, const T& x, const T& uin, bool masked, const float* bias, const int* tiles, T* out) {
+// plane format of the U-Net attentions' q | k | v: 0 fp16 rows, 2 fp16 hi | lo planes, 3 fp16 hi + e5m2 pair plane (the default precision)
+static int unet_attn_plane_fmt(const sdm_ctx* e) { return (e->cfg.precise_mask & SDM_PRECISE_UNET_ATTN) ? (attn_f8_enabled() ? 3 : 2) : 0; }
+
+// The key / value operand that every cross-attention of a forward shares (fold_cross_kv, cross_patch_planes_kernel): built once in front of the first
+// transformer block, freed behind the last.  k: [2][B][Lk][64] halves - the fp16 plane of all images, then their pair plane; vt: [B][64][ldvt].
+// The rule (`on`): option cross_shared != 0, the fp8-pair plane format (unet_attn_plane_fmt == 3: the default precision) and an fp32 U-Net input.  Every
+// other precision mode - the fp16 fast mode and the fp16 hi | lo planes of attn_f8 = 0 - keeps each block's own kv_folded conv + transpose.
+struct CrossPlanes { bool on = false; T k, vt; };
+static int cross_planes_build(sdm_ctx* e, const T& uin, CrossPlanes* cp) {
+  cp->on = opt("cross_shared") != 0 && unet_attn_plane_fmt(e) == 3 && uin.f32 == 1 && uin.C == 16;
+  if (!cp->on) return 0;
+  const int B = uin.N, Lk = uin.H * uin.W, ldvt = rup(Lk, 64);
+  cp->k = talloc(e, 2 * B, 1, Lk, 64, 0);
+  cp->vt = talloc(e, B, 1, 64, ldvt, 0);
+  if (e->dry) return 0;
+  prof_begin(e, "cross_patch_planes", 0, (double)B * Lk * (16.0 + 64 * 6));
+  count_kernel("cross_patch_planes");
+  const long nthr = std::max((long)B * Lk * 8, (long)B * 64 * (ldvt / 8));
+  SDM_LAUNCH(cross_patch_planes_kernel, dim3((unsigned)((nthr + 255) / 256), 2, 1), dim3(256), 0, e->stream, (const float*)uin.p, B, uin.H, uin.W,
+             (half_t*)cp->k.p, (half_t*)cp->k.p + (size_t)B * Lk * 64, (half_t*)cp->vt.p, ldvt);
+  prof_end(e);
+  return 0;
+}
+static void cross_planes_free(sdm_ctx* e, CrossPlanes* cp) {
+  if (!cp->on) return;
+  tfree(e, cp->vt); tfree(e, cp->k);
+}
+
+// plane-fed GEMMs (k_gemm.h) for every Linear of a transformer block, or for none
+static bool transformer_p3(sdm_ctx* e, const TfB& t, int pf) {
+  bool p3 = e->cfg.stream_f32 == 1 && pf == 3 && t.C % 32 == 0;
+  for (int l : {t.proj_in, t.qkv1, t.o1, t.q2, t.o2, t.q2s, t.o2s, t.ff1, t.ff2, t.proj_out}) p3 = p3 && p3_ok(e, e->convs[l]);
+  return p3;
+}
+
+// The cross-attention of a transformer block, from the normalised hidden state `n` (the block's operand format) to to_out + residual `res` -> *out (freed by the
+// caller; `n` is freed here).  cp.on: Q~ = q_shared(n) attends to the shared operand, out_shared maps the 36 live columns per head back; otherwise
+// to_q, the block's own kv_folded conv of the latent (+ transpose_v inside the operator), to_out.0.
+static int cross_attention(sdm_ctx* e, const TfB& t, T& n, const T& uin, const CrossPlanes& cp, int pf, bool p3, bool p3a, const T* res, T* out) {
+  const int C = t.C, N = n.N, H = n.H, W = n.W, L = H * W, L0 = uin.H * uin.W, sf = e->cfg.stream_f32;
+  const int pa = pf ? 1 : 0;
+  const bool need_vlo = pf == 2 && opt("attn_pv_split") != 0;
+  T q2, kv, ao;
+  TRY(linear(e, cp.on ? t.q2s : t.q2, n, &q2, C, pf));
+  tfree(e, n);
+  if (!cp.on) TRY(conv_simple(e, t.kv2, uin, &kv, 2 * C, pf, 1, 0, 0, nullptr, 1.0f, false, need_vlo ? -1 : C));      // folded aux_conv_in + to_k|to_v: tokens = latent pixels, row-major
+  ao = talloc(e, N, H, W, C, p3a ? kFmtP3 : e->act_f32);
+  {
+    AttnPrec ap; ap.prec = pa ? pf - 1 : 0; ap.out_f32 = p3a ? 1 : ao.f32; ap.out_p3 = p3a ? 1 : 0;
+    ap.q_lo = (long)q2.rows() * q2.C;
+    if (cp.on) {
+      const half_t* kk = (const half_t*)cp.k.p;
+      ap.shared_kv = true; ap.k_lo = (long)N * L0 * 64;
+      TRY(op_attention_raw(e, (const half_t*)q2.p, C, kk, 64, (const half_t*)cp.vt.p, 64, nullptr, N, t.heads, L, L0, 64, ao.p, C, true, nullptr, ap));
+    } else {
+      const half_t* kk = (const half_t*)kv.p;
+      ap.k_lo = ap.v_lo = (long)kv.rows() * kv.C;
+      TRY(op_attention_raw(e, (const half_t*)q2.p, C, kk, 2 * C, kk ? kk + C : nullptr, 2 * C, nullptr, N, t.heads, L, L0, 64, ao.p, C, true, nullptr, ap));
+    }
+  }
+  tfree(e, q2);
+  if (!cp.on) tfree(e, kv);
+  if (p3 && !p3a) {      // the attention output as the next GEMM's operand
+    T ap3;
+    TRY(op_to_p3(e, ao, &ap3));
+    tfree(e, ao);
+    ao = ap3;
+  }
+  TRY(linear(e, cp.on ? t.o2s : t.o2, ao, out, C, sf, res));
+  tfree(e, ao);
+  return 0;
+}
+
+static int transformer(sdm_ctx* e, const TfB& t, const T& x, const T& uin, const CrossPlanes& cp, bool masked, const float* bias, const int* tiles, T* out) {
   const int sf = e->cfg.stream_f32;
-  const int C = t.C, L = x.H * x.W, L0 = uin.H * uin.W;
-  T hn, h, n, qkv, ao, h2, q2, kv, f;
-  const int pa = (e->cfg.precise_mask & SDM_PRECISE_UNET_ATTN) ? 1 : 0;      // split-precision attention cores: q|k|v as hi|lo planes
-  const int pf = pa ? (attn_f8_enabled() ? 3 : 2) : 0;         // plane format of q | k | v; SDM_ATTN_PV_SPLIT=1 (fully split P.V, test hook) needs V_lo too
+  const int C = t.C, L = x.H * x.W;
+  T hn, h, n, qkv, ao, h2, f;
+  const int pf = unet_attn_plane_fmt(e);                        // plane format of q | k | v; SDM_ATTN_PV_SPLIT=1 (fully split P.V, test hook) needs V_lo too
+  const int pa = pf ? 1 : 0;                                   // split-precision attention cores: q|k|v as hi|lo planes
   const bool need_vlo = pf == 2 && opt("attn_pv_split") != 0;
   // plane-fed GEMMs (k_gemm.h): every Linear of the block takes a P3 operand written by its producer - GroupNorm apply, LayerNorm, the GEGLU and
   // ff.net.2 epilogues - or, behind the attention cores (fp32 output), by one conversion pass
-  bool p3 = sf == 1 && pf == 3 && C % 32 == 0;
-  for (int l : {t.proj_in, t.qkv1, t.o1, t.q2, t.o2, t.ff1, t.ff2, t.proj_out}) p3 = p3 && p3_ok(e, e->convs[l]);
+  const bool p3 = transformer_p3(e, t, pf);
   const int nf = p3 ? kFmtP3 : -1;                             // operand format of the norms' outputs (-1: the engine's activation type)
   const bool p3a = p3 && L % 32 == 0 && opt("gemm_p3_attn") != 0;                           // the attention cores write the planes themselves (O^T accumulators = the GEMM's operand layout)
   auto attn_out = [&](T& a) -> int {                           // the attention output as the next GEMM's operand
@@ -1924,20 +2023,8 @@ static int transformer(sdm_ctx* e, const TfB& t, const T& x, const T& uin, bool 
   tfree(e, ao); tfree(e, h);
   // cross-attention to the trimap-latent tokens
   TRY(op_ln(e, e->norms[t.ln2], h2, e->cfg.unet_ln_eps, &n, nf));
-  TRY(linear(e, t.q2, n, &q2, C, pf));
-  tfree(e, n);
-  TRY(conv_simple(e, t.kv2, uin, &kv, 2 * C, pf, 1, 0, 0, nullptr, 1.0f, false, need_vlo ? -1 : C));      // folded aux_conv_in + to_k|to_v: tokens = latent pixels, row-major
-  ao = talloc(e, x.N, x.H, x.W, C, p3a ? kFmtP3 : e->act_f32);
-  {
-    const half_t* kk = (const half_t*)kv.p;
-    AttnPrec ap; ap.prec = pa ? pf - 1 : 0; ap.out_f32 = p3a ? 1 : ao.f32; ap.out_p3 = p3a ? 1 : 0;
-    ap.q_lo = (long)q2.rows() * q2.C; ap.k_lo = ap.v_lo = (long)kv.rows() * kv.C;
-    TRY(op_attention_raw(e, (const half_t*)q2.p, C, kk, 2 * C, kk ? kk + C : nullptr, 2 * C, nullptr, x.N, t.heads, L, L0, 64, ao.p, C, true, nullptr, ap));
-  }
-  tfree(e, q2); tfree(e, kv);
-  TRY(attn_out(ao));
-  TRY(linear(e, t.o2, ao, &h, C, sf, &h2));
-  tfree(e, ao); tfree(e, h2);
+  TRY(cross_attention(e, t, n, uin, cp, pf, p3, p3a, &h2, &h));
+  tfree(e, h2);
   // GEGLU feed-forward
   TRY(op_ln(e, e->norms[t.ln3], h, e->cfg.unet_ln_eps, &n, nf));
   TRY(linear(e, t.ff1, n, &f, 4 * C, p3 ? kFmtP3 : e->act_f32));
@@ -2148,6 +2235,8 @@ static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bia
   const int sf = c.stream_f32;
   std::vector<T> skips;
   T h, t;
+  CrossPlanes cp;
+  TRY(cross_planes_build(e, uin, &cp));
   TRY(conv_simple(e, e->u_conv_in, uin, &h, c.unet_channels[0], sf, 1, 0, 0, nullptr, 1.0f, true));
   skips.push_back(h);
   for (int i = 0; i < 4; ++i) {
@@ -2155,7 +2244,7 @@ static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bia
       TRY(resblock(e, e->u_down_res[i][j], h, nullptr, eps, &t));
       if (i < 3) {
         T t2;
-        TRY(transformer(e, e->u_down_tf[i][j], t, uin, masked, bias_lvl[i], tiles_lvl[i], &t2));
+        TRY(transformer(e, e->u_down_tf[i][j], t, uin, cp, masked, bias_lvl[i], tiles_lvl[i], &t2));
         tfree(e, t); t = t2;
       }
       h = t;                       // previous h stays alive as a skip
@@ -2169,7 +2258,7 @@ static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bia
   }
   // mid (h aliases the last skip: do not free it here)
   TRY(resblock(e, e->u_mid0, h, nullptr, eps, &t)); h = t;
-  TRY(transformer(e, e->u_midtf, h, uin, masked, bias_lvl[3], tiles_lvl[3], &t)); tfree(e, h); h = t;
+  TRY(transformer(e, e->u_midtf, h, uin, cp, masked, bias_lvl[3], tiles_lvl[3], &t)); tfree(e, h); h = t;
   TRY(resblock(e, e->u_mid1, h, nullptr, eps, &t)); tfree(e, h); h = t;
   for (int i = 0; i < 4; ++i) {
     for (size_t j = 0; j < e->u_up_res[i].size(); ++j) {
@@ -2177,7 +2266,7 @@ static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bia
       TRY(resblock(e, e->u_up_res[i][j], h, &s, eps, &t));   // cat([h, skip], dim=1) then ResBlock (replace.py:509-536)
       tfree(e, h); tfree(e, s); h = t;
       if (i > 0) {
-        TRY(transformer(e, e->u_up_tf[i][j], h, uin, masked, bias_lvl[3 - i], tiles_lvl[3 - i], &t));
+        TRY(transformer(e, e->u_up_tf[i][j], h, uin, cp, masked, bias_lvl[3 - i], tiles_lvl[3 - i], &t));
         tfree(e, h); h = t;
       }
     }
@@ -2187,6 +2276,7 @@ static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bia
   *out = talloc(e, h.N, h.H, h.W, 16, e->act_f32);
   { ConvArgs a; a.out = out; a.out_scale = 1.0f / c.vae_scaling_factor; TRY(gn_conv(e, e->norms[e->u_norm_out], e->convs[e->u_conv_out], h, nullptr, 1, eps, a)); }
   tfree(e, h);
+  cross_planes_free(e, &cp);
   return 0;
 }
 
@@ -2693,6 +2783,10 @@ int sdm_load_tensor(sdm_ctx* e, const char* name, int dtype, int ndim, const int
     SDM_CHECK_DEV(e, dev_memcpy_h2d(e->stage, src, n * 4, e->stream));
     dsrc = (float*)e->stage;
 #endif
+    if (s.host_too) {
+      float* dst = e->hostblob.data() + s.host_off;
+      for (size_t i = 0; i < n; ++i) dst[i] = to_f32(host_ptr, dtype, i);
+    }
     if (s.kind == SLOT_CONV_W) {
       pack_layer_weight(e, e->convs[s.layer], dsrc, (int)s.shape[0], (int)s.shape[1], s.ci_off, s.co_off, s.w_scale);
     } else if (s.kind == SLOT_CONV_B) {
@@ -2713,6 +2807,79 @@ int sdm_load_tensor(sdm_ctx* e, const char* name, int dtype, int ndim, const int
 }
 
 // Exact fold of aux_conv_in into every cross-attention K|V projection; fp64 accumulation on the host.
+//   kv_folded: K = P.Ak + 1.bk^T, V = P.Av + 1.bv^T with P the [Lk][36] patch matrix of the trimap latent (j = ci*9 + tap), Ak[j][o] = wf[o][j] = W_k . W_aux.
+// One step further (the shared-operand form, option cross_shared): per head h the logits are Q_h K_h^T = (Q_h Ak_h^T) P^T + (Q_h bk_h) 1^T, whose second
+// term is constant along the keys of a row and cancels in the softmax, exactly; and softmax(S_h) V_h = (softmax(S_h) P) Av_h + bv_h^T because the rows of a
+// softmax sum to 1.  So the attention core can run on K = P, V^T = P^T (36 columns padded to the head dim 64) - the SAME operand for every head of every block,
+// built once per forward (cross_patch_planes_kernel) - between two Linears of unchanged shape:
+//   q_shared   [h*64 + j][c] = s . sum_d wf_k[h*64 + d][j] . Wq[h*64 + d][c]   (j < 36, else 0; s = the logit scale that w_scale folds into to_q; no bias)
+//   out_shared [c][h*64 + j] = sum_d Wo[c][h*64 + d] . wf_v[h*64 + d][j]       (j < 36, else 0),  bias b_o[c] + sum_{h,d} Wo[c][h*64 + d] . bv[h*64 + d]
+struct CrossFold { std::vector<float> wf, bf, wq, wo, bo; };
+static void fold_cross_block(const sdm_ctx* e, const TfB& t, const std::vector<double>& wa, const std::vector<double>& ba, CrossFold& f) {
+  const int ctx = e->cfg.cross_attention_dim, C = t.C;
+  const float* H = e->hostblob.data();
+  std::vector<double> wfd((size_t)2 * C * 36), bfd((size_t)2 * C);
+  for (int o = 0; o < 2 * C; ++o) {
+    const float* wrow = H + (o < C ? t.k_hoff + (size_t)o * ctx : t.v_hoff + (size_t)(o - C) * ctx);
+    double b = 0.0;
+    for (int m = 0; m < ctx; ++m) b += (double)wrow[m] * ba[m];
+    bfd[o] = b;                                                  // W_k . b_aux   (to_k / to_v have no bias of their own)
+    for (int j = 0; j < 36; ++j) {                               // j = ci*9 + tap (OIHW order of aux_conv_in.weight)
+      const double* wj = wa.data() + (size_t)j * ctx;
+      double acc = 0.0;
+      for (int m = 0; m < ctx; ++m) acc += (double)wrow[m] * wj[m];
+      wfd[(size_t)o * 36 + j] = acc;
+    }
+  }
+  f.wf.resize(wfd.size()); f.bf.resize(bfd.size());
+  for (size_t i = 0; i < wfd.size(); ++i) f.wf[i] = (float)wfd[i];
+  for (size_t i = 0; i < bfd.size(); ++i) f.bf[i] = (float)bfd[i];
+  const float* Wq = H + t.q_hoff;
+  const float* Wo = H + t.o_hoff;
+  const double s = (double)(0.125f * SDM_LOG2E);
+  f.wq.assign((size_t)C * C, 0.f); f.wo.assign((size_t)C * C, 0.f); f.bo.assign((size_t)C, 0.f);
+  std::vector<double> acc((size_t)C);
+  for (int h = 0; h < t.heads; ++h)
+    for (int j = 0; j < 36; ++j) {
+      std::fill(acc.begin(), acc.end(), 0.0);
+      for (int d = 0; d < 64; ++d) {
+        const double a = wfd[(size_t)(h * 64 + d) * 36 + j];
+        const float* row = Wq + (size_t)(h * 64 + d) * C;
+        for (int c = 0; c < C; ++c) acc[c] += a * (double)row[c];
+      }
+      float* dst = f.wq.data() + (size_t)(h * 64 + j) * C;
+      for (int c = 0; c < C; ++c) dst[c] = (float)(s * acc[c]);
+    }
+  for (int c = 0; c < C; ++c) {
+    const float* row = Wo + (size_t)c * C;
+    double b = (double)H[t.ob_hoff + c];
+    for (int hd = 0; hd < C; ++hd) b += (double)row[hd] * bfd[(size_t)C + hd];
+    f.bo[c] = (float)b;
+    for (int h = 0; h < t.heads; ++h) {
+      double a36[36] = {0.0};
+      for (int d = 0; d < 64; ++d) {
+        const double w = (double)row[h * 64 + d];
+        const double* v = wfd.data() + (size_t)(C + h * 64 + d) * 36;
+        for (int j = 0; j < 36; ++j) a36[j] += w * v[j];
+      }
+      for (int j = 0; j < 36; ++j) f.wo[(size_t)c * C + h * 64 + j] = (float)a36[j];
+    }
+  }
+}
+static int upload_folded(sdm_ctx* e, ConvL& L, const std::vector<float>& w, int O, int I, int ci_off, const std::vector<float>* bias) {
+  if (ensure_buf(e, &e->stage, &e->stage_bytes, std::max(w.size() * 4, (size_t)1 << 20)) != 0) return SDM_ERR_NOMEM;
+  SDM_CHECK_DEV(e, dev_memset(L.w, 0, L.w_bytes(), e->stream));
+  if (L.w_lo) SDM_CHECK_DEV(e, dev_memset(L.w_lo, 0, L.w_bytes(), e->stream));
+  SDM_CHECK_DEV(e, dev_memcpy_h2d(e->stage, w.data(), w.size() * 4, e->stream));
+  pack_layer_weight(e, L, (const float*)e->stage, O, I, ci_off, 0, 1.0f);
+  SDM_CHECK_DEV(e, dev_sync(e->stream));
+  if (bias) {
+    SDM_CHECK_DEV(e, dev_memcpy_h2d(e->stage, bias->data(), bias->size() * 4, e->stream));
+    pack_layer_bias(e, L, (const float*)e->stage, O, 0);
+    SDM_CHECK_DEV(e, dev_sync(e->stream));
+  }
+  return 0;
+}
 static int fold_cross_kv(sdm_ctx* e) {
   const sdm_config& c = e->cfg;
   const int ctx = c.cross_attention_dim;
@@ -2727,33 +2894,26 @@ static int fold_cross_kv(sdm_ctx* e) {
   for (auto& v : e->u_down_tf) for (auto& t : v) blocks.push_back(&t);
   blocks.push_back(&e->u_midtf);
   for (auto& v : e->u_up_tf) for (auto& t : v) blocks.push_back(&t);
-  std::vector<float> wf, bf;
-  for (const TfB* t : blocks) {
+  // the blocks are independent (about 1.3 G fp64 multiply-adds at the full architecture): spread over a few host threads, uploaded in order afterwards
+  std::vector<CrossFold> folds(blocks.size());
+  {
+    const unsigned hw = std::thread::hardware_concurrency();
+    const size_t nthr = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(hw ? hw : 1, 8), blocks.size()));
+    std::atomic<size_t> next{0};
+    auto work = [&]() { for (size_t i; (i = next.fetch_add(1)) < blocks.size();) fold_cross_block(e, *blocks[i], wa, ba, folds[i]); };
+    std::vector<std::thread> pool;
+    for (size_t i = 1; i < nthr; ++i) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+  }
+  for (size_t i = 0; i < blocks.size(); ++i) {
+    const TfB* t = blocks[i];
     const int C = t->C;
-    ConvL& L = e->convs[t->kv2];
-    wf.assign((size_t)2 * C * 36, 0.f); bf.assign((size_t)2 * C, 0.f);
-    for (int o = 0; o < 2 * C; ++o) {
-      const float* wrow = H + (o < C ? t->k_hoff + (size_t)o * ctx : t->v_hoff + (size_t)(o - C) * ctx);
-      double b = 0.0;
-      for (int m = 0; m < ctx; ++m) b += (double)wrow[m] * ba[m];
-      bf[o] = (float)b;                                            // W_k . b_aux   (to_k / to_v have no bias of their own)
-      for (int j = 0; j < 36; ++j) {                               // j = ci*9 + tap (OIHW order of aux_conv_in.weight)
-        const double* wj = wa.data() + (size_t)j * ctx;
-        double acc = 0.0;
-        for (int m = 0; m < ctx; ++m) acc += (double)wrow[m] * wj[m];
-        wf[(size_t)o * 36 + j] = (float)acc;
-      }
-    }
-    // upload as an OIHW [2C][4][3][3] tensor; the 4 latent channels sit at channels 4..7 of the 16-channel U-Net input
-    if (ensure_buf(e, &e->stage, &e->stage_bytes, std::max(wf.size() * 4, (size_t)1 << 20)) != 0) return SDM_ERR_NOMEM;
-    SDM_CHECK_DEV(e, dev_memset(L.w, 0, L.w_bytes(), e->stream));
-    if (L.w_lo) SDM_CHECK_DEV(e, dev_memset(L.w_lo, 0, L.w_bytes(), e->stream));
-    SDM_CHECK_DEV(e, dev_memcpy_h2d(e->stage, wf.data(), wf.size() * 4, e->stream));
-    pack_layer_weight(e, L, (const float*)e->stage, 2 * C, 4, 4, 0, 1.0f);
-    SDM_CHECK_DEV(e, dev_sync(e->stream));
-    SDM_CHECK_DEV(e, dev_memcpy_h2d(e->stage, bf.data(), bf.size() * 4, e->stream));
-    pack_layer_bias(e, L, (const float*)e->stage, 2 * C, 0);
-    SDM_CHECK_DEV(e, dev_sync(e->stream));
+    // kv_folded: uploaded as an OIHW [2C][4][3][3] tensor; the 4 latent channels sit at channels 4..7 of the 16-channel U-Net input
+    TRY(upload_folded(e, e->convs[t->kv2], folds[i].wf, 2 * C, 4, 4, &folds[i].bf));
+    TRY(upload_folded(e, e->convs[t->q2s], folds[i].wq, C, C, 0, nullptr));
+    TRY(upload_folded(e, e->convs[t->o2s], folds[i].wo, C, C, 0, &folds[i].bo));
+    folds[i] = CrossFold();
   }
   return 0;
 }

@@ -412,6 +412,7 @@ float sdm_bench_attn(sdm_ctx* e, int B, int heads, int Lq, int Lk, int qt, int a
   AttnParams p;
   memset(&p, 0, sizeof(p));
   p.q = (const half_t*)q.p; p.q_bs = (long)Lq * C; p.ldq = C; p.k = (const half_t*)k.p; p.k_bs = (long)Lk * C; p.ldk = C;
+  p.k_hs = 64;
   p.vt = (const half_t*)vt.p; p.vt_hs = (long)64 * ldvt; p.vt_bs = heads * p.vt_hs; p.ldvt = ldvt; p.o = (half_t*)o.p; p.o_bs = (long)Lq * C; p.ldo = C;
   p.Lq = Lq; p.Lk = Lk; p.scale_log2e = 0.125f * SDM_LOG2E; p.ablate = ablate;
   if (prec) { p.q_lo = (long)B * Lq * C; p.k_lo = (long)B * Lk * C; p.vt_lo = (long)B * p.vt_bs; p.o_f32 = 1; }
@@ -533,6 +534,78 @@ int sdm_op_attention_split_ex(sdm_ctx* e, const float* q, const float* k, const 
     if (out_p3 == 2) tfree(e, pl);
     if (out_p3) tfree(e, to);
     tfree(e, vp); tfree(e, kp); tfree(e, qp); tfree(e, b2);
+    return 0;
+  });
+}
+
+/* The shared key / value operand of the cross-attentions (cross_patch_planes_kernel) of a U-Net input tensor uin fp32 [B][H][W][16] (DEVICE; the trimap latent
+ * at channels 4..7): k_hi [B][H*W][64] fp16, k_pair the same number of bytes (the e5m2 pair plane), vt [B][64][rup(H*W, 64)] fp16.  Test hook. */
+int sdm_op_cross_patch_planes(sdm_ctx* e, const float* uin, int B, int H, int W, void* k_hi, void* k_pair, void* vt) {
+  if (e) dev_use(e->device);
+  if (!e || !uin || !k_hi || !k_pair || !vt || B < 1 || H < 1 || W < 1) return SDM_ERR_INVALID;
+  const int Lk = H * W, ldvt = rup(Lk, 64);
+  const long nthr = std::max((long)B * Lk * 8, (long)B * 64 * (ldvt / 8));
+  count_kernel("cross_patch_planes");
+  SDM_LAUNCH(cross_patch_planes_kernel, dim3((unsigned)((nthr + 255) / 256), 2, 1), dim3(256), 0, e->stream, uin, B, H, W, (half_t*)k_hi, (half_t*)k_pair, (half_t*)vt, ldvt);
+  SDM_CHECK_DEV(e, dev_sync(e->stream));
+  return 0;
+}
+
+/* sdm_op_attention_split on ONE key / value operand for every head (AttnPrec::shared_kv: head stride 0 for K and V^T, no V^T scratch, no transpose_v launch
+ * inside the operator): q fp32 [B,Lq,heads*64], ks / vs fp32 [B,Lk,64]; q_prescaled != 0: the logit scale is in q already; fp32 output [B,Lq,heads*64].
+ * Needs the fp8-pair plane format (options attn_f8 = 1, attn_pv_split = 0).  Test hook. */
+int sdm_op_attention_shared(sdm_ctx* e, const float* q, const float* ks, const float* vs, int B, int heads, int Lq, int Lk, int q_prescaled, float* out) {
+  if (e) dev_use(e->device);
+  if (!e || !q || !ks || !vs || !out) return SDM_ERR_INVALID;
+  if (!attn_f8_enabled() || opt("attn_pv_split")) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_attention_shared: the fp8-pair plane format only");
+  const int C = heads * 64, ldvt = rup(Lk, 64);
+  return run_two_pass(e, [&]() -> int {
+    T qp = talloc(e, B, 1, Lq, C, 3), kp = talloc(e, B, 1, Lk, 64, 3), vp = talloc(e, B, 1, Lk, 64, 2), vt = talloc(e, B, 1, 64, ldvt, 0);
+    const long nq = (long)B * Lq * C, nk = (long)B * Lk * 64;
+    if (!e->dry) {
+      SDM_LAUNCH(split_planes_kernel, dim3((unsigned)((nq / 4 + 255) / 256)), dim3(256), 0, e->stream, q, (half_t*)qp.p, (half_t*)qp.p + nq, nq,
+                 q_prescaled ? 1.0f : 0.125f * SDM_LOG2E, 3);
+      SDM_LAUNCH(split_planes_kernel, dim3((unsigned)((nk / 4 + 255) / 256)), dim3(256), 0, e->stream, ks, (half_t*)kp.p, (half_t*)kp.p + nk, nk, 1.0f, 3);
+      SDM_LAUNCH(split_planes_kernel, dim3((unsigned)((nk / 4 + 255) / 256)), dim3(256), 0, e->stream, vs, (half_t*)vp.p, (half_t*)vp.p + nk, nk, 1.0f, 2);
+      SDM_LAUNCH(transpose_v_kernel, dim3(ldvt / 64, 1, B), dim3(256), 0, e->stream, (const half_t*)vp.p, (long)Lk * 64, 64, (half_t*)vt.p, (long)64 * ldvt,
+                 (long)64 * ldvt, ldvt, Lk, 64);
+    }
+    AttnPrec ap; ap.prec = 2; ap.q_lo = nq; ap.k_lo = nk; ap.out_f32 = 1; ap.shared_kv = true;
+    TRY(op_attention_raw(e, (const half_t*)qp.p, C, (const half_t*)kp.p, 64, (const half_t*)vt.p, 64, nullptr, B, heads, Lq, Lk, 64, (void*)out, C, true, nullptr, ap));
+    tfree(e, vt); tfree(e, vp); tfree(e, kp); tfree(e, qp);
+    return 0;
+  });
+}
+
+/* The cross-attention of ONE transformer block of the loaded model as the forward runs it under the current options (cross_shared: the shared operand with
+ * q_shared / out_shared, or the block's own kv_folded + to_q / to_out.0): block = "unet.down_blocks.0.attentions.0" etc.; x fp32 [B][H][W][C] (DEVICE) is the
+ * normalised hidden state (the output of norm2), uin fp32 [B][h][w][16] the U-Net input tensor; out fp32 [B][H][W][C] = to_out(attention), no residual.
+ * Needs an engine with fp32 activations and an fp32 stream (the default precision).  Test hook. */
+int sdm_debug_cross_attention(sdm_ctx* e, const char* block, const float* x, int B, int H, int W, const float* uin, int h, int w, float* out) {
+  if (e) dev_use(e->device);
+  if (!e || !block || !x || !uin || !out) return SDM_ERR_INVALID;
+  if (!e->finalized) SDM_FAIL(e, SDM_ERR_STATE, "weights not finalised");
+  if (!e->act_f32 || e->cfg.stream_f32 != 1) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_debug_cross_attention: fp32 activations and stream expected");
+  std::vector<const TfB*> blocks;
+  for (auto& v : e->u_down_tf) for (auto& t : v) blocks.push_back(&t);
+  blocks.push_back(&e->u_midtf);
+  for (auto& v : e->u_up_tf) for (auto& t : v) blocks.push_back(&t);
+  const TfB* tb = nullptr;
+  for (const TfB* t : blocks) if (e->convs[t->q2].name == std::string(block) + ".transformer_blocks.0.attn2.to_q") tb = t;
+  if (!tb) SDM_FAIL(e, SDM_ERR_INVALID, "no transformer block named %s", block);
+  const int C = tb->C;
+  return run_two_pass(e, [&]() -> int {
+    const int pf = unet_attn_plane_fmt(e);
+    const bool p3 = transformer_p3(e, *tb, pf), p3a = p3 && (H * W) % 32 == 0 && opt("gemm_p3_attn") != 0;
+    const T tu = view(uin, B, h, w, 16, 1), tx = view(x, B, H, W, C, 1);
+    CrossPlanes cp;
+    TRY(cross_planes_build(e, tu, &cp));
+    T n = tx, o;
+    if (p3) TRY(op_to_p3(e, tx, &n));
+    TRY(cross_attention(e, *tb, n, tu, cp, pf, p3, p3a, nullptr, &o));
+    if (!e->dry) SDM_CHECK_DEV(e, dev_memcpy_d2d(out, o.p, (size_t)B * H * W * C * 4, e->stream));
+    tfree(e, o);
+    cross_planes_free(e, &cp);
     return 0;
   });
 }

@@ -85,7 +85,7 @@ EXPORTS = [
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
-    "sdm_op_mask_bias",
+    "sdm_op_mask_bias", "sdm_op_cross_patch_planes", "sdm_op_attention_shared", "sdm_debug_cross_attention",
     "sdm_set_option", "sdm_get_option", "sdm_reset_options", "sdm_option_name", "sdm_option_help", "sdm_kernel_counts", "sdm_kernel_counts_reset",
 ]
 
@@ -157,6 +157,9 @@ class Bindings:
             "sdm_debug_attn_plan": (i32, [i32] * 10 + [C.c_char_p, i32, C.POINTER(i32)]),
             "sdm_op_resize_aa": (i32, [vp, vp, i32, i32, i32, vp, i32, i32]),
             "sdm_op_mask_bias": (i32, [vp, vp, i32, i32, i32, vp]),
+            "sdm_op_cross_patch_planes": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+            "sdm_op_attention_shared": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+            "sdm_debug_cross_attention": (i32, [vp, C.c_char_p, vp, i32, i32, i32, vp, i32, i32, vp]),
             "sdm_set_option": (i32, [C.c_char_p, i32]),
             "sdm_get_option": (i32, [C.c_char_p, C.POINTER(i32)]),
             "sdm_reset_options": (None, []),
@@ -972,6 +975,37 @@ class Engine:
         self._check(self.lib.sdm_op_attention_split_ex(self.h, _ptr(qf), _ptr(kf), _ptr(vf), _ptr(bias), _ptr(tl), B, heads, Lq, Lk, int(out_p3),
                                                        _ptr(out), _ptr(raw)), "sdm_op_attention_split_ex")
         return (out, raw) if raw is not None else out
+
+    def op_cross_patch_planes(self, uin):
+        """Test hook: the shared cross-attention operand of a U-Net input tensor uin fp32 [B,H,W,16] (trimap latent at channels 4..7) ->
+        (k_hi fp16 [B,H*W,64], k_pair uint8 [B,H*W,64,2], vt fp16 [B,64,ceil(H*W/64)*64])."""
+        B, H, W_, _ = uin.shape
+        L = H * W_
+        ldvt = (L + 63) // 64 * 64
+        x = uin.float().contiguous()
+        k_hi = torch.full((B, L, 64), 7.0, dtype=torch.float16, device=x.device)
+        k_pair = torch.full((B, L, 64, 2), 7, dtype=torch.uint8, device=x.device)
+        vt = torch.full((B, 64, ldvt), 7.0, dtype=torch.float16, device=x.device)
+        self._check(self.lib.sdm_op_cross_patch_planes(self.h, _ptr(x), B, H, W_, _ptr(k_hi), _ptr(k_pair), _ptr(vt)), "sdm_op_cross_patch_planes")
+        return k_hi, k_pair, vt
+
+    def op_attention_shared(self, q, ks, vs, heads, q_prescaled=False):
+        """Test hook: op_attention_split on ONE key / value operand ks / vs fp32 [B,Lk,64] for every head (head stride 0 for K and V^T)."""
+        B, Lq, HD = q.shape
+        Lk = ks.shape[1]
+        qf, kf, vf = q.float().contiguous(), ks.float().contiguous(), vs.float().contiguous()
+        out = torch.empty(B, Lq, HD, dtype=torch.float32, device=q.device)
+        self._check(self.lib.sdm_op_attention_shared(self.h, _ptr(qf), _ptr(kf), _ptr(vf), B, heads, Lq, Lk, int(q_prescaled), _ptr(out)), "sdm_op_attention_shared")
+        return out
+
+    def debug_cross_attention(self, block, x_nhwc, uin):
+        """Test hook: the cross-attention of one transformer block of the loaded model under the current options: x fp32 [B,H,W,C] = the output of norm2,
+        uin fp32 [B,h,w,16] the U-Net input tensor -> to_out(attention) fp32 [B,H,W,C] (no residual)."""
+        B, H, W_, Cc = x_nhwc.shape
+        x, u = x_nhwc.float().contiguous(), uin.float().contiguous()
+        out = torch.empty(B, H, W_, Cc, dtype=torch.float32, device=x.device)
+        self._check(self.lib.sdm_debug_cross_attention(self.h, block.encode(), _ptr(x), B, H, W_, _ptr(u), u.shape[1], u.shape[2], _ptr(out)), "sdm_debug_cross_attention")
+        return out
 
     def op_resize_aa(self, planes, Hout, Wout):
         P, Hin, Win = planes.shape

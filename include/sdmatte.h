@@ -505,6 +505,15 @@ int sdm_op_attention_split(sdm_ctx* ctx, const float* q, const float* k, const f
  * planes != NULL, the raw planes (ceil(B*Lq/32)*32 * heads*64 * 3 bytes: fp16 hi plane, then the e5m2 xl plane). */
 int sdm_op_attention_split_ex(sdm_ctx* ctx, const float* q, const float* k, const float* v, const float* bias, const int* tiles, int B, int heads, int Lq,
                               int Lk, int out_p3, float* out, void* planes);
+/* Test hooks of the shared cross-attention operand.  sdm_op_cross_patch_planes: the key / value operand of every cross-attention of a forward
+ * from the U-Net input tensor uin fp32 [B][H][W][16] (DEVICE; the trimap latent at channels 4..7) - k_hi [B][H*W][64] fp16 (the 3x3 patch matrix, 36 live columns),
+ * k_pair the same number of bytes (its e5m2 pair plane), vt [B][64][rup(H*W, 64)] fp16 (k_hi transposed, zero filled).  sdm_op_attention_shared:
+ * sdm_op_attention_split on ONE ks / vs fp32 [B,Lk,64] for every head (head stride 0, no transpose inside the operator); q_prescaled != 0: the logit scale
+ * is in q already.  sdm_debug_cross_attention: the cross-attention of one transformer block of the loaded model ("unet.mid_block.attentions.0", ...) under the
+ * current options, from the normalised hidden state x fp32 [B][H][W][C] and the U-Net input uin fp32 [B][h][w][16] to to_out(attention) (no residual). */
+int sdm_op_cross_patch_planes(sdm_ctx* ctx, const float* uin, int B, int H, int W, void* k_hi, void* k_pair, void* vt);
+int sdm_op_attention_shared(sdm_ctx* ctx, const float* q, const float* ks, const float* vs, int B, int heads, int Lq, int Lk, int q_prescaled, float* out);
+int sdm_debug_cross_attention(sdm_ctx* ctx, const char* block, const float* x, int B, int H, int W, const float* uin, int h, int w, float* out);
 /* Test hook: the launch the attention operator would make for these shapes and flags under the current options, on a device of `cus` compute units:
  * the launch-counter name of the kernel (see sdm_kernel_counts) into kernel[cap] and the key split into *nsplit (1 = unsplit).  prec as in the engine:
  * 0 fp16 operands, 1 fp16 hi | lo planes, 2 fp16 + e5m2 pair planes (the default precision); has_bias / has_tiles: a key bias / a caller's tile list
