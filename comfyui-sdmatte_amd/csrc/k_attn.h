@@ -568,9 +568,14 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_d64_kernel(AttnParams p) {
 #define ATTN64PIPE4_KB (2 * 64 * ATTN64_PK + 256)
 #define ATTN64PIPE4_VB (64 * ATTN64_PV)
 #define ATTN64PIPE4_SMEM (2 * ATTN64PIPE4_KB + 3 * ATTN64PIPE4_VB)
-template <int NW>
+// NARROW = 1 (the engine's shared cross-attention operand, sdm_engine.cpp CrossPlanes with `narrow`; Lk % 64 == 0, no bias): the operand has 36 live columns,
+// columns 36..63 of K are zero and V^T rows 59 and 63 hold 1.0 for every key.  Q.K^T then skips its ks = 3 step (K columns 48..63: products with a zero
+// operand) and the denominator is not a fifth accumulator fed by a register of ones but o[1][15] - row 59 of O^T in lanes 0-31, row 63 in lanes 32-63 (the
+// mapping of the epilogue below): the same probabilities summed by the same MFMAs in the same order, so every live output column is bit-identical.
+template <int NW, int NARROW = 0>
 __global__ void __launch_bounds__(64 * NW, 2) attn_d64_pipe_kernel(AttnParams p) {
   constexpr int NTH = 64 * NW, VPT = 512 / NTH;
+  constexpr int NKS = NARROW ? 3 : 4;                                  // 16-channel steps of Q.K^T on the fp16 plane
   constexpr bool SPLITBUF = NW == 4;
   SDM_DYN_SMEM(smem);
   constexpr int PK = ATTN64_PK, PV = ATTN64_PV, BUF = ATTN64P_BUF;
@@ -592,7 +597,7 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_d64_pipe_kernel(AttnParams p)
     if (qrow > p.Lq - 1) qrow = p.Lq - 1;
     const half_t* qp = p.q + (size_t)b * p.q_bs + (size_t)qrow * p.ldq + head * 64 + hi * 8;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const f16x8*)(qp + ks * 16);
+    for (int ks = 0; ks < NKS; ++ks) qf[ks] = *(const f16x8*)(qp + ks * 16);
     const half_t* qb = p.q + (size_t)b * p.q_bs + p.q_lo + (size_t)qrow * p.ldq + head * 64 + hi * 16;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -600,7 +605,7 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_d64_pipe_kernel(AttnParams p)
       q8p[m] = i32x8{r0[1], r0[0], r0[3], r0[2], r1[1], r1[0], r1[3], r1[2]};
     }
   }
-  f32x16 o[2], ls;
+  f32x16 o[2], ls;                                                     // (NARROW: ls and ones are never read - the denominator is o[1][15])
   float m_i = SDM_NEG_BIG;
 #pragma unroll
   for (int r = 0; r < 16; ++r) { ls[r] = 0.0f; o[0][r] = 0.0f; o[1][r] = 0.0f; }
@@ -671,7 +676,7 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_d64_pipe_kernel(AttnParams p)
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
+      for (int ks = 0; ks < NKS; ++ks) {
         const f16x8 a = *(const f16x8*)(Ks + (kt * 32 + l31) * PK + ks * 32 + hi * 16);
         s[kt] = SDM_MFMA_32x32x16_F16(a, qf[ks], s[kt]);
       }
@@ -718,8 +723,10 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_d64_pipe_kernel(AttnParams p)
 #pragma unroll
       for (int r = 0; r < 16; ++r) sc[kt][r] = sdm_exp2(sc[kt][r] - mnew);
     if (__any(alpha != 1.0f)) {
+      if (!NARROW) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) ls[r] *= alpha;
+        for (int r = 0; r < 16; ++r) ls[r] *= alpha;
+      }
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -737,7 +744,7 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_d64_pipe_kernel(AttnParams p)
         f16x8 pf;
 #pragma unroll
         for (int j = 0; j < 8; ++j) pf[j] = (half_t)sc[kt][8 * u + j];
-        ls = SDM_MFMA_32x32x16_F16(ones, pf, ls);
+        if (!NARROW) ls = SDM_MFMA_32x32x16_F16(ones, pf, ls);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
           const unsigned char* vp = Vs + (dt * 32 + l31) * PV + (kt * 32 + 16 * u + 4 * hi) * 2;
@@ -759,11 +766,12 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_d64_pipe_kernel(AttnParams p)
   // epilogue (fp32 output): per-wave staging [32 q][64 d] at pitch 272 B -> coalesced 16-byte row stores
   constexpr int PS = 272;
   unsigned char* stf = smem + wave * (32 * PS);
-  const float inv = p.nsplit > 1 ? 1.0f : 1.0f / ls[0];                 // key split: unnormalised partial sums (attn_combine_kernel divides)
+  const float den = NARROW ? o[1][15] : ls[0];                          // NARROW: the ones row of V^T (59 | 63) this lane's half holds
+  const float inv = p.nsplit > 1 ? 1.0f : 1.0f / den;                   // key split: unnormalised partial sums (attn_combine_kernel divides)
   float* obase = (float*)p.o + (p.nsplit > 1 ? (size_t)sp * p.part_stride : (size_t)0) + (size_t)b * p.o_bs;
   if (p.nsplit > 1 && hi == 0 && q0 + l31 < p.Lq) {
     float* ml = p.part_ml + ((((size_t)sp * p.batch + b) * p.heads + head) * p.Lq + q0 + l31) * 2;
-    ml[0] = m_i; ml[1] = ls[0];
+    ml[0] = m_i; ml[1] = den;
   }
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
@@ -822,8 +830,10 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_d64_pipe_kernel(AttnParams p)
 // ------------------------------------------------------------------------------------------------
 #define ATTN64PP_SLOT (3 * 8192 + 256)
 #define ATTN64PP_SMEM (6 * ATTN64PP_SLOT)
-template <int ABL = 0, int BIAS = 1, int LIST = 1, int KE = 0, int DS = 1, int OB = 1>
+template <int ABL = 0, int BIAS = 1, int LIST = 1, int KE = 0, int DS = 1, int OB = 1, int NARROW = 0>
 __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
+  static_assert(!NARROW || !BIAS, "the narrow form serves the cross-attentions: no key bias");
+  constexpr int NKS = NARROW ? 3 : 4;                                  // 16-channel steps of Q.K^T on the fp16 plane (attn_d64_pipe_kernel: NARROW)
   SDM_DYN_SMEM(smem);
   constexpr int SLOT = ATTN64PP_SLOT, KLO = 8192, VOFF = 16384, BOFF = 24576;
   constexpr int R = KE < 0 ? 4 : 6, D = KE < 0 ? 3 : 4;             // ring slots; a segment of tile t requests tile t + D
@@ -842,7 +852,7 @@ __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
     if (qrow > p.Lq - 1) qrow = p.Lq - 1;
     const half_t* qp = p.q + (size_t)b * p.q_bs + (size_t)qrow * p.ldq + head * 64 + hi * 8;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const f16x8*)(qp + ks * 16);
+    for (int ks = 0; ks < NKS; ++ks) qf[ks] = *(const f16x8*)(qp + ks * 16);
     const half_t* qb = p.q + (size_t)b * p.q_bs + p.q_lo + (size_t)qrow * p.ldq + head * 64 + hi * 16;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -850,7 +860,7 @@ __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
       q8p[m] = i32x8{r0[1], r0[0], r0[3], r0[2], r1[1], r1[0], r1[3], r1[2]};
     }
   }
-  f32x16 o[2], ls;
+  f32x16 o[2], ls;                                                     // (NARROW: ls and ones are never read - the denominator is o[1][15])
   float m_i = SDM_NEG_BIG;
 #pragma unroll
   for (int r = 0; r < 16; ++r) { ls[r] = 0.0f; o[0][r] = 0.0f; o[1][r] = 0.0f; }
@@ -926,7 +936,7 @@ __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
     if (ABL & 32) { SDM_PIN_HERE_V4(f.h[0], f.h[1], f.h[2], f.h[3]); SDM_PIN_HERE_V4(f.f8[0], f.f8[1], f.h[0], f.h[1]); return; }
     const unsigned char* Ks = smem + slot * SLOT + kt * 4096;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) f.h[ks] = *(const f16x8*)(Ks + (kx ^ (ks * 32)));
+    for (int ks = 0; ks < NKS; ++ks) f.h[ks] = *(const f16x8*)(Ks + (kx ^ (ks * 32)));
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
       const i32x4 a0 = *(const i32x4*)(Ks + KLO + (k8x ^ (m * 64))), a1 = *(const i32x4*)(Ks + KLO + ((k8x ^ (m * 64)) ^ 16));
@@ -936,7 +946,7 @@ __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
   auto mma_k = [&](const KFrag& f, f32x16& sk) {
     if (ABL & 4) return;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) sk = SDM_MFMA_32x32x16_F16(f.h[ks], qf[ks], sk);
+    for (int ks = 0; ks < NKS; ++ks) sk = SDM_MFMA_32x32x16_F16(f.h[ks], qf[ks], sk);
 #pragma unroll
     for (int m = 0; m < 2; ++m) sk = SDM_MFMA_32x32x64_BF8_BF8(f.f8[m], q8p[m], sk, 127 - 11, 127);
   };
@@ -953,7 +963,7 @@ __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
     if (ABL & 2) return;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      ls = SDM_MFMA_32x32x16_F16(ones, pk[u], ls);
+      if (!NARROW) ls = SDM_MFMA_32x32x16_F16(ones, pk[u], ls);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) o[dt] = SDM_MFMA_32x32x16_F16(f.v[u][dt], pk[u], o[dt]);
     }
@@ -1001,8 +1011,10 @@ __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
     mid0();
     SDM_SCHED_FENCE();
     if (__any(alpha != 1.0f)) {
+      if (!NARROW) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) ls[r] *= alpha;
+        for (int r = 0; r < 16; ++r) ls[r] *= alpha;
+      }
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -1091,7 +1103,7 @@ __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
     if (KE < 2) load_k(b1, 1, k1);
     if (KE < 1) {
 #pragma unroll
-      for (int i = 0; i < 12; ++i) { SDM_SCHED_GROUP(0x008, 1, 0); SDM_SCHED_GROUP(0x100, 2, 0); SDM_SCHED_GROUP(0x002, 1, 0); }
+      for (int i = 0; i < (NARROW ? 8 : 12); ++i) { SDM_SCHED_GROUP(0x008, 1, 0); SDM_SCHED_GROUP(0x100, 2, 0); SDM_SCHED_GROUP(0x002, 1, 0); }      // (one group per P.V MFMA)
     } else if (KE < 2) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) { SDM_SCHED_GROUP(0x008, 1, 0); SDM_SCHED_GROUP(0x100, 1, 0); }
@@ -1127,11 +1139,12 @@ __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
   // epilogue (fp32 output): per-wave staging [32 q][64 d] at pitch 272 B -> coalesced 16-byte row stores
   constexpr int PS = 272;
   unsigned char* stf = smem + wave * (32 * PS);
-  const float inv = p.nsplit > 1 ? 1.0f : 1.0f / ls[0];                 // key split: unnormalised partial sums (attn_combine_kernel divides)
+  const float den = NARROW ? o[1][15] : ls[0];                          // NARROW: the ones row of V^T (59 | 63) this lane's half holds
+  const float inv = p.nsplit > 1 ? 1.0f : 1.0f / den;                   // key split: unnormalised partial sums (attn_combine_kernel divides)
   float* obase = (float*)p.o + (p.nsplit > 1 ? (size_t)sp * p.part_stride : (size_t)0) + (size_t)b * p.o_bs;
   if (p.nsplit > 1 && hi == 0 && q0 + l31 < p.Lq) {
     float* ml = p.part_ml + ((((size_t)sp * p.batch + b) * p.heads + head) * p.Lq + q0 + l31) * 2;
-    ml[0] = m_i; ml[1] = ls[0];
+    ml[0] = m_i; ml[1] = den;
   }
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
@@ -1150,6 +1163,69 @@ __global__ void __launch_bounds__(512, 2) attn_d64_pp_kernel(AttnParams p) {
     const int qg = q0 + row;
     if (qg < p.Lq)
       *(f32x4*)(obase + (size_t)qg * p.ldo + head * 64 + part * 4) = *(const f32x4*)(stf + row * PS + part * 16);
+  }
+}
+
+// epilogue of the d = 512 kernels: O^T accumulators of the wave's 32 queries x 256 d -> fp16 or fp32 rows through per-wave LDS staging (the tile buffers are
+// free: every wave is behind its last tile).  Block-wide barriers inside: every wave of the block calls it.
+SDM_DEV_INLINE void attn512_store(const AttnParams& p, unsigned char* smem, f32x16 (&o)[8], float l_i, int b, int q0, int dh, int wave, int lane) {
+  const int hi = lane >> 5, l31 = lane & 31;
+  l_i += __shfl_xor(l_i, 32);
+  const float inv = 1.0f / l_i;
+  if (p.o_f32) {                   // fp32 output (precise-mode graphs): [32 q][128 d] fp32 staging per wave, pitch 528 B
+    constexpr int PF = 528;
+    unsigned char* stf = smem + wave * (32 * PF);
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      __syncthreads();
+#pragma unroll
+      for (int d4 = 0; d4 < 4; ++d4) {
+        const int dt = half * 4 + d4;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          f32x4 h;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) h[e] = o[dt][4 * g + e] * inv;
+          *(f32x4*)(stf + l31 * PF + (d4 * 32 + 8 * g + 4 * hi) * 4) = h;
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int pass = 0; pass < 16; ++pass) {
+        const int row = pass * 2 + (lane >> 5), part = lane & 31;
+        const int qg = q0 + row;
+        if (qg < p.Lq)
+          *(f32x4*)((float*)p.o + (size_t)b * p.o_bs + (size_t)qg * p.ldo + dh * 256 + half * 128 + part * 4) =
+              *(const f32x4*)(stf + row * PF + part * 16);
+      }
+    }
+    return;
+  }
+  constexpr int PS = 272;
+  unsigned char* stg = smem + wave * (32 * PS);
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    __syncthreads();
+#pragma unroll
+    for (int d4 = 0; d4 < 4; ++d4) {
+      const int dt = half * 4 + d4;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f16x4 h;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) h[e] = (half_t)(o[dt][4 * g + e] * inv);
+        *(f16x4*)(stg + l31 * PS + (d4 * 32 + 8 * g + 4 * hi) * 2) = h;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int pass = 0; pass < 8; ++pass) {
+      const int row = pass * 4 + (lane >> 4), part = lane & 15;
+      const int qg = q0 + row;
+      if (qg < p.Lq)
+        *(f16x8*)(p.o + (size_t)b * p.o_bs + (size_t)qg * p.ldo + dh * 256 + half * 128 + part * 8) =
+            *(const f16x8*)(stg + row * PS + part * 16);
+    }
   }
 }
 
@@ -1338,63 +1414,214 @@ __global__ void __launch_bounds__(512) attn_d512_kernel(AttnParams p) {
     SDM_RAW_BARRIER();          // ... and so have everyone else's; every wave is done with tile t and the exchange buffer
   }
 
-  l_i += __shfl_xor(l_i, 32);
-  const float inv = 1.0f / l_i;
-  if (p.o_f32) {                   // fp32 output (precise-mode graphs): [32 q][128 d] fp32 staging per wave, pitch 528 B
-    constexpr int PF = 528;
-    unsigned char* stf = smem + wave * (32 * PF);
+  attn512_store(p, smem, o, l_i, b, q0, dh, wave, lane);
+}
+
+// ------------------------------------------------------------------------------------------------
+// d = 512, PING-PONG of the block's two wave halves (engine option attn512_pp; OFF by default until it has been timed on the GPU; the scheme of attn_d64_pp_kernel).  In attn_d512_kernel all 8 waves pass
+// the two barriers of a tile in the same phase: both waves of a SIMD multiply together, then both run the exchange and the softmax while the matrix pipe idles
+// (0.40 busy; softmax + exchange cost 0.8 + 0.5 ms of 2.45 in series, profiles/r06_attn_d512_ablation.txt).  Here waves 0-3 ("A", one per SIMD) and waves 4-7
+// ("B", their SIMD partners; the d-split pairs (w, w ^ 1) stay inside a half) run the SAME instruction sequence
+//     [exchange read + softmax of tile t]  barrier  [P.V of tile t, Q.K^T of tile t+1, write of the partial S^T of tile t+1]  barrier
+// one phase apart, so that a SIMD holds one wave in a matrix segment (32 back-to-back MFMAs, ONE basic block; its fragment reads three MFMAs ahead through four
+// rotating registers, across the P.V -> Q.K^T seam) beside one in a softmax segment.  Global phases (a phase = the time between two block-wide barriers):
+//     phase     -1      0            1                    2                    3             ...  2t             2t+1
+//     A (0-3):  QK(0)   softmax(0)   PV(0) QK(1)          softmax(1)           PV(1) QK(2)        softmax(t)     PV(t) QK(t+1)
+//     B (4-7):  -       QK(0)        softmax(0)           PV(0) QK(1)          softmax(1)         PV(t-1) QK(t)  softmax(t)
+//     DMAs:                          V(1) K(2)                                 V(2) K(3)                         V(t+1) K(t+2)
+// LDS stays at 160 KB (2 x K, 2 x V^T, exchange).  K(t) is last read by B in phase 2t, V^T(t-1) likewise (B's P.V of tile t-1): the DMAs that overwrite them -
+// K(t+2) and V^T(t+1), same buffer parities - go out at the head of phase 2t+1 from every wave (A: head of its matrix segment, B: head of its softmax segment).
+// Their first reader is A in phase 2t+3: every wave drains its DMAs (vmcnt(0): the batch is the only one in flight) in front of the barrier that ENDS phase 2t+2, a
+// whole tile period after issue - what attn_d512_kernel gives them; the barrier in between is passed with the batch in flight (raw s_barrier behind an LDS-only wait).
+// Because a tile lands only one barrier ahead of its first reader, its fragments cannot be requested under the exponentials of the preceding softmax segment (the
+// d = 64 kernel's six-slot ring allows that; double buffers do not): a matrix segment opens with one exposed LDS round trip, as the Q.K^T part of attn_d512_kernel does.
+// The exchange slots are per wave and only the d-split partner (same half) reads them: written at the end of a matrix segment, read in the next softmax segment.
+// Same MFMAs on the same operands in the same order per wave, the same fp32 row sums: results are BIT-IDENTICAL to attn_d512_kernel (tests/test_gpu_attn_d512_pp.py).
+// Behind the last tile Q.K^T runs once more on a buffer nobody refilled and writes logits nobody reads - a matrix segment has no branch.
+// pp_flags bit 0: s_setprio 1 for waves 4-7.  ABL as for attn_d512_kernel.
+// ------------------------------------------------------------------------------------------------
+template <int ABL = 0>
+__global__ void __launch_bounds__(512) attn_d512_pp_kernel(AttnParams p) {
+  SDM_DYN_SMEM(smem);
+  float* Xs = (float*)(smem + ATTN512P_X_OFF);
+  const int tid = threadIdx.x, lane = tid & 63, wave = SDM_UNIFORM_I(tid >> 6);
+  const int hi = lane >> 5, l31 = lane & 31;
+  const int qgp = wave >> 1, dh = wave & 1, grp = wave >> 2;
+  int b, head_unused, qblk;
+  if (!attn_block_coords(p, blockIdx.x, b, head_unused, qblk)) return;
+  const int q0 = qblk * 128 + qgp * 32;
+
+  f16x8 qf[16];
+  {
+    int qrow = q0 + l31;
+    if (qrow > p.Lq - 1) qrow = p.Lq - 1;
+    const half_t* qp = p.q + (size_t)b * p.q_bs + (size_t)qrow * p.ldq + dh * 256 + hi * 8;
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      __syncthreads();
+    for (int ks = 0; ks < 16; ++ks) qf[ks] = *(const f16x8*)(qp + ks * 16);
+  }
+  f32x16 o[8];
 #pragma unroll
-      for (int d4 = 0; d4 < 4; ++d4) {
-        const int dt = half * 4 + d4;
+  for (int dt = 0; dt < 8; ++dt)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          f32x4 h;
+    for (int r = 0; r < 16; ++r) o[dt][r] = 0.0f;
+  float m_i = SDM_NEG_BIG, l_i = 0.0f;
+
+  const half_t* kbase = p.k + (size_t)b * p.k_bs;
+  const half_t* vbase = p.vt + (size_t)b * p.vt_bs;
+  const int ntiles = (p.Lk + 31) / 32;
+
+  // DMA side: as attn_d512_kernel (4 K rows and 4 V^T row groups per wave and tile), K and V^T of different tiles per batch
+  const sdm_rsrc rsK = sdm_make_rsrc(kbase, (unsigned int)((size_t)p.Lk * p.ldk * 2));
+  const sdm_rsrc rsV = sdm_make_rsrc(vbase, (unsigned int)((size_t)512 * p.ldvt * 2));
+  const unsigned int v_voff = (unsigned int)((lane >> 2) * p.ldvt * 2 + (((lane & 3) ^ ((lane >> 4) & 3)) * 16));
+  int lane16 = lane * 16;
+  auto issue_k = [&](int t) {
+    if ((ABL & 8) || t >= ntiles) return;
+    const int k0 = t * 32;
+    unsigned char* Kd = smem + (t & 1) * ATTN512P_K_BYTES;
+    SDM_OPAQUE_I(lane16);                                             // (the four per-row offsets are one v_xor each HERE, not four registers carried around the loop: the kernel sits at 256)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) h[e] = o[dt][4 * g + e] * inv;
-          *(f32x4*)(stf + l31 * PF + (d4 * 32 + 8 * g + 4 * hi) * 4) = h;
+    for (int i = 0; i < 4; ++i) {
+      const int rho = 4 * wave + i;
+      const int pi = (rho & 16) | (((rho >> 2) & 1) << 3) | (((rho >> 3) & 1) << 2) | (rho & 3);
+      int kr = k0 + pi;
+      if (kr > p.Lk - 1) kr = p.Lk - 1;                              // keys >= Lk are masked after QK^T
+      sdm_glds16_buf(rsK, (unsigned int)(lane16 ^ ((rho & 15) * 16)), (unsigned int)kr * (unsigned int)(p.ldk * 2), Kd + rho * 1024);      // = (lane ^ (rho & 15)) * 16
+    }
+  };
+  auto issue_v = [&](int t) {
+    if ((ABL & 8) || t >= ntiles) return;
+    const int k0 = t * 32;
+    unsigned char* Vd = smem + 2 * ATTN512P_K_BYTES + (t & 1) * ATTN512P_V_BYTES;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int g = 4 * wave + i;
+      sdm_glds16_buf(rsV, v_voff, (unsigned int)((16 * g * p.ldvt + k0) * 2), Vd + g * 1024);
+    }
+  };
+  int kx = (l31 * 1024 + dh * 512) ^ ((hi ^ (l31 & 15)) * 16);      // read-side swizzles: attn_d512_kernel
+  int vx = (dh * 256 + l31) * 64 + ((hi ^ ((l31 >> 2) & 3)) * 16);
+  auto lds_barrier = [&]() { SDM_SCHED_FENCE(); SDM_WAIT_LGKMCNT0(); SDM_RAW_BARRIER(); SDM_SCHED_FENCE(); };
+  float* xme = Xs + wave * (16 * 64);
+  const float* xpt = Xs + (wave ^ 1) * (16 * 64);
+
+  f32x16 s;
+  f16x8 pf[2];
+  // matrix segment: P.V of tile tv (pv: not in the prologue), then Q.K^T of tile tv + 1 into s, then the partial S^T into the wave's exchange slot
+  auto matrix = [&](int tv, bool pv) {
+    const unsigned char* Vs = smem + 2 * ATTN512P_K_BYTES + (tv & 1) * ATTN512P_V_BYTES;
+    const unsigned char* Ks = smem + ((tv + 1) & 1) * ATTN512P_K_BYTES;
+    SDM_OPAQUE_I(kx);
+    SDM_OPAQUE_I(vx);
+    f16x8 a[4];
+    const int i0 = pv ? 0 : 16;
+    auto rd = [&](int i) -> f16x8 {      // i = 8 u + dt: V^T fragment; 16 + ks: K fragment
+      if (ABL & 32) return qf[(i + 1) & 15];
+      if (i < 16) return *(const f16x8*)(Vs + (vx ^ ((i >> 3) * 32)) + (i & 7) * 2048);
+      return *(const f16x8*)(Ks + (kx ^ ((i - 16) * 32)));
+    };
+#pragma unroll
+    for (int i = 0; i < 3; ++i) a[i] = rd(i0 + i);
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+      if (i < i0) continue;
+      if (i + 3 < 32) a[(i + 3) & 3] = rd(i + 3);
+      if (i < 16) { if (!(ABL & 2)) o[i & 7] = SDM_MFMA_32x32x16_F16(a[i & 3], pf[i >> 3], o[i & 7]); }
+      else if (i == 16) {                                            // accumulators start from the zero operand of the first MFMA
+        const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (!(ABL & 4)) s = SDM_MFMA_32x32x16_F16(a[0], qf[0], z); else s = z;
+      } else if (!(ABL & 4)) s = SDM_MFMA_32x32x16_F16(a[i & 3], qf[i - 16], s);
+    }
+    if (!(ABL & 38)) {
+      SDM_SCHED_GROUP(0x100, 3, 0);
+      if (pv) {
+#pragma unroll
+        for (int i = 0; i < 29; ++i) { SDM_SCHED_GROUP(0x100, 1, 0); SDM_SCHED_GROUP(0x008, 1, 0); }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 13; ++i) { SDM_SCHED_GROUP(0x100, 1, 0); SDM_SCHED_GROUP(0x008, 1, 0); }
+      }
+      SDM_SCHED_GROUP(0x008, 3, 0);
+    }
+    SDM_SCHED_FENCE();
+    if (!(ABL & 1)) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) xme[r * 64 + lane] = s[r];
+    }
+  };
+
+  // ---- prologue: K(0), V^T(0), K(1) in LDS; A computes the logits of tile 0 while B waits one phase ----
+  issue_k(0); issue_v(0); issue_k(1);
+  SDM_WAIT_VMCNT0();
+  lds_barrier();
+  if (grp) {
+    if (p.pp_flags & 1) SDM_SETPRIO(1);
+    lds_barrier();
+  }
+  matrix(-1, false);
+  lds_barrier();
+  for (int t = 0; t < ntiles; ++t) {
+    const int k0 = t * 32;
+    // ---- softmax segment of tile t (A: phase 2t, B: phase 2t + 1) ----
+    if (grp) { issue_v(t + 1); issue_k(t + 2); }
+    float mx = SDM_NEG_BIG;
+    if (!(ABL & 1)) {
+      if (k0 + 32 > p.Lk) {                                            // keys >= Lk: only the last tile can hold any (wave-uniform)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = k0 + 16 * (r >> 3) + 8 * hi + (r & 7);      // pi-permuted row -> actual key
+          float x = (s[r] + xpt[r * 64 + lane]) * p.scale_log2e;
+          if (key >= p.Lk) x = SDM_NEG_BIG;
+          s[r] = x;
+          mx = fmaxf(mx, x);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float x = (s[r] + xpt[r * 64 + lane]) * p.scale_log2e;
+          s[r] = x;
+          mx = fmaxf(mx, x);
         }
       }
-      __syncthreads();
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float mnew = fmaxf(m_i, mx);
+      const float alpha = sdm_exp2(m_i - mnew);
+      m_i = mnew;
+      float rs = 0.0f;
 #pragma unroll
-      for (int pass = 0; pass < 16; ++pass) {
-        const int row = pass * 2 + (lane >> 5), part = lane & 31;
-        const int qg = q0 + row;
-        if (qg < p.Lq)
-          *(f32x4*)((float*)p.o + (size_t)b * p.o_bs + (size_t)qg * p.ldo + dh * 256 + half * 128 + part * 4) =
-              *(const f32x4*)(stf + row * PF + part * 16);
+      for (int r = 0; r < 16; ++r) {
+        const float pv = sdm_exp2(s[r] - mnew);
+        s[r] = pv;
+        rs += pv;
       }
-    }
-    return;
-  }
-  constexpr int PS = 272;
-  unsigned char* stg = smem + wave * (32 * PS);
+      l_i = l_i * alpha + rs;
+      if (__any(alpha != 1.0f)) {
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    __syncthreads();
+        for (int dt = 0; dt < 8; ++dt)
 #pragma unroll
-    for (int d4 = 0; d4 < 4; ++d4) {
-      const int dt = half * 4 + d4;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f16x4 h;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) h[e] = (half_t)(o[dt][4 * g + e] * inv);
-        *(f16x4*)(stg + l31 * PS + (d4 * 32 + 8 * g + 4 * hi) * 2) = h;
+          for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
       }
-    }
-    __syncthreads();
+    } else l_i = 1.0f;
 #pragma unroll
-    for (int pass = 0; pass < 8; ++pass) {
-      const int row = pass * 4 + (lane >> 4), part = lane & 15;
-      const int qg = q0 + row;
-      if (qg < p.Lq)
-        *(f16x8*)(p.o + (size_t)b * p.o_bs + (size_t)qg * p.ldo + dh * 256 + half * 128 + part * 8) =
-            *(const f16x8*)(stg + row * PS + part * 16);
-    }
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pf[u][j] = (half_t)s[8 * u + j];
+    SDM_PIN_HERE_V2(pf[0], pf[1]);                                     // the probabilities are only consumed behind the barrier: left alone, the exp / pack stream sinks there
+    if (!grp) SDM_WAIT_VMCNT0();                                       // A: end of phase 2t - this wave's V^T(t), K(t+1) (issued at the head of phase 2t - 1) have landed
+    lds_barrier();
+    // ---- matrix segment (A: phase 2t + 1, B: phase 2t + 2) ----
+    if (!grp) { issue_v(t + 1); issue_k(t + 2); }
+    matrix(t, true);
+    if (grp) SDM_WAIT_VMCNT0();                                        // B: end of phase 2t + 2 - V^T(t+1), K(t+2) (issued at the head of phase 2t + 1) have landed
+    lds_barrier();
   }
+  if (!grp) lds_barrier();                                             // B's last matrix segment still reads its tile: the epilogue reuses the buffers
+  SDM_WAIT_VMCNT0();
+  // the epilogue's lane / wave values are derived again HERE: carried around the loop they cost the five registers that q's first fragment then lacks (scratch)
+  int tid_e = threadIdx.x;
+  SDM_OPAQUE_I(tid_e);
+  const int wave_e = SDM_UNIFORM_I(tid_e >> 6);
+  attn512_store(p, smem, o, l_i, b, qblk * 128 + (wave_e >> 1) * 32, wave_e & 1, wave_e, tid_e & 63);
 }
 
 // Active key tiles of every image (see AttnParams::tiles): one block per image.  bias is the log2-domain key bias [B][Lk].

@@ -213,6 +213,8 @@ __global__ void split_planes_kernel(const float* __restrict__ x, half_t* __restr
 // fp32 NHWC U-Net input `uin` [B][H][W][16].  Per image:
 //   k_hi  [Lk][64] fp16, k_pair [Lk][64] pair words at the same element offsets (sdm_pair_plane4): the K operand of the d = 64 PREC = 3 kernels (k_attn.h);
 //   vt    [64][ldvt] fp16 = k_hi transposed, rows 36..63 and the key columns Lk .. ldvt - 1 zero: their V^T operand.
+//   ones_rows != 0 (the narrow form of the d = 64 cores, k_attn.h NARROW): V^T rows 59 and 63 hold 1.0 for the key columns < Lk (0 behind them), so that the
+//   P.V MFMA of d = 32..63 delivers the softmax denominator in o[1][15] of either lane half.  k_hi / k_pair are the same in both forms.
 // blockIdx.y = 0: thread = 8 columns of one key row (16-byte stores to both planes); 1: thread = 8 keys of one V^T row (one 16-byte store).
 SDM_DEV_INLINE float cross_patch_value(const float* __restrict__ uin, int H, int W, long b, int key, int j) {
   if (j >= 36 || key >= H * W) return 0.0f;
@@ -222,7 +224,7 @@ SDM_DEV_INLINE float cross_patch_value(const float* __restrict__ uin, int H, int
   return uin[((size_t)b * H * W + (size_t)y * W + x) * 16 + 4 + ci];
 }
 __global__ void __launch_bounds__(256) cross_patch_planes_kernel(const float* __restrict__ uin, int B, int H, int W, half_t* __restrict__ k_hi,
-                                                                 half_t* __restrict__ k_pair, half_t* __restrict__ vt, int ldvt) {
+                                                                 half_t* __restrict__ k_pair, half_t* __restrict__ vt, int ldvt, int ones_rows) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int Lk = H * W;
   if (blockIdx.y == 0) {
@@ -253,7 +255,11 @@ __global__ void __launch_bounds__(256) cross_patch_planes_kernel(const float* __
     for (int g = 0; g < 2; ++g) {
       f16x4 oh;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) oh[e] = (half_t)fminf(fmaxf(cross_patch_value(uin, H, W, b, chunk * 8 + g * 4 + e, j), -57344.0f), 57344.0f);
+      for (int e = 0; e < 4; ++e) {
+        const int key = chunk * 8 + g * 4 + e;
+        const float x = (ones_rows && (j == 59 || j == 63) && key < Lk) ? 1.0f : cross_patch_value(uin, H, W, b, key, j);
+        oh[e] = (half_t)fminf(fmaxf(x, -57344.0f), 57344.0f);
+      }
       const u32x2 hw = __builtin_bit_cast(u32x2, oh);
       hv[2 * g] = hw[0]; hv[2 * g + 1] = hw[1];
     }

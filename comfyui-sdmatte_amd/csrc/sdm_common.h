@@ -176,6 +176,7 @@ static inline void sdm_glds4_buf(sdm_rsrc r, unsigned int voff, unsigned int sof
 #define SDM_UNIFORM_I(x) (x)
 #define SDM_OPAQUE_I(x) ((void)0)
 #define SDM_PIN_HERE_V4(a, b, c, d) ((void)0)
+#define SDM_PIN_HERE_V2(a, b) ((void)0)
 #define SDM_WAIT_VMCNT0() ((void)0)
 #define SDM_WAIT_VMCNT(n) ((void)0)
 #define SDM_WAIT_LGKMCNT0() ((void)0)
@@ -202,6 +203,7 @@ __device__ __forceinline__ void sdm_glds4_buf(sdm_rsrc r, unsigned int voff, uns
 // force four 128-bit register values to be fully computed at this point (stops the optimiser from sinking their producers
 // below a later branch, out of the block whose instruction interleave is being pinned)
 #define SDM_PIN_HERE_V4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
+#define SDM_PIN_HERE_V2(a, b) asm volatile("" : "+v"(a), "+v"(b))
 #define SDM_WAIT_VMCNT0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 // counted wait: at most n vector-memory operations of this wave (loads, LDS-DMAs, stores) may still be outstanding afterwards
 #define SDM_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")

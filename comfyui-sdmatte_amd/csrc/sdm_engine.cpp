@@ -133,6 +133,8 @@ static OptEntry g_opts[] = {
   {"attn_pp", 1, 1, "split-precision d=64 attention with fp32 output as a ping-pong of the block's wave halves (attn_d64_pp_kernel, 256 query rows per block): 0 off, 1 on, 2 on without the static priority of the younger half, 3 on with per-segment priority flips"},
   {"attn_pp_min_blocks", 128, 128, "attn_pp: launches with fewer 256-row blocks than this keep the 4-wave pipelines (0 in tests: the ping-pong kernel at any size)"},
   {"attn_ksplit", 0, 0, "key split of the d=64 split-precision attention: 0 by launch size (blocks that do not fill the chip's block slots a whole number of times), 1 off, 2 / 4 forced, 3 forced on the ping-pong kernel (ignored elsewhere: those launches run unsplit)"},
+  {"attn512_pp", 0, 0, "d=512 attention (VAE mid-block): the ping-pong kernel (the block's two wave halves one phase apart, attn_d512_pp_kernel; bit-identical): 1 with s_setprio 1 for waves 4-7, 2 without (A/B), 0 = attn_d512_kernel.  Off until its step time has been measured against attn_d512_kernel (profiles/NOTES.md)"},
+  {"cross_narrow", 1, 1, "cross_shared: the narrow form of the d = 64 cores on the shared operand (36 live columns: no Q.K^T step over columns 48..63, the softmax denominator from a row of ones in V^T instead of its own MFMAs; bit-identical).  0 = the full d = 64 program on an operand without the ones rows.  Read per forward"},
   {"cross_shared", 1, 1, "cross-attention on ONE key / value operand per forward, the patch matrix of the trimap latent (cross_patch_planes_kernel), with the K|V fold moved into q_shared / out_shared: 0 = every block's own kv_folded conv + transpose.  Read per forward"},
   {"precise_mask", -1, -1, "stages in split precision (-1 = the config's own mask; per-stage attribution experiments; read at sdm_create)"},
 #ifdef SDM_EMU
@@ -1519,11 +1521,14 @@ static int op_ln(sdm_ctx* e, const NormL& n, const T& x, float eps, T* out, int 
 // pointers exist only outside the dry pass, and the launch plan must be the same in both passes.
 // shared_kv (d = 64, no residual terms of P.V): ONE key / value operand for every head - `k` is [b][key][64] (ldk = 64, head stride 0) and `v` is the READY
 // V^T [b][64][rup(Lk, 64)] (zero filled behind Lk; ldv is not read): no V^T scratch, no transpose_v launch
-struct AttnPrec { int prec = 0; long q_lo = 0, k_lo = 0, v_lo = 0; int out_f32 = 0; int out_p3 = 0; bool has_bias = false, has_tiles = false; bool shared_kv = false; };      // out_p3 (with out_f32 = 1): `out` is a P3 tensor (k_gemm.h)
+// narrow36 (with shared_kv; set by cross_attention alone, for planes that cross_patch_planes_kernel wrote with ones_rows): columns 36..63 of q and k are zero and
+// V^T rows 59 / 63 hold 1.0 - the launch plan may take the narrow form of a core (k_attn.h NARROW).  NOT implied by shared_kv: a caller's operand
+// (sdm_op_attention_shared) may have live columns up to 63 and has no ones rows.
+struct AttnPrec { int prec = 0; long q_lo = 0, k_lo = 0, v_lo = 0; int out_f32 = 0; int out_p3 = 0; bool has_bias = false, has_tiles = false; bool shared_kv = false; bool narrow36 = false; };      // out_p3 (with out_f32 = 1): `out` is a P3 tensor (k_gemm.h)
 
 // Everything op_attention_raw decides about a launch, decided once: the sizing pass allocates from it, the launch pass launches from it.
-enum AttnKernel { kAttnPP, kAttnPPBias, kAttnPPTiles, kAttnPipe8, kAttnPipe4, kAttnP3W8, kAttnP3W4, kAttnP1W8, kAttnP1W4, kAttnP2W8, kAttnP2W4,
-                  kAttnF16W8, kAttnF16W4, kAttnD512 };
+enum AttnKernel { kAttnPP, kAttnPPBias, kAttnPPTiles, kAttnPPNarrow, kAttnPipe8, kAttnPipe4, kAttnPipe4Narrow, kAttnP3W8, kAttnP3W4, kAttnP1W8, kAttnP1W4, kAttnP2W8, kAttnP2W4,
+                  kAttnF16W8, kAttnF16W4, kAttnD512, kAttnD512PP };
 struct AttnPlan {
   AttnKernel kernel;              // row of kAttnKernels: launch counter (d = 64 launches are counted), block size, dynamic LDS
   const char* spec_counter;       // ping-pong kernel: the specialisation taken (tests); otherwise null
@@ -1534,6 +1539,7 @@ struct AttnPlan {
   bool walk_tiles, own_list;      // the kernel walks a list of active key tiles; the operator builds that list itself
   bool pv_split;                  // residual terms of P.V too: V^T_lo is needed as well
   int pp_flags;
+  bool narrow;                    // the narrow form of the kernel (AttnPrec::narrow36 and a kernel that has one): counted as attn_d64_narrow
 };
 struct AttnKernelInfo { const char* counter; int threads; size_t smem; void (*launch)(const AttnKernelInfo&, const AttnPlan&, const AttnParams&, void*); };
 template <auto K, int LDS_LIMIT = 160 * 1024>      // LDS_LIMIT: the dynamic-LDS limit the kernel is given (0: the default limit holds its LDS)
@@ -1545,8 +1551,10 @@ static const AttnKernelInfo kAttnKernels[] = {      // indexed by AttnKernel
   {"attn_d64_pp", 512, ATTN64PP_SMEM, attn_launch_t<attn_d64_pp_kernel<0, 0, 0>>},
   {"attn_d64_pp", 512, ATTN64PP_SMEM, attn_launch_t<attn_d64_pp_kernel<0, 1, 0>>},
   {"attn_d64_pp", 512, ATTN64PP_SMEM, attn_launch_t<attn_d64_pp_kernel<0, 1, 1>>},
+  {"attn_d64_pp", 512, ATTN64PP_SMEM, attn_launch_t<attn_d64_pp_kernel<0, 0, 0, 0, 1, 1, 1>>},
   {"attn_d64_pipe<8>", 512, ATTN64PIPE_SMEM, attn_launch_t<attn_d64_pipe_kernel<8>>},
   {"attn_d64_pipe<4>", 256, ATTN64PIPE4_SMEM, attn_launch_t<attn_d64_pipe_kernel<4>>},
+  {"attn_d64_pipe<4>", 256, ATTN64PIPE4_SMEM, attn_launch_t<attn_d64_pipe_kernel<4, 1>>},
   {"attn_d64<prec3,8>", 512, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 3, 8>>},
   {"attn_d64<prec3,4>", 256, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 3, 4>>},
   {"attn_d64<prec1,8>", 512, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 1, 8>>},
@@ -1556,15 +1564,18 @@ static const AttnKernelInfo kAttnKernels[] = {      // indexed by AttnKernel
   {"attn_d64<fp16,8>", 512, ATTN64P_SMEM, attn_launch_t<attn_d64_kernel<1, 0, 8>>},
   {"attn_d64<fp16,4>", 256, ATTN64_SMEM, attn_launch_t<attn_d64_kernel<1, 0, 4>, 0>},
   {"attn_d512", 512, ATTN512P_SMEM, attn_launch_t<attn_d512_kernel<0>, ATTN512P_SMEM>},
+  {"attn_d512_pp", 512, ATTN512P_SMEM, attn_launch_t<attn_d512_pp_kernel<0>, ATTN512P_SMEM>},
 };
 // Pure: shapes, flags, the options and the CU count in, the plan out.
-static AttnPlan attn_plan(int B, int heads, int Lq, int Lk, int D, int prec, int out_f32, bool has_bias, bool has_tiles, int cus) {
+static AttnPlan attn_plan(int B, int heads, int Lq, int Lk, int D, int prec, int out_f32, bool has_bias, bool has_tiles, int cus, bool narrow36 = false) {
   AttnPlan pl;
   memset(&pl, 0, sizeof(pl));
   pl.nsplit = 1;
   bool nw8 = true, pp = false;      // (d = 512: one 8-wave kernel, 128 query rows per block)
   if (D != 64) {
-    pl.kernel = kAttnD512; pl.qrows = 128;
+    const int pp5 = opt("attn512_pp");
+    pl.kernel = pp5 ? kAttnD512PP : kAttnD512; pl.qrows = 128;
+    pl.pp_flags = pp5 == 1 ? 1 : 0;
   } else {
     // key tiles whose bias underflows the softmax are skipped (exact, AttnParams::tiles); the engine passes one list per U-Net
     // level, the stand-alone operator entry builds it here.  The option attn_dense = 1 walks every tile (A/B hook).
@@ -1595,6 +1606,12 @@ static AttnPlan attn_plan(int B, int heads, int Lq, int Lk, int D, int prec, int
       pl.kernel = pl.pv_split ? (nw8 ? kAttnP1W8 : kAttnP1W4) : (nw8 ? kAttnP2W8 : kAttnP2W4);
     } else {
       pl.kernel = nw8 ? kAttnF16W8 : kAttnF16W4;
+    }
+    // narrow form (AttnPrec::narrow36): the ping-pong kernel without bias and the 4-wave pipeline have one, at whole 64-key tiles; every other launch (the
+    // 8-wave pipeline, the plain kernels, a ragged last tile) runs the full program on the same operand - the ones rows then only fill dead output columns
+    if (narrow36 && !has_bias && Lk % 64 == 0) {
+      if (pl.kernel == kAttnPP) { pl.kernel = kAttnPPNarrow; pl.narrow = true; }
+      else if (pl.kernel == kAttnPipe4) { pl.kernel = kAttnPipe4Narrow; pl.narrow = true; }
     }
     if (pp) {
       pl.spec_counter = pl.walk_tiles ? "attn_pp<0,1,1>" : (has_bias ? "attn_pp<0,1,0>" : "attn_pp<0,0,0>");
@@ -1630,7 +1647,8 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
   if (ap.prec == 2 && !q_prescaled) SDM_FAIL(e, SDM_ERR_INVALID, "attention: the fp8-residual form takes pre-scaled queries");
   if (!e->dry && (ap.has_bias != (bias_l2 != nullptr) || ap.has_tiles != (tiles != nullptr)))
     SDM_FAIL(e, SDM_ERR_STATE, "attention: bias / tile list do not match what the sizing pass was told");
-  const AttnPlan pl = attn_plan(B, heads, Lq, Lk, D, ap.prec, ap.out_f32, ap.has_bias, ap.has_tiles, device_cus());
+  if (ap.narrow36 && !ap.shared_kv) SDM_FAIL(e, SDM_ERR_INVALID, "attention: the narrow form exists for the shared key / value operand only");
+  const AttnPlan pl = attn_plan(B, heads, Lq, Lk, D, ap.prec, ap.out_f32, ap.has_bias, ap.has_tiles, device_cus(), ap.narrow36);
   const AttnKernelInfo& ki = kAttnKernels[pl.kernel];
   const int nsplit = pl.nsplit;
   const int ldvt = rup(Lk, 64);
@@ -1699,6 +1717,7 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
       prof_begin(e, "attn_d64", flops, bytes, adesc);
       count_kernel(ki.counter);
       if (pl.spec_counter) count_kernel(pl.spec_counter);
+      if (pl.narrow) count_kernel("attn_d64_narrow");
       ki.launch(ki, pl, p, e->stream);
       if (nsplit > 1) {
         count_kernel("attn_combine");
@@ -1715,6 +1734,7 @@ static int op_attention_raw(sdm_ctx* e, const half_t* q, int ldq, const half_t* 
       prof_end(e);
     } else {
       prof_begin(e, "attn_d512", flops, bytes);
+      if (pl.kernel == kAttnD512PP) count_kernel(ki.counter);
       ki.launch(ki, pl, p, e->stream);
       prof_end(e);
     }
@@ -1917,10 +1937,14 @@ static int unet_attn_plane_fmt(const sdm_ctx* e) { return (e->cfg.precise_mask &
 // transformer block, freed behind the last.  k: [2][B][Lk][64] halves - the fp16 plane of all images, then their pair plane; vt: [B][64][ldvt].
 // The rule (`on`): option cross_shared != 0, the fp8-pair plane format (unet_attn_plane_fmt == 3: the default precision) and an fp32 U-Net input.  Every
 // other precision mode - the fp16 fast mode and the fp16 hi | lo planes of attn_f8 = 0 - keeps each block's own kv_folded conv + transpose.
-struct CrossPlanes { bool on = false; T k, vt; };
+// narrow (option cross_narrow != 0): V^T rows 59 and 63 hold 1.0 and the cores may run their narrow form (AttnPrec::narrow36).  Columns 59 and 63 of every
+// head of the CORE OUTPUT then hold 1.0 (the denominator divided by itself) instead of 0, like 36..58 / 60..62 dead columns: they meet all-zero rows of out_shared, in
+// its fp16 part and in its fp8 residual part alike (fold_cross_shared packs 36 live rows per head), so nothing behind out_shared sees them.
+struct CrossPlanes { bool on = false, narrow = false; T k, vt; };
 static int cross_planes_build(sdm_ctx* e, const T& uin, CrossPlanes* cp) {
   cp->on = opt("cross_shared") != 0 && unet_attn_plane_fmt(e) == 3 && uin.f32 == 1 && uin.C == 16;
   if (!cp->on) return 0;
+  cp->narrow = opt("cross_narrow") != 0;
   const int B = uin.N, Lk = uin.H * uin.W, ldvt = rup(Lk, 64);
   cp->k = talloc(e, 2 * B, 1, Lk, 64, 0);
   cp->vt = talloc(e, B, 1, 64, ldvt, 0);
@@ -1929,7 +1953,7 @@ static int cross_planes_build(sdm_ctx* e, const T& uin, CrossPlanes* cp) {
   count_kernel("cross_patch_planes");
   const long nthr = std::max((long)B * Lk * 8, (long)B * 64 * (ldvt / 8));
   SDM_LAUNCH(cross_patch_planes_kernel, dim3((unsigned)((nthr + 255) / 256), 2, 1), dim3(256), 0, e->stream, (const float*)uin.p, B, uin.H, uin.W,
-             (half_t*)cp->k.p, (half_t*)cp->k.p + (size_t)B * Lk * 64, (half_t*)cp->vt.p, ldvt);
+             (half_t*)cp->k.p, (half_t*)cp->k.p + (size_t)B * Lk * 64, (half_t*)cp->vt.p, ldvt, cp->narrow ? 1 : 0);
   prof_end(e);
   return 0;
 }
@@ -1962,7 +1986,7 @@ static int cross_attention(sdm_ctx* e, const TfB& t, T& n, const T& uin, const C
     ap.q_lo = (long)q2.rows() * q2.C;
     if (cp.on) {
       const half_t* kk = (const half_t*)cp.k.p;
-      ap.shared_kv = true; ap.k_lo = (long)N * L0 * 64;
+      ap.shared_kv = true; ap.narrow36 = cp.narrow; ap.k_lo = (long)N * L0 * 64;
       TRY(op_attention_raw(e, (const half_t*)q2.p, C, kk, 64, (const half_t*)cp.vt.p, 64, nullptr, N, t.heads, L, L0, 64, ao.p, C, true, nullptr, ap));
     } else {
       const half_t* kk = (const half_t*)kv.p;

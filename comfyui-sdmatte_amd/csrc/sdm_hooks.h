@@ -372,7 +372,7 @@ float sdm_bench_attn(sdm_ctx* e, int B, int heads, int Lq, int Lk, int qt, int a
 #ifdef SDM_EMU
   return -1.f;
 #else
-  if (qt & 64) {      // bit 64: the d = 512 single-head kernel (VAE mid-block), ablate = its compile-time ABL mask
+  if (qt & 64) {      // bit 64: the d = 512 single-head kernel (VAE mid-block), ablate = its compile-time ABL mask; bit 256: its ping-pong form (bit 32: without s_setprio)
     const int ldvt5 = rup(Lk, 64);
     DevBuf q5, k5, v5, o5;
     if (q5.alloc((size_t)B * Lq * 512 * 2) || k5.alloc((size_t)B * Lk * 512 * 2) || v5.alloc((size_t)B * 512 * ldvt5 * 2) || o5.alloc((size_t)B * Lq * 512 * 4)) return -2.f;
@@ -386,6 +386,14 @@ float sdm_bench_attn(sdm_ctx* e, int B, int heads, int Lq, int Lk, int qt, int a
     p5.Lq = Lq; p5.Lk = Lk; p5.scale_log2e = 0.0441941738f * SDM_LOG2E;
     p5.batch = B; p5.heads = 1; p5.nq_blocks = sdm_cdiv(Lq, 128); p5.q_chunks = 8;
     const unsigned nb5 = (unsigned)(B * p5.q_chunks * sdm_cdiv(p5.nq_blocks, p5.q_chunks));
+    if (qt & 256) {
+      p5.pp_flags = (qt & 32) ? 0 : 1;
+      return time_launches(e, iters, [&]() {
+#define SDM_D512PP_ABL(A) case A: { auto kp = attn_d512_pp_kernel<A>; SDM_SET_SMEM(kp, ATTN512P_SMEM); SDM_LAUNCH(kp, dim3(nb5), dim3(512), ATTN512P_SMEM, e->stream, p5); } break;
+        switch (ablate) { SDM_D512PP_ABL(0) SDM_D512PP_ABL(1) SDM_D512PP_ABL(6) SDM_D512PP_ABL(7) SDM_D512PP_ABL(8) SDM_D512PP_ABL(32) SDM_D512PP_ABL(40) SDM_D512PP_ABL(41) default: break; }
+#undef SDM_D512PP_ABL
+      });
+    }
     return time_launches(e, iters, [&]() {
 #define SDM_D512_ABL(A) case A: { auto kp = attn_d512_kernel<A>; SDM_SET_SMEM(kp, ATTN512P_SMEM); SDM_LAUNCH(kp, dim3(nb5), dim3(512), ATTN512P_SMEM, e->stream, p5); } break;
       switch (ablate) { SDM_D512_ABL(0) SDM_D512_ABL(1) SDM_D512_ABL(6) SDM_D512_ABL(7) SDM_D512_ABL(8) SDM_D512_ABL(32) SDM_D512_ABL(40) SDM_D512_ABL(41) default: break; }
@@ -492,6 +500,18 @@ int sdm_op_attention(sdm_ctx* e, const void* q, int ldq, const void* k, int ldk,
   });
 }
 
+/* sdm_op_attention with an fp32 result (out_f32 != 0: `out` is fp32 [B][Lq][heads*D], ldo in elements) - the d = 512 core as the precise-mode VAE runs it.  Test hook. */
+int sdm_op_attention_ex(sdm_ctx* e, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int B, int heads, int Lq, int Lk, int D, int out_f32,
+                        void* out, int ldo) {
+  if (e) dev_use(e->device);
+  if (!e || !q || !k || !v || !out) return SDM_ERR_INVALID;
+  if (out_f32 && D != 512) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_attention_ex: fp32 output of fp16 operands exists for head dim 512 only");
+  return run_two_pass(e, [&]() {
+    AttnPrec ap; ap.out_f32 = out_f32 ? 1 : 0;
+    return op_attention_raw(e, (const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)v, ldv, nullptr, B, heads, Lq, Lk, D, out, ldo, false, nullptr, ap);
+  });
+}
+
 /* Split-precision d = 64 attention cores as the default precision runs them.  q [B,Lq,heads*64], k / v [B,Lk,heads*64]: contiguous fp32
  * DEVICE tensors.  They are first turned into the operand planes the producing GEMMs write in the engine (split_planes_kernel: fp16 hi plane
  * + fp16 lo plane, or + e5m2 pair plane when the Q.K^T residual terms run on fp8 MFMAs - the default; the option attn_f8 = 0 selects the former),
@@ -541,12 +561,16 @@ int sdm_op_attention_split_ex(sdm_ctx* e, const float* q, const float* k, const 
 /* The shared key / value operand of the cross-attentions (cross_patch_planes_kernel) of a U-Net input tensor uin fp32 [B][H][W][16] (DEVICE; the trimap latent
  * at channels 4..7): k_hi [B][H*W][64] fp16, k_pair the same number of bytes (the e5m2 pair plane), vt [B][64][rup(H*W, 64)] fp16.  Test hook. */
 int sdm_op_cross_patch_planes(sdm_ctx* e, const float* uin, int B, int H, int W, void* k_hi, void* k_pair, void* vt) {
+  return sdm_op_cross_patch_planes_ex(e, uin, B, H, W, k_hi, k_pair, vt, 0);
+}
+/* ... ones_rows != 0: with 1.0 in V^T rows 59 and 63 for the key columns < H*W, as the engine builds the operand under the option cross_narrow.  Test hook. */
+int sdm_op_cross_patch_planes_ex(sdm_ctx* e, const float* uin, int B, int H, int W, void* k_hi, void* k_pair, void* vt, int ones_rows) {
   if (e) dev_use(e->device);
   if (!e || !uin || !k_hi || !k_pair || !vt || B < 1 || H < 1 || W < 1) return SDM_ERR_INVALID;
   const int Lk = H * W, ldvt = rup(Lk, 64);
   const long nthr = std::max((long)B * Lk * 8, (long)B * 64 * (ldvt / 8));
   count_kernel("cross_patch_planes");
-  SDM_LAUNCH(cross_patch_planes_kernel, dim3((unsigned)((nthr + 255) / 256), 2, 1), dim3(256), 0, e->stream, uin, B, H, W, (half_t*)k_hi, (half_t*)k_pair, (half_t*)vt, ldvt);
+  SDM_LAUNCH(cross_patch_planes_kernel, dim3((unsigned)((nthr + 255) / 256), 2, 1), dim3(256), 0, e->stream, uin, B, H, W, (half_t*)k_hi, (half_t*)k_pair, (half_t*)vt, ldvt, ones_rows ? 1 : 0);
   SDM_CHECK_DEV(e, dev_sync(e->stream));
   return 0;
 }
@@ -605,6 +629,30 @@ int sdm_debug_cross_attention(sdm_ctx* e, const char* block, const float* x, int
     TRY(cross_attention(e, *tb, n, tu, cp, pf, p3, p3a, nullptr, &o));
     if (!e->dry) SDM_CHECK_DEV(e, dev_memcpy_d2d(out, o.p, (size_t)B * H * W * C * 4, e->stream));
     tfree(e, o);
+    cross_planes_free(e, &cp);
+    return 0;
+  });
+}
+
+/* The attention core of a cross-attention on the engine's OWN shared operand, for any number of heads (the tiny architecture has blocks of 1 and 2): q fp32
+ * [B][Lq][heads*64] (DEVICE; pre-scaled logits, columns 36..63 of every head zero as q_shared leaves them) attends to the planes that cross_planes_build makes
+ * of uin fp32 [B][h][w][16] under the current options (cross_narrow: ones rows and the narrow form) -> the core's fp32 output [B][Lq][heads*64], whose columns
+ * 0..35 per head are what out_shared reads.  Test hook. */
+int sdm_op_cross_core(sdm_ctx* e, const float* q, const float* uin, int B, int heads, int Lq, int h, int w, float* out) {
+  if (e) dev_use(e->device);
+  if (!e || !q || !uin || !out || B < 1 || heads < 1 || Lq < 1 || h < 1 || w < 1) return SDM_ERR_INVALID;
+  const int C = heads * 64, Lk = h * w;
+  return run_two_pass(e, [&]() -> int {
+    const T tu = view(uin, B, h, w, 16, 1);
+    CrossPlanes cp;
+    TRY(cross_planes_build(e, tu, &cp));
+    if (!cp.on) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_cross_core: the shared operand is off (cross_shared = 0 or another plane format)");
+    T qp = talloc(e, B, 1, Lq, C, 3);
+    const long nq = (long)B * Lq * C;
+    if (!e->dry) SDM_LAUNCH(split_planes_kernel, dim3((unsigned)((nq / 4 + 255) / 256)), dim3(256), 0, e->stream, q, (half_t*)qp.p, (half_t*)qp.p + nq, nq, 1.0f, 3);
+    AttnPrec ap; ap.prec = 2; ap.q_lo = nq; ap.k_lo = (long)B * Lk * 64; ap.out_f32 = 1; ap.shared_kv = true; ap.narrow36 = cp.narrow;
+    TRY(op_attention_raw(e, (const half_t*)qp.p, C, (const half_t*)cp.k.p, 64, (const half_t*)cp.vt.p, 64, nullptr, B, heads, Lq, Lk, 64, (void*)out, C, true, nullptr, ap));
+    tfree(e, qp);
     cross_planes_free(e, &cp);
     return 0;
   });

@@ -84,8 +84,8 @@ EXPORTS = [
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
-    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
-    "sdm_op_mask_bias", "sdm_op_cross_patch_planes", "sdm_op_attention_shared", "sdm_debug_cross_attention",
+    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
+    "sdm_op_mask_bias", "sdm_op_cross_patch_planes", "sdm_op_cross_patch_planes_ex", "sdm_op_attention_shared", "sdm_debug_cross_attention", "sdm_op_cross_core",
     "sdm_set_option", "sdm_get_option", "sdm_reset_options", "sdm_option_name", "sdm_option_help", "sdm_kernel_counts", "sdm_kernel_counts_reset",
 ]
 
@@ -152,12 +152,15 @@ class Bindings:
             "sdm_op_groupnorm": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, f32, i32, vp]),
             "sdm_op_layernorm": (i32, [vp, vp, i32, C.c_long, i32, vp, vp, f32, vp]),
             "sdm_op_attention": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32]),
+            "sdm_op_attention_ex": (i32, [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32]),
             "sdm_op_attention_split": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
             "sdm_op_attention_split_ex": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
             "sdm_debug_attn_plan": (i32, [i32] * 10 + [C.c_char_p, i32, C.POINTER(i32)]),
             "sdm_op_resize_aa": (i32, [vp, vp, i32, i32, i32, vp, i32, i32]),
             "sdm_op_mask_bias": (i32, [vp, vp, i32, i32, i32, vp]),
             "sdm_op_cross_patch_planes": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+            "sdm_op_cross_patch_planes_ex": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, i32]),
+            "sdm_op_cross_core": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
             "sdm_op_attention_shared": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
             "sdm_debug_cross_attention": (i32, [vp, C.c_char_p, vp, i32, i32, i32, vp, i32, i32, vp]),
             "sdm_set_option": (i32, [C.c_char_p, i32]),
@@ -956,6 +959,15 @@ class Engine:
                                               heads, Lq, Lk, D, _ptr(out), HD), "sdm_op_attention")
         return out
 
+    def op_attention_f32(self, q, k, v, heads):
+        """op_attention without a bias and with an fp32 result (head dim 512: the core as the precise-mode VAE runs it)."""
+        B, Lq, HD = q.shape
+        Lk = k.shape[1]
+        out = torch.empty(B, Lq, HD, dtype=torch.float32, device=q.device)
+        self._check(self.lib.sdm_op_attention_ex(self.h, _ptr(q), q.stride(1), _ptr(k), k.stride(1), _ptr(v), v.stride(1), B, heads, Lq, Lk, HD // heads, 1,
+                                                 _ptr(out), HD), "sdm_op_attention_ex")
+        return out
+
     def op_attention_split(self, q, k, v, heads, bias=None, out_p3=0, tiles=None, planes=False):
         """Split-precision attention cores (head dim 64): q [B,Lq,h*64], k / v [B,Lk,h*64] fp32; the C side splits them into the operand
         planes the producing GEMM epilogues write in the engine (fp16 high parts + fp8 residual pairs for Q.K^T); fp32 output.
@@ -976,9 +988,10 @@ class Engine:
                                                        _ptr(out), _ptr(raw)), "sdm_op_attention_split_ex")
         return (out, raw) if raw is not None else out
 
-    def op_cross_patch_planes(self, uin):
+    def op_cross_patch_planes(self, uin, ones_rows=False):
         """Test hook: the shared cross-attention operand of a U-Net input tensor uin fp32 [B,H,W,16] (trimap latent at channels 4..7) ->
-        (k_hi fp16 [B,H*W,64], k_pair uint8 [B,H*W,64,2], vt fp16 [B,64,ceil(H*W/64)*64])."""
+        (k_hi fp16 [B,H*W,64], k_pair uint8 [B,H*W,64,2], vt fp16 [B,64,ceil(H*W/64)*64]).  ones_rows: with 1.0 in vt rows 59 and 63 for the
+        keys < H*W, as the engine builds it under the option cross_narrow."""
         B, H, W_, _ = uin.shape
         L = H * W_
         ldvt = (L + 63) // 64 * 64
@@ -986,7 +999,8 @@ class Engine:
         k_hi = torch.full((B, L, 64), 7.0, dtype=torch.float16, device=x.device)
         k_pair = torch.full((B, L, 64, 2), 7, dtype=torch.uint8, device=x.device)
         vt = torch.full((B, 64, ldvt), 7.0, dtype=torch.float16, device=x.device)
-        self._check(self.lib.sdm_op_cross_patch_planes(self.h, _ptr(x), B, H, W_, _ptr(k_hi), _ptr(k_pair), _ptr(vt)), "sdm_op_cross_patch_planes")
+        self._check(self.lib.sdm_op_cross_patch_planes_ex(self.h, _ptr(x), B, H, W_, _ptr(k_hi), _ptr(k_pair), _ptr(vt), int(ones_rows)),
+                    "sdm_op_cross_patch_planes_ex")
         return k_hi, k_pair, vt
 
     def op_attention_shared(self, q, ks, vs, heads, q_prescaled=False):
@@ -1005,6 +1019,15 @@ class Engine:
         x, u = x_nhwc.float().contiguous(), uin.float().contiguous()
         out = torch.empty(B, H, W_, Cc, dtype=torch.float32, device=x.device)
         self._check(self.lib.sdm_debug_cross_attention(self.h, block.encode(), _ptr(x), B, H, W_, _ptr(u), u.shape[1], u.shape[2], _ptr(out)), "sdm_debug_cross_attention")
+        return out
+
+    def op_cross_core(self, q, uin, heads):
+        """Test hook: the attention core of a cross-attention on the engine's own shared operand, any number of heads: q fp32 [B,Lq,heads*64] (pre-scaled,
+        columns 36..63 of every head zero) and uin fp32 [B,h,w,16] -> fp32 [B,Lq,heads*64] under the current options (cross_narrow)."""
+        B, Lq, HD = q.shape
+        qf, u = q.float().contiguous(), uin.float().contiguous()
+        out = torch.empty(B, Lq, HD, dtype=torch.float32, device=qf.device)
+        self._check(self.lib.sdm_op_cross_core(self.h, _ptr(qf), _ptr(u), B, heads, Lq, u.shape[1], u.shape[2], _ptr(out)), "sdm_op_cross_core")
         return out
 
     def op_resize_aa(self, planes, Hout, Wout):

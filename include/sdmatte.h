@@ -478,6 +478,8 @@ int sdm_debug_set_input_cmask(sdm_ctx* ctx, const unsigned char* mask);
 int sdm_debug_run_layer(sdm_ctx* ctx, const char* layer_name, const float* x_nhwc, int N, int H, int W, float* out_nhwc, int Cout);
 int sdm_debug_temb_row(sdm_ctx* ctx, int temb_index, int is_trans, const float* coords4, float* out_host, int cout);
 /* Bench/ablation helper: ms per launch of one conv (random-ish data), HIP-event timed on the engine stream. */
+/* (qt: 2 split-precision, 4 eight-wave blocks, 8 P.V on plain fp16, 16 the d = 64 ping-pong kernel, 32 without s_setprio, 64 the d = 512 kernel, 256 with 64: its
+ * ping-pong form; ablate: the kernel's compile-time ABL mask) */
 float sdm_bench_attn(sdm_ctx* ctx, int B, int heads, int Lq, int Lk, int qt, int ablate, int iters);
 float sdm_bench_conv(sdm_ctx* ctx, int N, int H, int W, int Cin, int Cout, int ntaps, int stride, int in_f32, int tile_cfg, int ablate, int iters);
 /* GroupNorm(groups)+optional SiLU over NHWC (concat of two sources) -> fp16 NHWC. */
@@ -494,6 +496,9 @@ int sdm_op_layernorm(sdm_ctx* ctx, const void* x, int in_f32, long rows, int C, 
  * every tile; the engine option attn_dense = 1 disables the skip. */
 int sdm_op_attention(sdm_ctx* ctx, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* bias,
                      int B, int heads, int Lq, int Lk, int D, void* out, int ldo);
+/* Test hook: sdm_op_attention without a bias and with an fp32 result (out_f32 != 0; head dim 512 only): the d = 512 core as the precise-mode VAE runs it. */
+int sdm_op_attention_ex(sdm_ctx* ctx, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int B, int heads, int Lq, int Lk, int D, int out_f32,
+                        void* out, int ldo);
 /* Split-precision attention cores (head dim 64) as the default precision runs them: contiguous fp32 q [B,Lq,heads*64], k / v [B,Lk,heads*64]
  * are split into the operand planes the engine's GEMM epilogues produce (fp16 high parts + e5m2 residual pairs for Q.K^T, fp16 V), the
  * logit scale goes into Q; fp32 output [B,Lq,heads*64].  Test hook for the kernel the engine runs. */
@@ -512,8 +517,13 @@ int sdm_op_attention_split_ex(sdm_ctx* ctx, const float* q, const float* k, cons
  * is in q already.  sdm_debug_cross_attention: the cross-attention of one transformer block of the loaded model ("unet.mid_block.attentions.0", ...) under the
  * current options, from the normalised hidden state x fp32 [B][H][W][C] and the U-Net input uin fp32 [B][h][w][16] to to_out(attention) (no residual). */
 int sdm_op_cross_patch_planes(sdm_ctx* ctx, const float* uin, int B, int H, int W, void* k_hi, void* k_pair, void* vt);
+/* ... ones_rows != 0: the operand as the engine builds it under the option cross_narrow - 1.0 in vt rows 59 and 63 for the key columns < H*W. */
+int sdm_op_cross_patch_planes_ex(sdm_ctx* ctx, const float* uin, int B, int H, int W, void* k_hi, void* k_pair, void* vt, int ones_rows);
 int sdm_op_attention_shared(sdm_ctx* ctx, const float* q, const float* ks, const float* vs, int B, int heads, int Lq, int Lk, int q_prescaled, float* out);
 int sdm_debug_cross_attention(sdm_ctx* ctx, const char* block, const float* x, int B, int H, int W, const float* uin, int h, int w, float* out);
+/* Test hook: the attention core of a cross-attention on the engine's own shared operand for any number of heads - q fp32 [B][Lq][heads*64] (pre-scaled, columns
+ * 36..63 of every head zero) attends to the planes built from uin fp32 [B][h][w][16] under the current options (cross_narrow) -> fp32 [B][Lq][heads*64]. */
+int sdm_op_cross_core(sdm_ctx* ctx, const float* q, const float* uin, int B, int heads, int Lq, int h, int w, float* out);
 /* Test hook: the launch the attention operator would make for these shapes and flags under the current options, on a device of `cus` compute units:
  * the launch-counter name of the kernel (see sdm_kernel_counts) into kernel[cap] and the key split into *nsplit (1 = unsplit).  prec as in the engine:
  * 0 fp16 operands, 1 fp16 hi | lo planes, 2 fp16 + e5m2 pair planes (the default precision); has_bias / has_tiles: a key bias / a caller's tile list
