@@ -24,6 +24,7 @@
 #include "k_roi.h"
 #include "k_canvas.h"
 #include "k_boxes.h"
+#include "k_distance.h"
 #include "../../include/sdmatte.h"
 
 #include <algorithm>
@@ -2431,6 +2432,71 @@ static void op_roi_box(sdm_ctx* e, const float* plane, int B, int H, int W, floa
 }
 
 // ------------------------------------------------------------------------------------------------
+// the distance field (k_distance.h): plane fp32 [B,H,W] -> class words -> carries -> column distances uint16 [B,H,W] -> the row pass, which writes
+// the field (mode 0), the offset mask (mode 1) or the outlined cut-out (mode 2)
+// ------------------------------------------------------------------------------------------------
+static int df_check(sdm_ctx* e, const char* what, int B, int H, int W, float threshold) {
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "%s: bad plane size %dx%dx%d", what, B, H, W);
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "%s: %dx%dx%d is too large (sides up to %d, %d pixels in all)", what, B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  if (!std::isfinite(threshold) || !(threshold >= 0.0f) || !(threshold < 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "%s: threshold = %g must be a finite number in [0, 1)", what, (double)threshold);
+  return 0;
+}
+
+struct DfScratch { T bits, carry, cols; };
+static DfScratch df_talloc(sdm_ctx* e, int B, int H, int W) {
+  const int nt = sdm_cdiv(H, SDM_DF_TILE);
+  DfScratch s;
+  s.bits = talloc(e, B, nt, W, 1, 1);
+  s.carry = talloc(e, B, nt, W, 4, 1);
+  s.cols = talloc(e, B, H, W, 1, 0);      // (2 bytes per pixel)
+  return s;
+}
+static void df_tfree(sdm_ctx* e, DfScratch& s) { tfree(e, s.cols); tfree(e, s.carry); tfree(e, s.bits); }
+
+// four launches, whatever the arguments: df_bits, df_carry, df_cols and the row pass under the name of its mode (df_rows, df_offset, df_outline)
+static void op_distance(sdm_ctx* e, const float* plane, int B, int H, int W, float threshold, DfScratch& s, int mode, const DfEmit& emit) {
+  static_assert(SDM_DF_FIELD_NONE == SDM_DF_NONE && SDM_FG_MAX_SIDE <= 32768, "distance field limits");
+  const int nt = sdm_cdiv(H, SDM_DF_TILE);
+  const double px = (double)B * H * W, words = (double)B * nt * W;
+  const dim3 tiles((unsigned)(B * nt * sdm_cdiv(W, 256)));
+  prof_begin(e, "df_bits", 0, px * 4 + words * 4);
+  count_kernel("df_bits");
+  SDM_LAUNCH(df_bits_kernel, tiles, dim3(256), 0, e->stream, plane, (unsigned int*)s.bits.p, B, H, W, threshold);
+  prof_end(e);
+  prof_begin(e, "df_carry", 0, words * 24);      // the words twice, four carries
+  count_kernel("df_carry");
+  SDM_LAUNCH(df_carry_kernel, dim3((unsigned)sdm_cdiv(B * W, 256)), dim3(256), 0, e->stream, (const unsigned int*)s.bits.p, (int*)s.carry.p, B, H, W);
+  prof_end(e);
+  prof_begin(e, "df_cols", 0, words * 20 + px * 2);
+  count_kernel("df_cols");
+  SDM_LAUNCH(df_cols_kernel, tiles, dim3(256), 0, e->stream, (const unsigned int*)s.bits.p, (const int*)s.carry.p, (unsigned short*)s.cols.p, B, H, W);
+  prof_end(e);
+  const size_t smem = df_rows_smem(W);
+  const dim3 rows((unsigned)(B * H));
+  const unsigned short* cols = (const unsigned short*)s.cols.p;
+  // per pixel: the column distance (2 bytes) and what the mode reads and writes
+  if (mode == 0) {
+    if (smem > 48 * 1024) SDM_SET_SMEM((df_rows_kernel<0>), df_rows_smem(SDM_FG_MAX_SIDE));
+    prof_begin(e, "df_rows", 0, px * 6);
+    count_kernel("df_rows");
+    SDM_LAUNCH((df_rows_kernel<0>), rows, dim3(256), smem, e->stream, cols, B, H, W, emit);
+  } else if (mode == 1) {
+    if (smem > 48 * 1024) SDM_SET_SMEM((df_rows_kernel<1>), df_rows_smem(SDM_FG_MAX_SIDE));
+    prof_begin(e, "df_offset", 0, px * 6);
+    count_kernel("df_offset");
+    SDM_LAUNCH((df_rows_kernel<1>), rows, dim3(256), smem, e->stream, cols, B, H, W, emit);
+  } else {
+    if (smem > 48 * 1024) SDM_SET_SMEM((df_rows_kernel<2>), df_rows_smem(SDM_FG_MAX_SIDE));
+    prof_begin(e, "df_outline", 0, px * 34);
+    count_kernel("df_outline");
+    SDM_LAUNCH((df_rows_kernel<2>), rows, dim3(256), smem, e->stream, cols, B, H, W, emit);
+  }
+  prof_end(e);
+}
+
+// ------------------------------------------------------------------------------------------------
 // top-level forward helpers
 // ------------------------------------------------------------------------------------------------
 static int ensure_buf(sdm_ctx* e, void** p, size_t* cap, size_t need) {
@@ -2459,7 +2525,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -3678,6 +3744,86 @@ int sdm_compose_canvas(sdm_ctx* e, const float* fg, const float* alpha, int B, i
     }
     if (shadow) { tfree(e, tplane); tfree(e, layer); }
     tfree(e, place); tfree(e, box); tfree(e, raw);
+    return 0;
+  });
+}
+
+/* The distance field on its own (k_distance.h).  The class words, the carries and the column distances live in the activation arena.  Four launches,
+ * whatever the arguments. */
+int sdm_distance_field(sdm_ctx* e, const float* plane, int B, int H, int W, float threshold, int32_t* field, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !plane || !field) return SDM_ERR_INVALID;
+  TRY(df_check(e, "distance field", B, H, W, threshold));
+  const size_t bytes = (size_t)B * H * W * 4;
+  IoSpan in[] = {{(void*)plane, bytes}}, out[] = {{field, bytes}};
+  return product_call(e, ptr_kind, stream_arg, in, out, [&]() -> int {
+    DfScratch s = df_talloc(e, B, H, W);
+    if (!e->dry) {
+      DfEmit emit;
+      memset(&emit, 0, sizeof(emit));
+      emit.field = (int32_t*)out[0].p;
+      op_distance(e, (const float*)in[0].p, B, H, W, threshold, s, 0, emit);
+    }
+    df_tfree(e, s);
+    return 0;
+  });
+}
+
+/* Grow, shrink and feather a mask: the row pass of the distance field applies the ramp, the field itself is never stored.  Four launches. */
+int sdm_offset_mask(sdm_ctx* e, const float* mask, int B, int H, int W, float threshold, float offset_px, float feather_px, float* out_mask, int ptr_kind,
+                    void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !mask || !out_mask) return SDM_ERR_INVALID;
+  TRY(df_check(e, "offset mask", B, H, W, threshold));
+  if (!std::isfinite(offset_px) || !(offset_px >= -(float)SDM_DF_MAX_OFFSET) || !(offset_px <= (float)SDM_DF_MAX_OFFSET))
+    SDM_FAIL(e, SDM_ERR_INVALID, "offset mask: offset_px = %g must be a finite number within +-%d", (double)offset_px, SDM_DF_MAX_OFFSET);
+  if (!std::isfinite(feather_px) || !(feather_px >= 1.0f) || !(feather_px <= (float)SDM_DF_MAX_FEATHER))
+    SDM_FAIL(e, SDM_ERR_INVALID, "offset mask: feather_px = %g must be a finite number in [1, %d]", (double)feather_px, SDM_DF_MAX_FEATHER);
+  const size_t bytes = (size_t)B * H * W * 4;
+  IoSpan in[] = {{(void*)mask, bytes}}, out[] = {{out_mask, bytes}};
+  return product_call(e, ptr_kind, stream_arg, in, out, [&]() -> int {
+    DfScratch s = df_talloc(e, B, H, W);
+    if (!e->dry) {
+      DfEmit emit;
+      memset(&emit, 0, sizeof(emit));
+      emit.out = (float*)out[0].p; emit.offset = offset_px; emit.feather = feather_px;
+      op_distance(e, (const float*)in[0].p, B, H, W, threshold, s, 1, emit);
+    }
+    df_tfree(e, s);
+    return 0;
+  });
+}
+
+/* A stroke along the silhouette of a straight-alpha cut-out, composed with it in the row pass of the distance field of the alpha.  Four launches. */
+int sdm_outline(sdm_ctx* e, const float* fg, const float* alpha, int B, int H, int W, float edge_threshold, int position, float width_px, float softness_px,
+                const float* rgb3, float opacity, float* out_rgb, float* out_alpha, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !fg || !alpha || !rgb3 || !out_rgb || !out_alpha) return SDM_ERR_INVALID;
+  TRY(df_check(e, "outline", B, H, W, edge_threshold));
+  if (position < 0 || position > 2) SDM_FAIL(e, SDM_ERR_INVALID, "outline: position = %d outside 0 .. 2", position);
+  if (!std::isfinite(width_px) || !(width_px > 0.0f) || !(width_px <= (float)SDM_OUTLINE_MAX_WIDTH))
+    SDM_FAIL(e, SDM_ERR_INVALID, "outline: width_px = %g must be a finite number in (0, %d]", (double)width_px, SDM_OUTLINE_MAX_WIDTH);
+  if (!std::isfinite(softness_px) || !(softness_px >= 1.0f) || !(softness_px <= (float)SDM_DF_MAX_FEATHER))
+    SDM_FAIL(e, SDM_ERR_INVALID, "outline: softness_px = %g must be a finite number in [1, %d]", (double)softness_px, SDM_DF_MAX_FEATHER);
+  if (!std::isfinite(opacity) || !(opacity >= 0.0f) || !(opacity <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "outline: opacity = %g must be a finite number in [0, 1]", (double)opacity);
+  for (int c = 0; c < 3; ++c)
+    if (!std::isfinite(rgb3[c])) SDM_FAIL(e, SDM_ERR_INVALID, "outline: rgb3[%d] = %g must be finite", c, (double)rgb3[c]);
+  const size_t px = (size_t)B * H * W;
+  IoSpan in[] = {{(void*)fg, px * 12}, {(void*)alpha, px * 4}}, out[] = {{out_rgb, px * 12}, {out_alpha, px * 4}};
+  return product_call(e, ptr_kind, stream_arg, in, out, [&]() -> int {
+    DfScratch s = df_talloc(e, B, H, W);
+    if (!e->dry) {
+      DfEmit emit;
+      memset(&emit, 0, sizeof(emit));
+      emit.fg = (const float*)in[0].p; emit.alpha = (const float*)in[1].p; emit.out_rgb = (float*)out[0].p; emit.out_alpha = (float*)out[1].p;
+      emit.position = position; emit.softness = softness_px; emit.opacity = opacity;
+      emit.hi = position == 0 ? width_px : (position == 1 ? width_px * 0.5f : 0.0f);
+      emit.lo = position == 1 ? -width_px * 0.5f : -width_px;      // (not read for position 0: no lower edge)
+      for (int c = 0; c < 3; ++c) emit.rgb[c] = rgb3[c];
+      op_distance(e, emit.alpha, B, H, W, edge_threshold, s, 2, emit);
+    }
+    df_tfree(e, s);
     return 0;
   });
 }

@@ -83,6 +83,7 @@ EXPORTS = [
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
+    "sdm_distance_field", "sdm_offset_mask", "sdm_outline",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias", "sdm_op_cross_patch_planes", "sdm_op_cross_patch_planes_ex", "sdm_op_attention_shared", "sdm_debug_cross_attention", "sdm_op_cross_core",
@@ -126,6 +127,9 @@ class Bindings:
             "sdm_estimate_foreground": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
             "sdm_refine_alpha_guided": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp]),
             "sdm_compose_canvas": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
+            "sdm_distance_field": (i32, [vp, vp, i32, i32, i32, f32, vp, i32, vp]),
+            "sdm_offset_mask": (i32, [vp, vp, i32, i32, i32, f32, f32, f32, vp, i32, vp]),
+            "sdm_outline": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, f32, f32, vp, f32, vp, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
             "sdm_resident_bytes": (i64, [vp]),
@@ -803,6 +807,109 @@ class Engine:
         if sync:
             self.synchronize()
         return (out, place) if return_placement else out
+
+    DF_NONE = 2147483647         # SDM_DF_NONE (include/sdmatte.h)
+    DF_MAX_OFFSET = 1024         # SDM_DF_MAX_OFFSET
+    DF_MAX_FEATHER = 1024        # SDM_DF_MAX_FEATHER
+    OUTLINE_MAX_WIDTH = 1024     # SDM_OUTLINE_MAX_WIDTH
+    OUTLINE_POSITION = {"outside": 0, "center": 1, "inside": 2}
+
+    @classmethod
+    def _check_df_plane(cls, what, plane, threshold):
+        """The limits every distance-field call shares; returns (B, H, W, threshold as it crosses the C ABI)."""
+        if plane.dim() != 3 or plane.numel() == 0:
+            raise ValueError(f"{what}: the plane must be a non-empty [B,H,W], got {tuple(plane.shape)}")
+        B, H, W = (int(v) for v in plane.shape)
+        if max(H, W) > cls.FG_MAX_SIDE or B * H * W > cls.FG_MAX_PIXELS:
+            raise ValueError(f"{what}: {(B, H, W)} is too large (sides up to {cls.FG_MAX_SIDE}, {cls.FG_MAX_PIXELS} pixels in all)")
+        threshold = float(threshold)
+        if not (0.0 <= threshold < 1.0) or float(np.float32(threshold)) >= 1.0:
+            raise ValueError(f"{what}: threshold must be in [0, 1), got {threshold!r}")
+        return B, H, W, threshold
+
+    @staticmethod
+    def _check_f32_range(what, name, v, lo, hi, lo_open=False):
+        """A finite number in [lo, hi] (or (lo, hi]) after rounding to fp32, which is what the C ABI sees."""
+        import math
+        if isinstance(v, str):
+            raise ValueError(f"{what}: {name} must be a number, got {v!r}")
+        v = C.c_float(float(v)).value
+        if not math.isfinite(v) or v > hi or v < lo or (lo_open and v <= lo):
+            raise ValueError(f"{what}: {name} must be a finite number in {'(' if lo_open else '['}{lo}, {hi}], got {v!r}")
+        return v
+
+    def distance_field(self, plane, threshold=0.5, out=None, sync=True):
+        """The exact Euclidean distance transform on the GPU (sdm_distance_field): plane [B,H,W] -> int32 [B,H,W], +d2 for the pixels of
+        `plane > threshold` and -d2 for the others, d2 the squared distance to the nearest pixel of the other class of the same image (DF_NONE where
+        there is none).  Needs no loaded weights.  `sdmatte_nodes.distance_field` is the same function on CPU tensors, exactly."""
+        B, H, W, threshold = self._check_df_plane("distance_field", plane, threshold)
+        plane = plane.float().contiguous()
+        if out is None:
+            out = torch.empty(B, H, W, dtype=torch.int32, device=plane.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != B * H * W:
+            raise ValueError("distance_field: out must be a contiguous int32 tensor of B*H*W elements")
+        stream = self._check_io("distance_field", plane, out)
+        self._check(self.lib.sdm_distance_field(self.h, _ptr(plane), B, H, W, threshold, _ptr(out), self._kind(plane), stream), "sdm_distance_field")
+        if sync:
+            self.synchronize()
+        return out
+
+    def offset_mask(self, mask, offset_px=0.0, feather_px=1.0, threshold=0.5, out=None, sync=True):
+        """Grow (offset_px > 0), shrink (< 0) and feather a mask on the GPU (sdm_offset_mask): mask [B,H,W] -> fp32 [B,H,W] =
+        clamp((offset_px - sd) / feather_px + 0.5, 0, 1) with sd the signed distance to the silhouette of `mask > threshold` (negative inside).
+        (0, 1) gives the binarised mask; an integer offset r with feather 1 is exactly 1.0 on the dilation by the closed disk of radius r.  Needs no
+        loaded weights.  `sdmatte_nodes.offset_mask` is the same function on CPU tensors."""
+        B, H, W, threshold = self._check_df_plane("offset_mask", mask, threshold)
+        offset_px = self._check_f32_range("offset_mask", "offset_px", offset_px, -self.DF_MAX_OFFSET, self.DF_MAX_OFFSET)
+        feather_px = self._check_f32_range("offset_mask", "feather_px", feather_px, 1, self.DF_MAX_FEATHER)
+        mask = mask.float().contiguous()
+        if out is None:
+            out = torch.empty(B, H, W, dtype=torch.float32, device=mask.device)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * H * W:
+            raise ValueError("offset_mask: out must be a contiguous fp32 tensor of B*H*W elements")
+        stream = self._check_io("offset_mask", mask, out)
+        self._check(self.lib.sdm_offset_mask(self.h, _ptr(mask), B, H, W, threshold, offset_px, feather_px, _ptr(out), self._kind(mask), stream),
+                    "sdm_offset_mask")
+        if sync:
+            self.synchronize()
+        return out
+
+    def outline(self, fg_bhw3, alpha_bhw, width_px=8.0, color=(1.0, 1.0, 1.0), position="outside", softness_px=1.0, opacity=1.0, edge_threshold=0.5,
+                out=None, sync=True):
+        """An outline along the silhouette of a straight-alpha cut-out on the GPU (sdm_outline, defined in include/sdmatte.h): fg [B,H,W,3], alpha
+        [B,H,W] -> (rgb [B,H,W,3], alpha [B,H,W]), straight again.  The silhouette is that of `alpha > edge_threshold`; position "outside" (the stroke
+        lies under the subject), "center" or "inside" (over it), or 0 .. 2.  `out` is an (rgb, alpha) pair.  Needs no loaded weights.
+        `sdmatte_nodes.outline_cutout` is the same function in torch, equal to fp32 rounding."""
+        if fg_bhw3.dim() != 4 or fg_bhw3.shape[-1] != 3 or fg_bhw3.numel() == 0:
+            raise ValueError(f"outline: fg must be a non-empty [B,H,W,3], got {tuple(fg_bhw3.shape)}")
+        if tuple(alpha_bhw.shape) != tuple(fg_bhw3.shape[:3]):
+            raise ValueError(f"outline: alpha must be [B,H,W] = {tuple(fg_bhw3.shape[:3])}, got {tuple(alpha_bhw.shape)}")
+        B, H, W, edge_threshold = self._check_df_plane("outline", alpha_bhw, edge_threshold)
+        position = self.OUTLINE_POSITION.get(position, position)
+        if isinstance(position, str) or int(position) != position or not 0 <= int(position) <= 2:
+            raise ValueError(f"outline: position must be one of {sorted(self.OUTLINE_POSITION)} or 0 .. 2, got {position!r}")
+        width_px = self._check_f32_range("outline", "width_px", width_px, 0, self.OUTLINE_MAX_WIDTH, lo_open=True)
+        softness_px = self._check_f32_range("outline", "softness_px", softness_px, 1, self.DF_MAX_FEATHER)
+        opacity = self._check_f32_range("outline", "opacity", opacity, 0, 1)
+        rgb = np.ascontiguousarray(np.asarray(color, np.float32).reshape(-1))
+        if rgb.shape != (3, ) or not np.isfinite(rgb).all():
+            raise ValueError(f"outline: color must be 3 finite numbers, got {color!r}")
+        fg_bhw3 = fg_bhw3.float().contiguous()
+        alpha_bhw = alpha_bhw.float().contiguous()
+        dev = fg_bhw3.device
+        if out is None:
+            out = (torch.empty(B, H, W, 3, dtype=torch.float32, device=dev), torch.empty(B, H, W, dtype=torch.float32, device=dev))
+        out_rgb, out_alpha = out
+        for t, shape in ((out_rgb, (B, H, W, 3)), (out_alpha, (B, H, W))):
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"outline: out must be a pair of contiguous fp32 tensors {(B, H, W, 3)} and {(B, H, W)}")
+        stream = self._check_io("outline", fg_bhw3, alpha_bhw, out_rgb, out_alpha)
+        self._check(self.lib.sdm_outline(self.h, _ptr(fg_bhw3), _ptr(alpha_bhw), B, H, W, edge_threshold, int(position), width_px, softness_px,
+                                         rgb.ctypes.data_as(C.c_void_p), opacity, _ptr(out_rgb), _ptr(out_alpha), self._kind(fg_bhw3), stream),
+                    "sdm_outline")
+        if sync:
+            self.synchronize()
+        return out_rgb, out_alpha
 
     def synchronize(self):
         self._check(self.lib.sdm_synchronize(self.h), "sdm_synchronize")

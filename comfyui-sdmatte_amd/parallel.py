@@ -397,5 +397,17 @@ class MultiGpuEngine:
                                               shadow_opacity, shadow_sigma, shadow_dy, shadow_dx, roi_threshold, out_channels,
                                               return_placement=return_placement)
 
+    def distance_field(self, plane_bhw, threshold=0.5):
+        """The exact distance field (no model involved): on the first engine; plane [B,H,W] (host or any device) -> int32 [B,H,W] on the HOST."""
+        return self.engines[0].distance_field(self._to_host(plane_bhw), threshold)
+
+    def offset_mask(self, mask_bhw, offset_px=0.0, feather_px=1.0, threshold=0.5):
+        """Grow / shrink / feather a mask (no model involved): on the first engine; mask [B,H,W] (host or any device) -> fp32 [B,H,W] on the HOST."""
+        return self.engines[0].offset_mask(self._to_host(mask_bhw), offset_px, feather_px, threshold)
+
+    def outline(self, fg_bhw3, alpha_bhw, width_px=8.0, color=(1.0, 1.0, 1.0), position="outside", softness_px=1.0, opacity=1.0, edge_threshold=0.5):
+        """An outline around a cut-out (no model involved): on the first engine; inputs on the host or any device -> (rgb, alpha) on the HOST."""
+        return self.engines[0].outline(self._to_host(fg_bhw3), self._to_host(alpha_bhw), width_px, color, position, softness_px, opacity, edge_threshold)
+
     def last_forward_ms(self):
         return max(e.last_forward_ms() for e in self.engines)

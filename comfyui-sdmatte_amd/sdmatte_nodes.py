@@ -788,6 +788,105 @@ def guided_refine_alpha(image, alpha, subsample, radius=2, eps=1e-4):
     return ((up[..., :3] * image).sum(-1) + up[..., 3]).clamp(0.0, 1.0).contiguous()
 
 
+DF_NONE = 2147483647      # SDM_DF_NONE (include/sdmatte.h)
+OUTLINE_POSITION = {"outside": 0, "center": 1, "inside": 2}
+
+
+def _nearest_other_sq(other):
+    """other: bool [H,W].  int64 [H,W]: the squared distance of every pixel to the nearest True pixel, DF_NONE without one.  Exact: column distances by
+    two running scans, then the lower envelope of the rows' parabolas by an outward search that stops once dx^2 reaches the largest best."""
+    import numpy as np
+    H, W = other.shape
+    big = np.int64(1) << 40
+    if not other.any():
+        return np.full((H, W), DF_NONE, np.int64)
+    rows = np.arange(H, dtype=np.int64)[:, None]
+    above = np.maximum.accumulate(np.where(other, rows, -big), axis=0)                      # row of the nearest True pixel at or above
+    below = np.minimum.accumulate(np.where(other, rows, big)[::-1], axis=0)[::-1]           # ... at or below
+    g = np.minimum(rows - above, below - rows)
+    g2 = np.where(g >= big // 2, big, g * g)
+    best = g2.copy()
+    for dx in range(1, W):
+        d2 = np.int64(dx) * dx
+        if d2 >= best.max():
+            break
+        np.minimum(best[:, dx:], g2[:, :-dx] + d2, out=best[:, dx:])
+        np.minimum(best[:, :-dx], g2[:, dx:] + d2, out=best[:, :-dx])
+    return best
+
+
+def distance_field(plane, threshold=0.5):
+    """CPU restatement of the GPU op `Engine.distance_field` (sdm_distance_field, defined in include/sdmatte.h): plane [B,H,W] -> int32 [B,H,W], +d2 on
+    the pixels of `plane > threshold`, -d2 on the others, d2 the squared Euclidean distance to the nearest pixel of the other class of the same image
+    (DF_NONE where that class is empty).  Integers only: exact."""
+    if plane.dim() != 3 or plane.numel() == 0:
+        raise ValueError(f"distance_field: plane must be a non-empty [B,H,W], got {tuple(plane.shape)}")
+    import numpy as np
+    with np.errstate(invalid="ignore"):
+        fg = plane.detach().cpu().float().numpy() > np.float32(threshold)
+    out = np.empty(fg.shape, np.int32)
+    for b in range(fg.shape[0]):
+        out[b] = np.where(fg[b], _nearest_other_sq(~fg[b]), -_nearest_other_sq(fg[b])).astype(np.int32)
+    return torch.from_numpy(out)
+
+
+def _signed_distance(field, dtype):
+    r = field.abs().to(dtype).sqrt() - 0.5
+    return torch.where(field > 0, -r, r)
+
+
+def _ramp(num, den):
+    return (num / den + 0.5).clamp(0.0, 1.0)
+
+
+def offset_mask(mask, offset_px=0.0, feather_px=1.0, threshold=0.5, dtype=torch.float32):
+    """CPU restatement of the GPU op `Engine.offset_mask` (sdm_offset_mask): clamp((offset_px - sd) / feather_px + 0.5, 0, 1) with sd the signed
+    distance to the silhouette of `mask > threshold`.  The parameters are rounded to fp32 first, as they cross the C ABI that way; `dtype` is the
+    precision of the arithmetic (float64: the yardstick of the tests)."""
+    from .engine import Engine
+    Engine._check_df_plane("offset_mask", mask, threshold)
+    offset_px = Engine._check_f32_range("offset_mask", "offset_px", offset_px, -Engine.DF_MAX_OFFSET, Engine.DF_MAX_OFFSET)
+    feather_px = Engine._check_f32_range("offset_mask", "feather_px", feather_px, 1, Engine.DF_MAX_FEATHER)
+    sd = _signed_distance(distance_field(mask, threshold), dtype)
+    return _ramp(torch.tensor(offset_px, dtype=dtype) - sd, torch.tensor(feather_px, dtype=dtype))
+
+
+def outline_cutout(fg, alpha, width_px=8.0, color=(1.0, 1.0, 1.0), position="outside", softness_px=1.0, opacity=1.0, edge_threshold=0.5,
+                   dtype=torch.float32):
+    """CPU restatement of the GPU op `Engine.outline` (sdm_outline, defined in include/sdmatte.h): (rgb [B,H,W,3], alpha [B,H,W]) of the straight-alpha
+    cut-out with a stroke along the silhouette of `alpha > edge_threshold`.  Parameters rounded to fp32 first; `dtype` as in offset_mask."""
+    from .engine import Engine
+    if fg.dim() != 4 or fg.shape[-1] != 3 or tuple(alpha.shape) != tuple(fg.shape[:3]):
+        raise ValueError(f"outline_cutout: fg must be [B,H,W,3] and alpha [B,H,W], got {tuple(fg.shape)} and {tuple(alpha.shape)}")
+    Engine._check_df_plane("outline_cutout", alpha, edge_threshold)
+    position = OUTLINE_POSITION.get(position, position)
+    if isinstance(position, str) or int(position) != position or not 0 <= int(position) <= 2:
+        raise ValueError(f"outline_cutout: position must be one of {sorted(OUTLINE_POSITION)} or 0 .. 2, got {position!r}")
+    width = torch.tensor(Engine._check_f32_range("outline_cutout", "width_px", width_px, 0, Engine.OUTLINE_MAX_WIDTH, lo_open=True), dtype=torch.float32)
+    soft = torch.tensor(Engine._check_f32_range("outline_cutout", "softness_px", softness_px, 1, Engine.DF_MAX_FEATHER), dtype=dtype)
+    opacity = torch.tensor(Engine._check_f32_range("outline_cutout", "opacity", opacity, 0, 1), dtype=dtype)
+    rgb = torch.tensor([float(v) for v in color], dtype=torch.float32)
+    if rgb.shape != (3, ) or not bool(torch.isfinite(rgb).all()):
+        raise ValueError(f"outline_cutout: color must be 3 finite numbers, got {color!r}")
+    rgb = rgb.to(dtype)
+    alpha = alpha.detach().cpu().float()
+    F = fg.detach().cpu().float().to(dtype)
+    sd = _signed_distance(distance_field(alpha, edge_threshold), dtype)
+    # the band's edges are fp32 values (width / 2 is exact)
+    hi = (width if position == 0 else (width * 0.5 if position == 1 else torch.zeros(()))).to(dtype)
+    lo = (-width * 0.5 if position == 1 else -width).to(dtype)
+    c = _ramp(hi - sd, soft)
+    if position != 0:
+        c = c * _ramp(sd - lo, soft)
+    a = torch.nan_to_num(alpha, nan=0.0).clamp(0.0, 1.0).to(dtype)
+    a_s = c * opacity
+    ws = a_s * (1.0 - a) if position == 0 else a_s
+    A = a + ws if position == 0 else a_s + a * (1.0 - a_s)
+    t = torch.where(A > 0, ws / torch.where(A > 0, A, torch.ones_like(A)), torch.zeros_like(A)).unsqueeze(-1)
+    mixed = torch.where((a > 0).unsqueeze(-1), F + (rgb - F) * t, rgb.expand_as(F))
+    return torch.where((A > 0).unsqueeze(-1), mixed, torch.zeros_like(F)), A
+
+
 class SDMatteApply:
 
     @classmethod
@@ -1201,11 +1300,75 @@ class SDMatteCanvas:
         return (_trimap_engine(_torch_device()).compose_canvas(*args), )
 
 
+class SDMatteOffsetMask:
+    """MASK -> MASK: grow, shrink and feather a mask by any number of pixels on the GPU (the exact Euclidean distance transform; no radius cap, one
+    pass whatever the radius).  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"mask": ("MASK", {"tooltip": "mask to grow (offset above 0) or shrink (below 0)"}),
+                             "offset_px": ("FLOAT", {"default": 0.0, "min": -1024.0, "max": 1024.0, "step": 0.5, "tooltip": "how far the edge moves outwards, in pixels"}),
+                             "feather_px": ("FLOAT", {"default": 1.0, "min": 1.0, "max": 1024.0, "step": 0.5, "tooltip": "width of the ramp across the new edge (1 = hard)"})},
+                "optional": {"threshold": ("FLOAT", {"default": 0.5, "min": 0.0, "max": 0.99, "step": 0.01, "tooltip": "the mask's foreground is mask > threshold"}),
+                             "force_cpu": ("BOOLEAN", {"default": False, "tooltip": "evaluate the numpy / torch restatement on the CPU instead of the GPU call"})}}
+
+    RETURN_TYPES = ("MASK", )
+    RETURN_NAMES = ("mask", )
+    FUNCTION = "offset"
+    CATEGORY = "Matting/SDMatte"
+
+    def offset(self, mask, offset_px, feather_px, threshold=0.5, force_cpu=False):
+        if mask.dim() == 2:
+            mask = mask.unsqueeze(0)
+        args = (mask.detach().cpu(), float(offset_px), float(feather_px), float(threshold))
+        if force_cpu:      # an explicit request, never a silent substitute
+            return (offset_mask(*args), )
+        return (_trimap_engine(_torch_device()).offset_mask(*args), )
+
+
+class SDMatteOutline:
+    """Foreground + alpha -> the cut-out with an outline (the "sticker" stroke) along its silhouette on the GPU, as straight colours and alpha: what
+    SDMatte Canvas takes.  The stroke stays inside the frame: place the cut-out on a canvas first to give it room.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"foreground": ("IMAGE", {"tooltip": "foreground colours of the cut-out"}),
+                             "alpha": ("MASK", {"tooltip": "alpha matte of the foreground"}),
+                             "width_px": ("FLOAT", {"default": 8.0, "min": 0.5, "max": 1024.0, "step": 0.5}),
+                             "position": (list(OUTLINE_POSITION), {"default": "outside", "tooltip": "outside: under the subject; center / inside: over it"})},
+                "optional": {"red": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.01}),
+                             "green": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.01}),
+                             "blue": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.01}),
+                             "opacity": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.01}),
+                             "softness_px": ("FLOAT", {"default": 1.0, "min": 1.0, "max": 1024.0, "step": 0.5, "tooltip": "width of the stroke's soft edges (1 = hard)"}),
+                             "edge_threshold": ("FLOAT", {"default": 0.5, "min": 0.0, "max": 0.99, "step": 0.01, "tooltip": "the silhouette is that of alpha > edge_threshold"}),
+                             "force_cpu": ("BOOLEAN", {"default": False, "tooltip": "evaluate the torch restatement on the CPU instead of the GPU call"})}}
+
+    RETURN_TYPES = ("IMAGE", "MASK")
+    RETURN_NAMES = ("foreground", "alpha")
+    FUNCTION = "outline"
+    CATEGORY = "Matting/SDMatte"
+
+    def outline(self, foreground, alpha, width_px, position, red=1.0, green=1.0, blue=1.0, opacity=1.0, softness_px=1.0, edge_threshold=0.5, force_cpu=False):
+        if foreground.dim() != 4 or foreground.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] foreground must be [B,H,W,3], got {tuple(foreground.shape)}")
+        if alpha.dim() == 2:
+            alpha = alpha.unsqueeze(0)
+        if tuple(alpha.shape) != tuple(foreground.shape[:3]):
+            raise ValueError(f"[SDMatte] alpha must be [B,H,W] of the foreground {tuple(foreground.shape[:3])}, got {tuple(alpha.shape)}")
+        args = (foreground.detach().cpu(), alpha.detach().cpu(), float(width_px), (float(red), float(green), float(blue)), position, float(softness_px),
+                float(opacity), float(edge_threshold))
+        if force_cpu:      # an explicit request, never a silent substitute
+            return outline_cutout(*args)
+        return _trimap_engine(_torch_device()).outline(*args)
+
+
 def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False, canvas: bool = False,
-                  subjects: bool = False):
+                  subjects: bool = False, edge: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
     node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`, plus the subject-box node when `roi`,
-    plus the canvas node when `canvas`, plus the box-per-subject node when `subjects`."""
+    plus the canvas node when `canvas`, plus the box-per-subject node when `subjects`, plus the two
+    distance-field nodes (mask offset, outline) when `edge`."""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
@@ -1229,10 +1392,13 @@ def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, c
     if subjects:
         classes["SDMatteApplySubjects"] = SDMatteApplySubjects
         names["SDMatteApplySubjects"] = "Apply SDMatte (Subjects)"
+    if edge:
+        classes.update({"SDMatteOffsetMask": SDMatteOffsetMask, "SDMatteOutline": SDMatteOutline})
+        names.update({"SDMatteOffsetMask": "SDMatte Grow / Shrink Mask", "SDMatteOutline": "SDMatte Outline"})
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1), like the multi-GPU fan-out
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
 NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
@@ -1240,4 +1406,5 @@ NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("
                                                                 os.environ.get("SDMATTE_CLEAN_NODE") == "1",
                                                                 os.environ.get("SDMATTE_ROI_NODE") == "1",
                                                                 os.environ.get("SDMATTE_CANVAS_NODE") == "1",
-                                                                os.environ.get("SDMATTE_SUBJECTS_NODE") == "1")
+                                                                os.environ.get("SDMATTE_SUBJECTS_NODE") == "1",
+                                                                os.environ.get("SDMATTE_EDGE_NODES") == "1")

@@ -396,6 +396,61 @@ int sdm_compose_canvas(sdm_ctx* ctx, const float* fg_bhw3, const float* alpha_bh
                        int fill_pct, int valign, int bg_mode, const float* bg_rgb3, const float* bg_image, int bg_batch, float shadow_opacity,
                        float shadow_sigma, int shadow_dy, int shadow_dx, float* out, int out_channels, int32_t* place_out, int ptr_kind, void* stream);
 
+/* The exact Euclidean distance transform, on the GPU (beyond the reference): the primitive under "grow / shrink / feather a mask by any amount" and under
+ * an outline around a cut-out; sdm_make_trimap's morphology is capped at SDM_TRIMAP_MAX_RADIUS and yields 0 / 0.5 / 1 only.
+ * plane fp32 [B,H,W] -> field_bhw int32 [B,H,W], of the same pointer kind.
+ *   F        = { p : plane[p] > threshold } (one fp32 compare, so NaN is outside F).  Images of a batch are independent; pixels beyond the border do not
+ *            exist, as in sdm_make_trimap.
+ *   d2(p)    the minimum of dy^2 + dx^2 over the pixels of the OTHER class (outside F for p in F, in F otherwise) of the same image; SDM_DF_NONE where
+ *            that class is empty in the image.  No radius cap.
+ *   field[p] = +d2(p) for p in F, -d2(p) otherwise.  Hence |field| >= 1 everywhere, and the largest real value, 2 * 32767^2, is below SDM_DF_NONE.
+ * The trimap of sdm_make_trimap is 1.0 where field > erode_px^2, 0.0 where field < -dilate_px^2 and 0.5 elsewhere.
+ * Integer arithmetic only: GPU, emulator and sdmatte_nodes.distance_field agree exactly.  threshold finite in [0, 1), B, H, W >= 1 within SDM_FG_MAX_SIDE /
+ * SDM_FG_MAX_PIXELS: SDM_ERR_INVALID otherwise, and then nothing is queued or written.  Stream contract and pointer kinds as sdm_subject_roi;
+ * sdm_last_forward_ms covers the launches.  Needs no weights.  Four kernel launches (csrc/k_distance.h), whatever B, H, W and the content, no host
+ * readback: df_bits (one class bit per pixel), df_carry (per column, the nearest row of either class above and below every 32-row tile), df_cols (the
+ * column distances, 2 bytes per pixel), df_rows (per row the lower envelope of the columns' parabolas; writes the field).  These are the names in
+ * sdm_kernel_counts and the per-launch profile.  The class words, the carries and the column distances are part of the activation arena, host
+ * pointers go through the I/O staging (sdm_resident_bytes counts both, sdm_release_memory frees them). */
+#define SDM_DF_NONE 2147483647
+int sdm_distance_field(sdm_ctx* ctx, const float* plane_bhw, int B, int H, int W, float threshold, int32_t* field_bhw, int ptr_kind, void* stream);
+/* Grow (offset_px > 0), shrink (< 0) and feather a mask by any amount: mask fp32 [B,H,W] -> out fp32 [B,H,W].  With the field of mask > threshold:
+ *   sd(p)    = sqrt((float)|field[p]|) - 0.5, negated for the pixels of F: the signed distance to the silhouette, which runs half-way between the two
+ *            classes.  Negative inside, positive outside, -0.5 to +0.5 across the silhouette.  sqrt is the correctly rounded fp32 square root.
+ *   out[p]   = clamp((offset_px - sd(p)) / feather_px + 0.5, 0, 1), fp32 throughout, a true fp32 division.
+ * Consequences, exact in fp32:
+ *   offset_px = 0, feather_px = 1 returns the binarised mask (1.0 on F, 0.0 elsewhere);
+ *   an integer offset_px = r >= 0 with feather_px = 1 gives out == 1.0 exactly on the dilation of F by the closed disk of radius r (d2 <= r^2),
+ *   and out > 0 exactly where d2 < (r + 1)^2.
+ * SDM_DF_MAX_OFFSET is what keeps the second one true: sqrtf(r^2 + 1) > r holds for r up to 2048 and fails at 4096.
+ * An empty or a full F is not an error: |field| is SDM_DF_NONE and the formulas apply.  threshold, B, H, W as sdm_distance_field, offset_px finite
+ * within +-SDM_DF_MAX_OFFSET, feather_px finite in [1, SDM_DF_MAX_FEATHER]: SDM_ERR_INVALID otherwise, and then nothing is queued or written.
+ * sdmatte_nodes.offset_mask is the same function on CPU tensors.  Stream contract, pointer kinds, weights and memory as sdm_distance_field.  Four
+ * launches: df_bits, df_carry, df_cols, df_offset (the row pass with the ramp applied in registers: the field is never stored). */
+#define SDM_DF_MAX_OFFSET 1024
+#define SDM_DF_MAX_FEATHER 1024
+int sdm_offset_mask(sdm_ctx* ctx, const float* mask_bhw, int B, int H, int W, float threshold, float offset_px, float feather_px, float* out_bhw,
+                    int ptr_kind, void* stream);
+/* An outline (the "sticker" stroke) along the silhouette of a straight-alpha cut-out: fg fp32 [B,H,W,3], alpha fp32 [B,H,W] -> out_rgb [B,H,W,3],
+ * out_alpha [B,H,W], straight again: what sdm_compose_canvas takes as foreground and alpha.
+ *   a        the alpha with NaN -> 0, clamped to [0, 1].  The field is that of the RAW alpha > edge_threshold, sd as in sdm_offset_mask.
+ *   band     [lo, hi] by position: 0 outside: lo = -inf, hi = width_px (the stroke is the dilated silhouette and lies UNDER the subject);
+ *            1 centre: [-width_px / 2, width_px / 2]; 2 inside: [-width_px, 0] (both OVER the subject).
+ *   coverage c = clamp((hi - sd) / softness_px + 0.5, 0, 1) * clamp((sd - lo) / softness_px + 0.5, 0, 1); the second factor is 1 for lo = -inf.
+ *   layers   premultiplied: the stroke (c * opacity * rgb3, As = c * opacity) and the subject (a * F, a); "over" in the order of the position.
+ *            out_alpha A = a + As * (1 - a) for position 0, As + a * (1 - As) otherwise.
+ *   out_rgb  the straight colour P / A where A > 0, else 0, evaluated as F + (rgb3 - F) * (ws / A) with ws the stroke's share of A (As * (1 - a) for
+ *            position 0, As otherwise): exactly F where the stroke adds nothing (opacity 0 returns the subject unchanged), and exactly rgb3 where
+ *            a == 0 (the subject's colour means nothing there, whatever it holds).
+ * rgb3 is 3 finite floats, ALWAYS a HOST pointer.  An empty or a full silhouette is not an error.  A stroke does not extend beyond the frame: place the
+ * cut-out with sdm_compose_canvas first.  B, H, W as sdm_distance_field, edge_threshold finite in [0, 1), position in 0 .. 2, width_px finite in
+ * (0, SDM_OUTLINE_MAX_WIDTH], softness_px finite in [1, SDM_DF_MAX_FEATHER], opacity finite in [0, 1]: SDM_ERR_INVALID otherwise, and then nothing is
+ * queued or written.  sdmatte_nodes.outline_cutout is the same function in torch (equal to fp32 rounding).  Stream contract, pointer kinds, weights and
+ * memory as sdm_distance_field.  Four launches: df_bits, df_carry, df_cols, df_outline (the row pass with the composition applied in registers). */
+#define SDM_OUTLINE_MAX_WIDTH 1024
+int sdm_outline(sdm_ctx* ctx, const float* fg_bhw3, const float* alpha_bhw, int B, int H, int W, float edge_threshold, int position, float width_px,
+                float softness_px, const float* rgb3, float opacity, float* out_rgb_bhw3, float* out_alpha_bhw, int ptr_kind, void* stream);
+
 /* Memory the engine holds outside any framework allocator: packed weights + activation arena (sized by the largest batch /
  * resolution seen) + I/O staging.  sdm_release_memory frees everything but the weights (the next forward re-allocates). */
 int64_t sdm_resident_bytes(sdm_ctx* ctx);
