@@ -21,6 +21,7 @@
 #include "k_cclabel.h"
 #include "k_foreground.h"
 #include "k_guided.h"
+#include "k_temporal.h"
 #include "k_roi.h"
 #include "k_canvas.h"
 #include "k_boxes.h"
@@ -2525,7 +2526,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -3434,6 +3435,50 @@ int sdm_refine_alpha_guided(sdm_ctx* e, const float* image, const float* alpha, 
       prof_end(e);
     }
     tfree(e, abar); tfree(e, ab); tfree(e, coarse);
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// temporal smoothing of the alpha, guided by the frames (k_temporal.h): the batch axis is time
+// ------------------------------------------------------------------------------------------------
+/* Nothing in the arena.  One launch, whatever the arguments. */
+int sdm_smooth_alpha_temporal(sdm_ctx* e, const float* image, const float* alpha, int B, int H, int W, int clip_len, int radius, int patch,
+                              float color_tolerance, float strength, float max_change, float* out, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !alpha || !out) return SDM_ERR_INVALID;
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: bad image size %dx%dx%d", B, H, W);
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: %dx%dx%d is too large (sides up to %d, %d pixels in all)", B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  if (clip_len < 0 || clip_len > B) SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: clip_len = %d outside 0 .. B = %d", clip_len, B);
+  if (radius < 1 || radius > SDM_TS_MAX_RADIUS) SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: radius = %d outside 1 .. %d", radius, SDM_TS_MAX_RADIUS);
+  if (patch < 0 || patch > SDM_TS_MAX_PATCH) SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: patch = %d outside 0 .. %d", patch, SDM_TS_MAX_PATCH);
+  if (!std::isfinite(color_tolerance) || !(color_tolerance >= 1.0f / 1024.0f) || !(color_tolerance <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: color_tolerance = %g must be a finite number in [1/1024, 1]", (double)color_tolerance);
+  if (!std::isfinite(strength) || !(strength >= 0.0f) || !(strength <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: strength = %g must be a finite number in [0, 1]", (double)strength);
+  if (!std::isfinite(max_change) || !(max_change >= 0.0f) || !(max_change <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: max_change = %g must be a finite number in [0, 1]", (double)max_change);
+  const size_t px = (size_t)B * H * W;
+  IoSpan in[] = {{(void*)image, px * 12}, {(void*)alpha, px * 4}}, outs[] = {{out, px * 4}};
+  const int L = clip_len ? clip_len : B;
+  const float tau2 = color_tolerance * color_tolerance;
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_img = (const float*)in[0].p; const float* d_alpha = (const float*)in[1].p; float* d_out = (float*)outs[0].p;
+    if (!e->dry) {
+      const int vec = W % 4 == 0 && aligned16(d_img) && aligned16(d_alpha) && aligned16(d_out) ? 1 : 0;
+      const dim3 grid((unsigned)(sdm_cdiv(B, L) * sdm_cdiv(H, ts_tile_h(patch)) * sdm_cdiv(W, SDM_TS_TW))), blk(256);
+      prof_begin(e, "ts_smooth", 0, (double)px * 20);
+      count_kernel("ts_smooth");
+#define SDM_TS_CASE(R, P) \
+  case (R) * 3 + (P): SDM_LAUNCH((ts_smooth_kernel<R, P>), grid, blk, 0, e->stream, d_img, d_alpha, B, H, W, L, tau2, strength, max_change, vec, d_out); break
+      switch (radius * 3 + patch) {
+        SDM_TS_CASE(1, 0); SDM_TS_CASE(1, 1); SDM_TS_CASE(1, 2); SDM_TS_CASE(2, 0); SDM_TS_CASE(2, 1); SDM_TS_CASE(2, 2);
+        SDM_TS_CASE(3, 0); SDM_TS_CASE(3, 1); SDM_TS_CASE(3, 2); SDM_TS_CASE(4, 0); SDM_TS_CASE(4, 1); SDM_TS_CASE(4, 2);
+      }
+#undef SDM_TS_CASE
+      prof_end(e);
+    }
     return 0;
   });
 }

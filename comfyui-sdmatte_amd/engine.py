@@ -83,7 +83,7 @@ EXPORTS = [
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
-    "sdm_distance_field", "sdm_offset_mask", "sdm_outline",
+    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias", "sdm_op_cross_patch_planes", "sdm_op_cross_patch_planes_ex", "sdm_op_attention_shared", "sdm_debug_cross_attention", "sdm_op_cross_core",
@@ -130,6 +130,7 @@ class Bindings:
             "sdm_distance_field": (i32, [vp, vp, i32, i32, i32, f32, vp, i32, vp]),
             "sdm_offset_mask": (i32, [vp, vp, i32, i32, i32, f32, f32, f32, vp, i32, vp]),
             "sdm_outline": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, f32, f32, vp, f32, vp, vp, i32, vp]),
+            "sdm_smooth_alpha_temporal": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
             "sdm_resident_bytes": (i64, [vp]),
@@ -910,6 +911,47 @@ class Engine:
         if sync:
             self.synchronize()
         return out_rgb, out_alpha
+
+    # SDM_TS_* (include/sdmatte.h)
+    TS_DEFAULTS = {"radius": 2, "patch": 1, "color_tolerance": 0.1, "strength": 1.0, "max_change": 1.0, "clip_len": 0}
+    TS_MAX_RADIUS = 4
+    TS_MAX_PATCH = 2
+
+    @classmethod
+    def _check_ts_params(cls, what, B, radius, patch, color_tolerance, strength, max_change, clip_len):
+        """The argument limits of sdm_smooth_alpha_temporal; returns the values that cross the C ABI (the floats rounded to fp32)."""
+        for name, v, lo, hi in (("radius", radius, 1, cls.TS_MAX_RADIUS), ("patch", patch, 0, cls.TS_MAX_PATCH), ("clip_len", clip_len, 0, B)):
+            if isinstance(v, str) or int(v) != v or not lo <= int(v) <= hi:
+                raise ValueError(f"{what}: {name} must be an integer in {lo} .. {hi}, got {v!r}")
+        color_tolerance = cls._check_f32_range(what, "color_tolerance", color_tolerance, 1.0 / 1024.0, 1)
+        strength = cls._check_f32_range(what, "strength", strength, 0, 1)
+        max_change = cls._check_f32_range(what, "max_change", max_change, 0, 1)
+        return int(radius), int(patch), color_tolerance, strength, max_change, int(clip_len)
+
+    def smooth_alpha_temporal(self, image_bhwc, alpha_bhw, radius=2, patch=1, color_tolerance=0.1, strength=1.0, max_change=1.0, clip_len=0, sync=True):
+        """The alpha [B,H,W] of B consecutive frames [B,H,W,3] filtered along time on the GPU (sdm_smooth_alpha_temporal, defined in include/sdmatte.h):
+        a frame within `radius` contributes to a pixel as far as the `patch` neighbourhood of that pixel did not change between the two frames
+        (`color_tolerance`); where it did, the weight is exactly 0.  `clip_len` > 0 cuts the batch into independent clips of that many frames.  Returns fp32
+        [B,H,W] in [0,1] on the inputs' device.  One kernel launch.  Needs no loaded weights.  `sdmatte_nodes.temporal_smooth_alpha` is the same function
+        in torch, equal to fp32 rounding."""
+        if image_bhwc.dim() != 4 or image_bhwc.shape[-1] != 3 or image_bhwc.numel() == 0:
+            raise ValueError(f"smooth_alpha_temporal: image must be a non-empty [B,H,W,3], got {tuple(image_bhwc.shape)}")
+        B, H, W, _ = (int(v) for v in image_bhwc.shape)
+        if tuple(alpha_bhw.shape) != (B, H, W):
+            raise ValueError(f"smooth_alpha_temporal: alpha must be [B,H,W] = {(B, H, W)}, got {tuple(alpha_bhw.shape)}")
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"smooth_alpha_temporal: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        radius, patch, color_tolerance, strength, max_change, clip_len = self._check_ts_params(
+            "smooth_alpha_temporal", B, radius, patch, color_tolerance, strength, max_change, clip_len)
+        image_bhwc = image_bhwc.float().contiguous()
+        alpha_bhw = alpha_bhw.float().contiguous()
+        out = torch.empty(B, H, W, dtype=torch.float32, device=image_bhwc.device)
+        stream = self._check_io("smooth_alpha_temporal", image_bhwc, alpha_bhw, out)
+        self._check(self.lib.sdm_smooth_alpha_temporal(self.h, _ptr(image_bhwc), _ptr(alpha_bhw), B, H, W, clip_len, radius, patch, color_tolerance,
+                                                       strength, max_change, _ptr(out), self._kind(image_bhwc), stream), "sdm_smooth_alpha_temporal")
+        if sync:
+            self.synchronize()
+        return out
 
     def synchronize(self):
         self._check(self.lib.sdm_synchronize(self.h), "sdm_synchronize")

@@ -299,6 +299,12 @@ class MultiGpuEngine:
         on the HOST."""
         return self.engines[0].refine_alpha_guided(self._to_host(image_bhwc), self._to_host(alpha_bhw), subsample, radius, eps)
 
+    def smooth_alpha_temporal(self, image_bhwc, alpha_bhw, radius=2, patch=1, color_tolerance=0.1, strength=1.0, max_change=1.0, clip_len=0):
+        """The alpha filtered along time (no model involved): on the first engine - the frames of a clip are coupled, so there is no batch split;
+        inputs on the host or any device -> alpha [B,H,W] on the HOST."""
+        return self.engines[0].smooth_alpha_temporal(self._to_host(image_bhwc), self._to_host(alpha_bhw), radius, patch, color_tolerance, strength,
+                                                     max_change, clip_len)
+
     def apply_matte_mask(self, image_bhwc, mask_bhw, S, is_transparent, output_mode, mask_refine, trimap_constraint, threshold=0.5, erode_px=10,
                          dilate_px=10):
         """`apply_matte_node` with the trimap made from the mask on each GPU (images are independent: so are their trimaps); returns

@@ -25,6 +25,8 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
   * and one registered only with SDMATTE_CANVAS_NODE=1: `SDMatteCanvas` frames a straight-alpha cut-out on a canvas of a given size (scaled, aligned,
     over a colour, an image or transparency, with an optional soft shadow), resampled premultiplied, in one engine call; `canvas_fit` is the exact
     restatement of its placement and `compose_canvas` its torch restatement;
+  * and one registered only with SDMATTE_VIDEO_NODE=1: `SDMatteTemporalSmooth` takes the batch as a clip and filters the alpha along time, guided by
+    the frames themselves, in one kernel launch; `temporal_smooth_alpha` below is its torch restatement;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -887,6 +889,45 @@ def outline_cutout(fg, alpha, width_px=8.0, color=(1.0, 1.0, 1.0), position="out
     return torch.where((A > 0).unsqueeze(-1), mixed, torch.zeros_like(F)), A
 
 
+def temporal_smooth_alpha(image, alpha, radius=2, patch=1, color_tolerance=0.1, strength=1.0, max_change=1.0, clip_len=0):
+    """`Engine.smooth_alpha_temporal` in torch fp32, on the tensors' own device (the image-guided temporal filter defined in include/sdmatte.h): the
+    alpha [B,H,W] of B consecutive frames [B,H,W,3] -> fp32 [B,H,W] in [0,1].  Equal to the kernel to fp32 rounding, not bit for bit; the identities of
+    the header (strength 0, max_change 0, one frame, clip_len 1, a hard cut, clips = separate calls) hold exactly here too.  It materialises two
+    full-size tensors per offset k, which is what the kernel is there to avoid."""
+    import torch.nn.functional as F
+    from .engine import Engine
+    if image.dim() != 4 or image.shape[-1] != 3 or image.numel() == 0:
+        raise ValueError(f"temporal_smooth_alpha: image must be a non-empty [B,H,W,3], got {tuple(image.shape)}")
+    if tuple(alpha.shape) != tuple(image.shape[:3]):
+        raise ValueError(f"temporal_smooth_alpha: alpha must be [B,H,W] = {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+    B = int(image.shape[0])
+    radius, patch, color_tolerance, strength, max_change, clip_len = Engine._check_ts_params(
+        "temporal_smooth_alpha", B, radius, patch, color_tolerance, strength, max_change, clip_len)
+    dev = image.device
+    img = image.detach().float()
+    a = torch.nan_to_num(alpha.detach().float(), nan=0.0).clamp(0.0, 1.0)
+    tol = torch.tensor(color_tolerance, dtype=torch.float32, device=dev)
+    tau2 = tol * tol
+    clip = torch.arange(B, device=dev) // (clip_len if clip_len else B)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    num, den = a.clone(), torch.ones_like(a)
+    for k in range(1, min(radius, B - 1) + 1):
+        d = img[k:] - img[:-k]
+        e = (d * d).sum(-1)
+        if patch:          # the mean over the pixels of the patch that exist
+            e = F.avg_pool2d(e.unsqueeze(1), 2 * patch + 1, 1, patch, count_include_pad=False).squeeze(1)
+        u = 1.0 - (e / 3.0) / tau2
+        u = torch.where(u > 0, u, zero)
+        ck = torch.tensor(strength, dtype=torch.float32, device=dev) * (1.0 - torch.tensor(float(k), device=dev) / float(radius + 1))
+        w = torch.where((clip[k:] == clip[:-k]).view(-1, 1, 1), ck * (u * u), zero)
+        num[:-k] += w * a[k:]
+        den[:-k] += w
+        num[k:] += w * a[:-k]
+        den[k:] += w
+    limit = torch.tensor(max_change, dtype=torch.float32, device=dev)
+    return (a + torch.minimum(torch.maximum(num / den - a, -limit), limit)).clamp(0.0, 1.0)
+
+
 class SDMatteApply:
 
     @classmethod
@@ -1363,12 +1404,52 @@ class SDMatteOutline:
         return _trimap_engine(_torch_device()).outline(*args)
 
 
+class SDMatteTemporalSmooth:
+    """Frames + their alphas -> the alphas filtered along time on the GPU: the batch is a clip.  A neighbouring frame contributes to a pixel only where the
+    picture around it did not change between the two frames, so static regions stop shimmering while motion and cuts keep their own alpha.  One kernel
+    launch, no optical flow.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE", {"tooltip": "the frames of the clip, in order (the batch axis is time)"}),
+                             "alpha": ("MASK", {"tooltip": "the alpha matte of every frame"})},
+                "optional": {"radius": ("INT", {"default": 2, "min": 1, "max": 4, "tooltip": "frames on either side that may contribute"}),
+                             "patch": ("INT", {"default": 1, "min": 0, "max": 2,
+                                               "tooltip": "the picture is compared over a (2 patch + 1)^2 neighbourhood of the pixel"}),
+                             "color_tolerance": ("FLOAT", {"default": 0.1, "min": 0.001, "max": 1.0, "step": 0.005,
+                                                           "tooltip": "RMS colour change at which a neighbouring frame stops contributing"}),
+                             "strength": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.05, "tooltip": "0 returns the alpha unchanged"}),
+                             "max_change": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.01,
+                                                      "tooltip": "the most a pixel's alpha may move away from its own frame's value"}),
+                             "clip_len": ("INT", {"default": 0, "min": 0, "max": 1 << 20,
+                                                  "tooltip": "0: the batch is one clip; otherwise independent clips of this many frames"}),
+                             "force_cpu": ("BOOLEAN", {"default": False, "tooltip": "evaluate the torch restatement on the CPU instead of the GPU call"})}}
+
+    RETURN_TYPES = ("MASK", )
+    RETURN_NAMES = ("alpha", )
+    FUNCTION = "smooth"
+    CATEGORY = "Matting/SDMatte"
+
+    def smooth(self, image, alpha, radius=2, patch=1, color_tolerance=0.1, strength=1.0, max_change=1.0, clip_len=0, force_cpu=False):
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        if alpha.dim() == 2:
+            alpha = alpha.unsqueeze(0)
+        if tuple(alpha.shape) != tuple(image.shape[:3]):
+            raise ValueError(f"[SDMatte] alpha must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+        args = (image.detach().cpu(), alpha.detach().cpu(), int(radius), int(patch), float(color_tolerance), float(strength), float(max_change),
+                int(clip_len))
+        if force_cpu:      # an explicit request, never a silent substitute: the same function in torch
+            return (temporal_smooth_alpha(*args), )
+        return (_trimap_engine(_torch_device()).smooth_alpha_temporal(*args), )
+
+
 def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False, canvas: bool = False,
-                  subjects: bool = False, edge: bool = False):
+                  subjects: bool = False, edge: bool = False, video: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
     node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`, plus the subject-box node when `roi`,
     plus the canvas node when `canvas`, plus the box-per-subject node when `subjects`, plus the two
-    distance-field nodes (mask offset, outline) when `edge`."""
+    distance-field nodes (mask offset, outline) when `edge`, plus the temporal smoothing node when `video`."""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
@@ -1395,10 +1476,13 @@ def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, c
     if edge:
         classes.update({"SDMatteOffsetMask": SDMatteOffsetMask, "SDMatteOutline": SDMatteOutline})
         names.update({"SDMatteOffsetMask": "SDMatte Grow / Shrink Mask", "SDMatteOutline": "SDMatte Outline"})
+    if video:
+        classes["SDMatteTemporalSmooth"] = SDMatteTemporalSmooth
+        names["SDMatteTemporalSmooth"] = "SDMatte Temporal Smooth"
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1), like the multi-GPU fan-out
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
 NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
@@ -1407,4 +1491,5 @@ NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("
                                                                 os.environ.get("SDMATTE_ROI_NODE") == "1",
                                                                 os.environ.get("SDMATTE_CANVAS_NODE") == "1",
                                                                 os.environ.get("SDMATTE_SUBJECTS_NODE") == "1",
-                                                                os.environ.get("SDMATTE_EDGE_NODES") == "1")
+                                                                os.environ.get("SDMATTE_EDGE_NODES") == "1",
+                                                                os.environ.get("SDMATTE_VIDEO_NODE") == "1")

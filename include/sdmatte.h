@@ -451,6 +451,38 @@ int sdm_offset_mask(sdm_ctx* ctx, const float* mask_bhw, int B, int H, int W, fl
 int sdm_outline(sdm_ctx* ctx, const float* fg_bhw3, const float* alpha_bhw, int B, int H, int W, float edge_threshold, int position, float width_px,
                 float softness_px, const float* rgb3, float opacity, float* out_rgb_bhw3, float* out_alpha_bhw, int ptr_kind, void* stream);
 
+/* Steady mattes for video, on the GPU (beyond the reference): a temporal filter of the alpha guided by the frames themselves, with no optical flow.  This is
+ * the one call whose batch axis is TIME: image [B,H,W,3] is B consecutive frames.  A neighbouring frame contributes to a pixel only as far as the image
+ * around that pixel did not change between the two frames: static regions are averaged over time (the frame-to-frame shimmer of per-frame matting goes),
+ * and where something moved, or the shot changed, the weight is exactly zero and the frame keeps its own alpha.  Everything is fp32.
+ *   image fp32 [B,H,W,3] (values used as they are), alpha fp32 [B,H,W] (a = alpha with NaN -> 0, then clamped to [0,1]), out fp32 [B,H,W] in [0,1]
+ *   clips     L = clip_len, or B when clip_len == 0.  Frames [i*L, min(B, i*L + L)) form clip i; clips are independent; the last one may be shorter.
+ *   distance  for frames t and s = t + k of the same clip, k != 0, |k| <= radius: e(q) = sum over the 3 channels of (I_s(q,c) - I_t(q,c))^2;
+ *             D_k(p) = (sum of e over the pixels q within Chebyshev distance `patch` of p that exist in the frame) / (3*n), n the number of those pixels.
+ *             Pixels beyond the border do not exist, as everywhere in this header.
+ *   weight    u = 1 - D_k(p) / tau2 with tau2 = color_tolerance * color_tolerance (one fp32 product, a true fp32 division); u = u > 0 ? u : 0 (one compare,
+ *             so a NaN distance gives weight 0); g = u*u; w_k = strength * (1 - |k| / (radius + 1)) * g
+ *   filter    f = (a_t + sum_k w_k * a_s) / (1 + sum_k w_k) over the k whose frame lies in the clip (a true fp32 division; the denominator is at least 1)
+ *   limit     out = clamp(a_t + clamp(f - a_t, -max_change, +max_change), 0, 1)
+ * These hold bit for bit:
+ *   out equals a when strength == 0, or max_change == 0, or B == 1, or clip_len == 1, or every D_k >= tau2 for the pixel;
+ *   a zero weight is an exact no-op in both sums, so a sequence with a hard cut (every D >= tau2 across it) gives the bits of the two shots filtered on
+ *   their own: a cut needs no flag;
+ *   a call with clip_len = L gives the bits of one call per clip;
+ *   a frame's neighbours contribute in a fixed order (k = -1 .. -radius, then +1 .. +radius): two calls, host and device pointers, aligned and unaligned
+ *   pointers all give the same bits.
+ * sdmatte_nodes.temporal_smooth_alpha is the same function in torch (equal to fp32 rounding, not bit for bit).
+ * Limits: B, H, W >= 1 within SDM_FG_MAX_SIDE / SDM_FG_MAX_PIXELS; clip_len in 0 .. B; radius in 1 .. SDM_TS_MAX_RADIUS; patch in 0 .. SDM_TS_MAX_PATCH;
+ * color_tolerance finite in [1/1024, 1]; strength finite in [0, 1]; max_change finite in [0, 1]: SDM_ERR_INVALID otherwise, with a message that names the
+ * argument, and then nothing is queued or written.  Stream contract and pointer kinds as sdm_make_trimap; sdm_last_forward_ms covers the launch.  Needs
+ * no weights.  ONE kernel launch (csrc/k_temporal.h), `ts_smooth` in sdm_kernel_counts and the per-launch profile, whatever the arguments and the content;
+ * every frame is read once per tile (about 20 bytes per pixel and frame), no host readback.  The call keeps nothing in the arena; host pointers go
+ * through the I/O staging (sdm_resident_bytes counts it, sdm_release_memory frees it). */
+#define SDM_TS_MAX_RADIUS 4
+#define SDM_TS_MAX_PATCH 2
+int sdm_smooth_alpha_temporal(sdm_ctx* ctx, const float* image_bhwc, const float* alpha_bhw, int B, int H, int W, int clip_len, int radius, int patch,
+                              float color_tolerance, float strength, float max_change, float* out_bhw, int ptr_kind, void* stream);
+
 /* Memory the engine holds outside any framework allocator: packed weights + activation arena (sized by the largest batch /
  * resolution seen) + I/O staging.  sdm_release_memory frees everything but the weights (the next forward re-allocates). */
 int64_t sdm_resident_bytes(sdm_ctx* ctx);
@@ -476,7 +508,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas: their launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
