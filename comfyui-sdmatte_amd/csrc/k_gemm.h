@@ -100,6 +100,9 @@ struct GemmP3Params {
   // (the GEMM's K is 4 * Cin), w = four W3 matrices [4 * Cin][N], one per phase 2 * py + px; out = fp32 NHWC [N][2 up_H][2 up_W][ldo];
   // stats: [imgs][tiles_per_img * 8][ldo][2], partial row (M tile, phase, wave row)
   int up_H, up_W;
+  // PT = 1 (EPI 0 / 4, rows_per_img = H * pt_W): the GEMM's rows are the tokens of a transformer in patch order (sdm_common.h), `out` and `res` are pixel-order
+  // rows [imgs][H][pt_W][..]: row token -> pixel row of the same image, for the store and for the residual load
+  int pt_W;
 };
 
 // 16 fp32 values of a 32-row x 32-channel accumulator block (register r = channel (r&3) + 8*(r>>2) + 4*(lane>>5) of row lane&31)
@@ -135,7 +138,7 @@ SDM_DEV_INLINE void p3_pack_block(const float (&v)[16], u32x4 (&hi)[2], u32x4& x
 
 // NS = LDS stages (ring): the DMAs of chunk c + NS - 1 are issued when chunk c starts - NS - 1 chunks of landing time.  2 stages of the 256 x 128 tile
 // leave room for two blocks per CU; deeper rings trade the second block for landing time (one block per CU from 3 stages of the 256-row tile).
-template <int MT, int NT, int EPI, int NS = 2, int UP = 0>
+template <int MT, int NT, int EPI, int NS = 2, int UP = 0, int PT = 0>
 __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 128) <= 80 * 1024) ? 2 : 1) gemm_p3_kernel(GemmP3Params p) {
   constexpr int BM = 2 * MT * 32, BN = 2 * NT * 32;
   constexpr int A_HI = BM * 64, A_XL = BM * 32, B_HI = BN * 64, B_F8 = BN * 64;
@@ -145,6 +148,7 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
   static_assert(EPI != 1 || NT == 2, "GEGLU: a wave's 64 columns are one [u32 | g32] group");
   static_assert(NS >= 2 && NS * STAGE <= 160 * 1024 && (NS - 2) * PER <= 63, "LDS ring / vmcnt range");
   static_assert(!UP || EPI == 0 || EPI == 4, "up-sampling phase convs store fp32 rows");
+  static_assert(!PT || ((EPI == 0 || EPI == 4) && !UP), "the token -> pixel row map belongs to the fp32 epilogues");
   SDM_DYN_SMEM(smem);
   const int tx = (int)threadIdx.x, lane = tx & 63, wave = SDM_UNIFORM_I(tx >> 6);
   const int wm = wave >> 1, wn = wave & 1, h = lane >> 5, l31 = lane & 31;
@@ -284,10 +288,21 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
   const long m0 = tile_rows(mt_c, img, mti, m_end);
   const int n0 = nt_col0(nt_c), phase = nt_phase(nt_c);
   const unsigned int rows_left = (unsigned int)((m_end - m0) < (long)BM ? (m_end - m0) : (long)BM);
+  // PT: the tile's tokens q0 .. q0 + rows_left - 1 of image img (q0 % 64 == 0: whole patches) lie in the patch rows pr0 .. pr1; the descriptors of the
+  // output and of the residual span the pixel rows 8 pr0 .. 8 pr1 + 7 of that image and nothing else (the launcher keeps that below SDM_BUF_INVALID), and
+  // pt_row(row) = the token's pixel row behind the first of them, SDM_BUF_INVALID-to-be (~0u) for rows beyond the tile's end
+  const unsigned int pt_q0 = PT ? (unsigned int)(m0 - (long)img * p.rows_per_img) : 0u, pt_pw = PT ? (unsigned int)p.pt_W >> 3 : 1u;
+  const unsigned int pt_pr0 = PT ? (pt_q0 >> 6) / pt_pw : 0u, pt_pr1 = PT ? ((pt_q0 + rows_left - 1u) >> 6) / pt_pw : 0u;
+  const size_t pt_first = PT ? (size_t)img * p.rows_per_img + (size_t)pt_pr0 * 8u * (unsigned int)p.pt_W : 0;      // first pixel row of the span
+  const unsigned int pt_span = PT ? (pt_pr1 - pt_pr0 + 1u) * 8u * (unsigned int)p.pt_W : 0u;                       // pixel rows in the span
+  auto pt_row = [&](unsigned int row) -> unsigned int {
+    return row < rows_left ? sdm_patch_pixel_of_token(pt_q0 + row, (unsigned int)p.pt_W) - pt_pr0 * 8u * (unsigned int)p.pt_W : ~0u;
+  };
   // the accumulators start from the fp32 residual (register quad = four consecutive channels of a row = one 16-byte load; rows / channels beyond the end
   // read 0): the loads fly while the tile's first chunk lands, and no epilogue waits for memory
   if ((EPI == 0 || EPI == 3 || EPI == 4) && p.res) {
-    const sdm_rsrc rs_res = sdm_make_rsrc(p.res + (size_t)m0 * p.ldr, rows_left * (unsigned int)p.ldr * 4u);
+    const sdm_rsrc rs_res = PT ? sdm_make_rsrc(p.res + pt_first * p.ldr, pt_span * (unsigned int)p.ldr * 4u)
+                               : sdm_make_rsrc(p.res + (size_t)m0 * p.ldr, rows_left * (unsigned int)p.ldr * 4u);
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -295,8 +310,8 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int ch = n0 + (wn * NT + j) * 32 + 8 * g + 4 * h;
-          const unsigned int row = (unsigned int)((wm * MT + i) * 32 + l31);
-          const f32x4 r4 = __builtin_bit_cast(f32x4, sdm_buffer_load16(rs_res, ch < p.n_valid ? row * (unsigned int)p.ldr * 4u + (unsigned int)ch * 4u : SDM_BUF_INVALID, 0));
+          const unsigned int row_t = (unsigned int)((wm * MT + i) * 32 + l31), row = PT ? pt_row(row_t) : row_t;
+          const f32x4 r4 = __builtin_bit_cast(f32x4, sdm_buffer_load16(rs_res, (ch < p.n_valid && (!PT || row != ~0u)) ? row * (unsigned int)p.ldr * 4u + (unsigned int)ch * 4u : SDM_BUF_INVALID, 0));
 #pragma unroll
           for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = r4[e];
         }
@@ -406,6 +421,15 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
         ro[i] = inside ? (((2u * (yp - yb) + (unsigned int)py) * 2u * (unsigned int)p.up_W + 2u * (xp - 1u) + (unsigned int)px) * (unsigned int)p.ldo) * 4u : SDM_BUF_INVALID;
       }
     }
+    if (PT) {      // the same scatter by the token -> pixel map
+      obase = (const float*)p.out + pt_first * p.ldo;
+      obytes = (size_t)pt_span * (unsigned int)p.ldo * 4u;
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const unsigned int pr = pt_row((unsigned int)((wm * MT + i) * 32 + l31));
+        ro[i] = pr != ~0u ? pr * (unsigned int)p.ldo * 4u : SDM_BUF_INVALID;
+      }
+    }
     const sdm_rsrc rs_out = sdm_make_rsrc(obase, (unsigned int)obytes);
     constexpr bool do_stats = (EPI == 4);
     // channel quad by channel quad, the MT row blocks of a quad back to back: a quad's statistics (per channel over this wave's MT * 32 rows) are complete
@@ -422,9 +446,9 @@ __global__ void __launch_bounds__(256, (NS * (2 * MT * 32 * 96 + 2 * NT * 32 * 1
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * g + e] + bq[j][g][e];
-        const bool live = UP ? ro[i] != SDM_BUF_INVALID : row < rows_left;
-        const unsigned int rbyte = UP ? ro[i] : row * (unsigned int)p.ldo * 4u;
-        sdm_buffer_store16(__builtin_bit_cast(u32x4, v), rs_out, (ch < p.n_valid && (!UP || live)) ? rbyte + (unsigned int)ch * 4u : SDM_BUF_INVALID, 0);
+        const bool live = (UP || PT) ? ro[i] != SDM_BUF_INVALID : row < rows_left;
+        const unsigned int rbyte = (UP || PT) ? ro[i] : row * (unsigned int)p.ldo * 4u;
+        sdm_buffer_store16(__builtin_bit_cast(u32x4, v), rs_out, (ch < p.n_valid && (!(UP || PT) || live)) ? rbyte + (unsigned int)ch * 4u : SDM_BUF_INVALID, 0);
         if (do_stats && live) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) { t1[e] += v[e]; t2[e] += v[e] * v[e]; }

@@ -102,15 +102,17 @@ __global__ void prep_nchw_kernel(const float* __restrict__ img, const float* __r
 // bias[level][b][i*wk + j] = (1 - (t[b][8*s*i][8*s*j] + 1)/2) * mask_value * log2e, s = 2^level, (hk, wk) = (SH/8, SW/8) >> level.
 // The reference only admits square latents (replace.py:57-60 asserts perfect squares); the stride-2^k pick is the same rule
 // on a rectangle.
+// patch_tokens != 0: key (ii, j) is written at its patch-order token (sdm_common.h) - the order in which the level's transformers number their tokens.
 __global__ void mask_bias_kernel(const float* __restrict__ plane, float* __restrict__ bias, int B, int SH, int SW, int level, float mask_value,
-                                 float mult) {
+                                 float mult, int patch_tokens) {
   const int hk = (SH / 8) >> level, wk = (SW / 8) >> level, s = 1 << level;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)B * hk * wk) return;
   const int j = i % wk, ii = (i / wk) % hk, b = i / ((long)hk * wk);
   const float t = plane[((size_t)b * SH + (size_t)8 * s * ii) * SW + 8 * s * j];
   const float m = (t + 1.0f) / 2.0f;
-  bias[i] = ((1.0f - m) * mask_value) * mult;
+  const long o = patch_tokens ? (long)b * hk * wk + (long)sdm_patch_token_of_pixel((unsigned int)ii, (unsigned int)j, (unsigned int)wk) : i;
+  bias[o] = ((1.0f - m) * mask_value) * mult;
 }
 
 // decoded fp32 [B,S,S,4] (3 real channels) -> alpha fp32 [B,S,S] = (clip(mean3,-1,1)+1)/2

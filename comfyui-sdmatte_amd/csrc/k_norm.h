@@ -201,19 +201,22 @@ __global__ void __launch_bounds__(512) gn_apply_kernel(GnSrc s, const float* __r
 // A block = 16 consecutive rows (one row block of the HI plane); thread (r = tid & 15, u = tid >> 4) walks the 8-channel runs v = u, u + 16, ...: a wave
 // reads 16 rows x 128 bytes (whole lines) and writes one whole 1 KB block of the HI plane plus two 256-byte runs of the XL plane per step.
 __global__ void __launch_bounds__(256) gn_apply_p3_kernel(GnSrc s, const float* __restrict__ scale, const float* __restrict__ shift, unsigned char* __restrict__ out,
-                                                          int silu, long rows_total) {
+                                                          int silu, long rows_total, int pt_W) {
   const int C = s.C0 + s.C1, nv = C / 8;
   const int tid = threadIdx.x;
   const long row = (long)blockIdx.x * 16 + (tid & 15);
   if (row >= rows_total) return;
   const long n = row / s.HW;
+  // pt_W != 0 (patch token order, sdm_common.h; the image is pt_W pixels wide): output row = token, so the 16 rows of a block - two 8-pixel runs of a patch -
+  // still fill whole blocks of the planes; the pixel it reads is the token's
+  const long src_row = pt_W ? n * s.HW + (long)sdm_patch_pixel_of_token((unsigned int)(row - n * s.HW), (unsigned int)pt_W) : row;
   unsigned char* xl = out + p3_rows_pad((size_t)rows_total) * (size_t)C * 2;
   for (int v = tid >> 4; v < nv; v += 16) {
     const int c = v * 8;
     const void* src = s.in0; int Cs = s.C0, cc = c;
     if (c >= s.C0) { src = s.in1; Cs = s.C1; cc = c - s.C0; }
     float x8[8], y[8];
-    sdm_load8_as_f32(src, (size_t)row * Cs + cc, s.in_f32, x8);
+    sdm_load8_as_f32(src, (size_t)src_row * Cs + cc, s.in_f32, x8);
     const f32x4 a0 = *(const f32x4*)(scale + (size_t)n * C + c), a1 = *(const f32x4*)(scale + (size_t)n * C + c + 4);
     const f32x4 b0 = *(const f32x4*)(shift + (size_t)n * C + c), b1 = *(const f32x4*)(shift + (size_t)n * C + c + 4);
 #pragma unroll

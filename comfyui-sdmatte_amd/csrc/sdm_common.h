@@ -297,3 +297,18 @@ SDM_DEV_INLINE void sdm_load8_as_f32(const void* base, size_t elem_index, int is
 }
 
 static inline int sdm_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// ---- patch token order of the U-Net transformers: inside a Transformer2DModel 64 consecutive tokens are an 8 x 8 patch of the H x W
+//      latent, so that a 64-key tile of the self-attention covers a square and not a 1 x 64 strip - the tiles the trimap bias lets the kernels skip follow
+//      the foreground's shape.  Only GroupNorm-apply in front of proj_in (pixel -> token) and the proj_out epilogue (token -> pixel) know the order. ----
+// the rule: whole patches, and a strip that is no better than a patch already (W < 64: a 64-key strip spans two or more rows)
+SDM_HD_INLINE bool sdm_patch_tokens_ok(int H, int W) { return H > 0 && W >= 64 && (H & 7) == 0 && (W & 7) == 0; }
+// pixel (y, x) of an image -> its token inside the image
+SDM_HD_INLINE unsigned int sdm_patch_token_of_pixel(unsigned int y, unsigned int x, unsigned int W) {
+  return (((y >> 3) * (W >> 3) + (x >> 3)) << 6) + ((y & 7u) << 3) + (x & 7u);
+}
+// token t inside an image -> its row-major pixel index y * W + x
+SDM_HD_INLINE unsigned int sdm_patch_pixel_of_token(unsigned int t, unsigned int W) {
+  const unsigned int pw = W >> 3, pi = t >> 6, pr = pi / pw, pc = pi - pr * pw;
+  return ((pr << 3) + ((t >> 3) & 7u)) * W + (pc << 3) + (t & 7u);
+}

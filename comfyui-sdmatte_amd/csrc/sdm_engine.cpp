@@ -135,9 +135,10 @@ static OptEntry g_opts[] = {
   {"attn_pp", 1, 1, "split-precision d=64 attention with fp32 output as a ping-pong of the block's wave halves (attn_d64_pp_kernel, 256 query rows per block): 0 off, 1 on, 2 on without the static priority of the younger half, 3 on with per-segment priority flips"},
   {"attn_pp_min_blocks", 128, 128, "attn_pp: launches with fewer 256-row blocks than this keep the 4-wave pipelines (0 in tests: the ping-pong kernel at any size)"},
   {"attn_ksplit", 0, 0, "key split of the d=64 split-precision attention: 0 by launch size (blocks that do not fill the chip's block slots a whole number of times), 1 off, 2 / 4 forced, 3 forced on the ping-pong kernel (ignored elsewhere: those launches run unsplit)"},
-  {"attn512_pp", 0, 0, "d=512 attention (VAE mid-block): the ping-pong kernel (the block's two wave halves one phase apart, attn_d512_pp_kernel; bit-identical): 1 with s_setprio 1 for waves 4-7, 2 without (A/B), 0 = attn_d512_kernel.  Off until its step time has been measured against attn_d512_kernel (profiles/NOTES.md)"},
+  {"attn512_pp", 0, 0, "d=512 attention (VAE mid-block): the ping-pong kernel (the block's two wave halves one phase apart, attn_d512_pp_kernel; bit-identical): 1 with s_setprio 1 for waves 4-7, 2 without (A/B), 0 = attn_d512_kernel.  Off: measured at 4 x 1024^2 it gains 0.08 ms per step, inside the run-to-run spread (profiles/r09_patch_tokens_ab.txt)"},
   {"cross_narrow", 1, 1, "cross_shared: the narrow form of the d = 64 cores on the shared operand (36 live columns: no Q.K^T step over columns 48..63, the softmax denominator from a row of ones in V^T instead of its own MFMAs; bit-identical).  0 = the full d = 64 program on an operand without the ones rows.  Read per forward"},
   {"cross_shared", 1, 1, "cross-attention on ONE key / value operand per forward, the patch matrix of the trimap latent (cross_patch_planes_kernel), with the K|V fold moved into q_shared / out_shared: 0 = every block's own kv_folded conv + transpose.  Read per forward"},
+  {"attn_patch_tokens", 1, 1, "token order inside the U-Net transformers of a level whose latent is whole 8x8 patches and at least 64 wide (sdm_patch_tokens_ok): 64 consecutive tokens = an 8x8 patch, so the key tiles the trimap bias skips follow the foreground's shape (GroupNorm-apply in front of proj_in, the proj_out epilogue and the level's key bias carry the map).  0 = row-major pixel order everywhere.  Read per forward"},
   {"precise_mask", -1, -1, "stages in split precision (-1 = the config's own mask; per-stage attribution experiments; read at sdm_create)"},
 #ifdef SDM_EMU
   {"emu_arena_extra", 0, 0, "emulator build only, self-test of the arena check: the launch pass of a stand-alone op allocates one block its sizing pass did not"},
@@ -404,7 +405,7 @@ static void launch_gemm_f8(const ConvParams& p_in, void* stream) {
 }
 
 // ---- plane-fed GEMM (k_gemm.h): tile = (64 * MT) rows x 128 channels, 4 waves; NS LDS stages (2 stages of the 256-row tile: two blocks per CU) ----
-template <int MT, int EPI, int UP = 0>
+template <int MT, int EPI, int UP = 0, int PT = 0>
 static void launch_gemm_p3_t(GemmP3Params p, void* stream) {
   constexpr int BM = 64 * MT, NS = 2, SMEM = NS * (BM * 96 + 128 * 128);
   const long rows = p.rows_per_img ? (long)p.rows_per_img : p.M;
@@ -420,7 +421,7 @@ static void launch_gemm_p3_t(GemmP3Params p, void* stream) {
     const unsigned slots = pp > 1 ? (unsigned)pp : ((unsigned)(device_cus() * ((SMEM <= 80 * 1024) ? 2 : 1)) & ~7u);      // (pp > 1: forced grid, tests)
     if (slots >= 1 && grid > slots) grid = slots;
   }
-  auto k = gemm_p3_kernel<MT, 2, EPI, NS, UP>;
+  auto k = gemm_p3_kernel<MT, 2, EPI, NS, UP, PT>;
   SDM_SET_SMEM(k, SMEM);
 #ifndef SDM_EMU
   if (opt("gemm_p3_ablate") & 256) {      // lab: resident blocks per CU as the runtime sees them
@@ -447,8 +448,20 @@ static int gemm_p3_pick_bm(long M, int N, int rows_per_img, int phases = 1) {
   for (int bm : {256, 128}) if (imgs * ((rows + bm - 1) / bm) * tn >= cus) return bm;
   return 64;
 }
+// proj_out of a transformer in patch token order (GemmP3Params::pt_W): its own instantiations of epilogues 0 / 4, so that every other launch keeps its code
+template <int EPI>
+static void launch_gemm_p3_tokens(const GemmP3Params& p, int bm, void* stream) {
+  if (bm == 256) launch_gemm_p3_t<4, EPI, 0, 1>(p, stream);
+  else if (bm == 128) launch_gemm_p3_t<2, EPI, 0, 1>(p, stream);
+  else launch_gemm_p3_t<1, EPI, 0, 1>(p, stream);
+}
 static void launch_gemm_p3(const GemmP3Params& p, int epi, void* stream) {
   const int bm = gemm_p3_pick_bm(p.M, p.N, p.rows_per_img);
+  if (p.pt_W) {
+    count_kernel("gemm_p3_tokens");
+    if (epi == 4) launch_gemm_p3_tokens<4>(p, bm, stream); else launch_gemm_p3_tokens<0>(p, bm, stream);
+    return;
+  }
   switch (epi) {
     case 0: launch_gemm_p3_e<0>(p, bm, stream); break;
     case 1: launch_gemm_p3_e<1>(p, bm, stream); break;
@@ -1467,9 +1480,11 @@ static int gn_scale_shift(sdm_ctx* e, const void* in0, const void* in1, int C0, 
 
 static int op_groupnorm_raw(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1, int in_f32, int N, int HW, int groups,
                             const float* gamma, const float* beta, float eps, int silu, void* out, int out_f32, const float* st0 = nullptr,
-                            int rows0 = 0, const float* st1 = nullptr, int rows1 = 0, bool have_stats = false) {
+                            int rows0 = 0, const float* st1 = nullptr, int rows1 = 0, bool have_stats = false, int pt_W = 0) {
   const int C = C0 + C1;
   T scratch; float* scale; float* shift;
+  // pt_W: width of the image whose P3 rows are written in patch token order (sdm_common.h), 0 = row-major
+  if (pt_W && (out_f32 != kFmtP3 || HW % pt_W || !sdm_patch_tokens_ok(HW / pt_W, pt_W))) SDM_FAIL(e, SDM_ERR_INVALID, "groupnorm: patch token order needs P3 output and whole 8x8 patches");
   TRY(gn_scale_shift(e, in0, in1, C0, C1, in_f32, N, HW, groups, gamma, beta, eps, st0, rows0, st1, rows1, have_stats, &scratch, &scale, &shift));
   if (!e->dry) {
     GnSrc s; s.in0 = in0; s.in1 = in1; s.C0 = C0; s.C1 = C1; s.in_f32 = in_f32; s.HW = HW;
@@ -1477,7 +1492,7 @@ static int op_groupnorm_raw(sdm_ctx* e, const void* in0, const void* in1, int C0
     prof_begin(e, "gn_apply", 0, (double)N * HW * C * (in_f32 ? 4 : 2) + (double)N * HW * C * (double)fmt_bytes(out_f32));
     if (out_f32 == kFmtP3)
       SDM_LAUNCH(gn_apply_p3_kernel, dim3((unsigned)(((long)N * HW + 15) / 16)), dim3(256), 0, e->stream, s, (const float*)scale, (const float*)shift, (unsigned char*)out,
-                 silu, (long)N * HW);
+                 silu, (long)N * HW, pt_W);
     else
     SDM_LAUNCH(gn_apply_kernel, dim3(g.nb, N), dim3(g.threads), 0, e->stream, s, (const float*)scale, (const float*)shift, out, out_f32, silu, g.ppb);
     prof_end(e);
@@ -1486,13 +1501,13 @@ static int op_groupnorm_raw(sdm_ctx* e, const void* in0, const void* in1, int C0
   return 0;
 }
 
-static int op_gn(sdm_ctx* e, const NormL& n, const T& x, const T* x2, int silu, float eps, T* out, int out_fmt = -1) {
+static int op_gn(sdm_ctx* e, const NormL& n, const T& x, const T* x2, int silu, float eps, T* out, int out_fmt = -1, bool patch_tokens = false) {
   const int C = x.C + (x2 ? x2->C : 0);
   if (C != n.C) SDM_FAIL(e, SDM_ERR_INVALID, "groupnorm: C %d != %d", C, n.C);
   *out = talloc(e, x.N, x.H, x.W, C, out_fmt >= 0 ? out_fmt : e->act_f32);
   const bool hs = x.sbytes && (!x2 || x2->sbytes);     // statistics already produced by the conv epilogue(s)
   return op_groupnorm_raw(e, x.p, x2 ? x2->p : nullptr, x.C, x2 ? x2->C : 0, x.f32, x.N, x.H * x.W, e->cfg.groups, n.g, n.b, eps, silu,
-                          out->p, out->f32, x.stats, x.srows, x2 ? x2->stats : nullptr, x2 ? x2->srows : 0, hs);
+                          out->p, out->f32, x.stats, x.srows, x2 ? x2->stats : nullptr, x2 ? x2->srows : 0, hs, patch_tokens ? x.W : 0);
 }
 
 static int op_ln(sdm_ctx* e, const NormL& n, const T& x, float eps, T* out, int out_fmt = -1) {
@@ -1829,7 +1844,8 @@ static int resblock(sdm_ctx* e, const ResB& r, const T& x, const T* x2, float ep
 // ---- plane-fed GEMM path (k_gemm.h).  `in` is a P3 tensor (T::f32 == kFmtP3); the output format picks the epilogue: fp32 (+residual, +statistics),
 //      P3 (GEGLU layers, or linear + residual), or the q | k | v operand planes of the attention cores (format 3) ----
 static bool p3_ok(sdm_ctx* e, const ConvL& L) { return L.w3 != nullptr && e->act_f32 && opt("gemm_p3") != 0; }
-static int op_gemm_p3(sdm_ctx* e, const ConvL& L, const T& in, T* out, const T* res, int lo_cols) {
+// patch_tokens: `in` holds the rows of its images in patch token order (sdm_common.h), `out` and `res` are pixel-order NHWC (epilogues 0 / 4 only)
+static int op_gemm_p3(sdm_ctx* e, const ConvL& L, const T& in, T* out, const T* res, int lo_cols, bool patch_tokens = false) {
   if (in.f32 != kFmtP3 || in.C != L.Cin_pad) SDM_FAIL(e, SDM_ERR_INVALID, "gemm %s: needs a P3 operand of %d channels", L.name.c_str(), L.Cin_pad);
   if (!L.w3) SDM_FAIL(e, SDM_ERR_STATE, "gemm %s: no W3 weight copy", L.name.c_str());
   if (res && res->f32 != 1) SDM_FAIL(e, SDM_ERR_INVALID, "gemm %s: fp32 residual expected", L.name.c_str());
@@ -1861,12 +1877,20 @@ static int op_gemm_p3(sdm_ctx* e, const ConvL& L, const T& in, T* out, const T* 
     out->soff = sb.off; out->sbytes = sb.bytes; out->stats = (float*)sb.p;
     p.stats = out->stats;
   }
+  if (patch_tokens) {
+    if ((epi != 0 && epi != 4) || !sdm_patch_tokens_ok(in.H, in.W)) SDM_FAIL(e, SDM_ERR_INVALID, "gemm %s: patch token order needs an fp32 output and whole 8x8 patches", L.name.c_str());
+    p.rows_per_img = in.H * in.W; p.pt_W = in.W;
+    // a tile's descriptors span the pixel rows of the patch rows it touches (k_gemm.h): at most ceil(4 / (W / 8)) + 1 of them with the 256-row tile
+    const double span = (double)(sdm_cdiv(4, in.W / 8) + 1) * 8.0 * in.W * std::max(p.ldo, p.ldr) * 4.0;
+    if (span >= (double)SDM_BUF_INVALID) SDM_FAIL(e, SDM_ERR_INVALID, "gemm %s: a tile's pixel rows exceed the buffer descriptor range", L.name.c_str());
+  }
   if (e->dry) return 0;
   const double flops = 2.0 * (double)p.M * L.O * L.I;
   const double bytes = (double)p.M * p.K * 3 + (double)p.M * p.n_valid * (double)fmt_bytes(out->f32) + (double)p.K * p.N * 4 + (res ? (double)p.M * p.n_valid * 4 : 0.0);
   if (e->prof_on) {
     char d[256];
-    snprintf(d, sizeof(d), "%s N=%d Hout=%d Wout=%d Cin=%d Cout=%d p3 epi=%d bm=%d", L.name.c_str(), in.N, in.H, in.W, L.Cin_pad, L.O, epi, gemm_p3_pick_bm(p.M, p.N, p.rows_per_img));
+    snprintf(d, sizeof(d), "%s N=%d Hout=%d Wout=%d Cin=%d Cout=%d p3 epi=%d bm=%d%s", L.name.c_str(), in.N, in.H, in.W, L.Cin_pad, L.O, epi, gemm_p3_pick_bm(p.M, p.N, p.rows_per_img),
+             patch_tokens ? " patch_tokens" : "");
     prof_begin(e, "gemm_mfma", flops, bytes, d);
   } else {
     prof_begin(e, "conv", flops, bytes);
@@ -1892,10 +1916,12 @@ static int op_to_p3(sdm_ctx* e, const T& x, T* out) {
   return 0;
 }
 
-static int linear(sdm_ctx* e, int layer, const T& in, T* out, int Cout, int out_f32, const T* res = nullptr, bool want_stats = false, int lo_cols = -1) {
+static int linear(sdm_ctx* e, int layer, const T& in, T* out, int Cout, int out_f32, const T* res = nullptr, bool want_stats = false, int lo_cols = -1,
+                  bool patch_tokens = false) {
   *out = talloc(e, in.N, in.H, in.W, Cout, out_f32);
   if (want_stats) TRY(tstats(e, *out));
-  if (in.f32 == kFmtP3) return op_gemm_p3(e, e->convs[layer], in, out, res, lo_cols);
+  if (in.f32 == kFmtP3) return op_gemm_p3(e, e->convs[layer], in, out, res, lo_cols, patch_tokens);
+  if (patch_tokens) SDM_FAIL(e, SDM_ERR_STATE, "linear %s: patch token order without the plane-fed GEMM", e->convs[layer].name.c_str());
   ConvArgs a; a.in0 = &in; a.out = out; a.res = res; a.lo_cols = lo_cols;
   return op_conv(e, e->convs[layer], a);
 }
@@ -2009,7 +2035,10 @@ static int cross_attention(sdm_ctx* e, const TfB& t, T& n, const T& uin, const C
   return 0;
 }
 
-static int transformer(sdm_ctx* e, const TfB& t, const T& x, const T& uin, const CrossPlanes& cp, bool masked, const float* bias, const int* tiles, T* out) {
+// patch_tokens: the block's tokens are numbered in patch order (sdm_common.h) between the GroupNorm in front of proj_in and the proj_out epilogue, and `bias` /
+// `tiles` come in that order; everything in between is order-free (LayerNorm, the Linears, the softmax over keys, the shared cross-attention operand)
+static int transformer(sdm_ctx* e, const TfB& t, const T& x, const T& uin, const CrossPlanes& cp, bool masked, const float* bias, const int* tiles, bool patch_tokens,
+                       T* out) {
   const int sf = e->cfg.stream_f32;
   const int C = t.C, L = x.H * x.W;
   T hn, h, n, qkv, ao, h2, f;
@@ -2029,7 +2058,8 @@ static int transformer(sdm_ctx* e, const TfB& t, const T& x, const T& uin, const
     a = ap;
     return 0;
   };
-  TRY(op_gn(e, e->norms[t.gn], x, nullptr, 0, e->cfg.unet_tf_gn_eps, &hn, nf));
+  if (patch_tokens && !(p3 && sdm_patch_tokens_ok(x.H, x.W))) SDM_FAIL(e, SDM_ERR_STATE, "transformer: patch token order without the plane-fed GEMMs");
+  TRY(op_gn(e, e->norms[t.gn], x, nullptr, 0, e->cfg.unet_tf_gn_eps, &hn, nf, patch_tokens));
   TRY(linear(e, t.proj_in, hn, &h, C, sf));
   tfree(e, hn);
   // self-attention with the trimap key bias
@@ -2058,7 +2088,7 @@ static int transformer(sdm_ctx* e, const TfB& t, const T& x, const T& uin, const
   // (P3: h2 only feeds proj_out - whose fused statistics need image-aligned row tiles on whole 32-row blocks; otherwise proj_out keeps the fp32 kernel)
   TRY(linear(e, t.ff2, f, &h2, C, (p3 && L % 32 == 0) ? kFmtP3 : sf, &h));
   tfree(e, f); tfree(e, h);
-  TRY(linear(e, t.proj_out, h2, out, C, sf, &x, true));
+  TRY(linear(e, t.proj_out, h2, out, C, sf, &x, true, -1, patch_tokens));
   tfree(e, h2);
   return 0;
 }
@@ -2255,7 +2285,19 @@ static int vae_decode(sdm_ctx* e, const T& z, T* dec) {
   return 0;
 }
 
-static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bias_lvl, int* const* tiles_lvl, T* out) {
+// Does U-Net level k (latent H x W) run its transformers in patch token order?  The option, the rule of the shape, and every transformer of the level on the
+// plane-fed GEMMs (the two kernels that carry the map).  Decided once per forward in run_model, for the level's key bias and its transformers alike.
+static bool level_patch_tokens(sdm_ctx* e, int k, int H, int W, bool option_on) {
+  if (!option_on || !sdm_patch_tokens_ok(H, W)) return false;
+  const int pf = unet_attn_plane_fmt(e);
+  bool ok = true;
+  if (k < 3) for (auto& t : e->u_down_tf[k]) ok = ok && transformer_p3(e, t, pf);
+  if (k == 3) ok = ok && transformer_p3(e, e->u_midtf, pf);
+  if (k < 3) for (auto& t : e->u_up_tf[3 - k]) ok = ok && transformer_p3(e, t, pf);
+  return ok;
+}
+
+static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bias_lvl, int* const* tiles_lvl, const bool* patch_lvl, T* out) {
   const sdm_config& c = e->cfg;
   const float eps = c.unet_res_eps;
   const int sf = c.stream_f32;
@@ -2270,7 +2312,7 @@ static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bia
       TRY(resblock(e, e->u_down_res[i][j], h, nullptr, eps, &t));
       if (i < 3) {
         T t2;
-        TRY(transformer(e, e->u_down_tf[i][j], t, uin, cp, masked, bias_lvl[i], tiles_lvl[i], &t2));
+        TRY(transformer(e, e->u_down_tf[i][j], t, uin, cp, masked, bias_lvl[i], tiles_lvl[i], patch_lvl[i], &t2));
         tfree(e, t); t = t2;
       }
       h = t;                       // previous h stays alive as a skip
@@ -2284,7 +2326,7 @@ static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bia
   }
   // mid (h aliases the last skip: do not free it here)
   TRY(resblock(e, e->u_mid0, h, nullptr, eps, &t)); h = t;
-  TRY(transformer(e, e->u_midtf, h, uin, cp, masked, bias_lvl[3], tiles_lvl[3], &t)); tfree(e, h); h = t;
+  TRY(transformer(e, e->u_midtf, h, uin, cp, masked, bias_lvl[3], tiles_lvl[3], patch_lvl[3], &t)); tfree(e, h); h = t;
   TRY(resblock(e, e->u_mid1, h, nullptr, eps, &t)); tfree(e, h); h = t;
   for (int i = 0; i < 4; ++i) {
     for (size_t j = 0; j < e->u_up_res[i].size(); ++j) {
@@ -2292,7 +2334,7 @@ static int unet_forward(sdm_ctx* e, const T& uin, bool masked, float* const* bia
       TRY(resblock(e, e->u_up_res[i][j], h, &s, eps, &t));   // cat([h, skip], dim=1) then ResBlock (replace.py:509-536)
       tfree(e, h); tfree(e, s); h = t;
       if (i > 0) {
-        TRY(transformer(e, e->u_up_tf[i][j], h, uin, cp, masked, bias_lvl[3 - i], tiles_lvl[3 - i], &t));
+        TRY(transformer(e, e->u_up_tf[i][j], h, uin, cp, masked, bias_lvl[3 - i], tiles_lvl[3 - i], patch_lvl[3 - i], &t));
         tfree(e, h); h = t;
       }
     }
@@ -2313,15 +2355,18 @@ static int run_model(sdm_ctx* e, const T& x16, const T& plane, int B, int SH, in
   T biasbuf[4], tilebuf[4];
   float* bias_lvl[4];
   int* tiles_lvl[4];            // per level: the key tiles that can contribute to the softmax (AttnParams::tiles), built once per forward
+  bool patch_lvl[4];            // per level: tokens in patch order (the bias is written in the order the level's transformers number their tokens)
+  const bool patch_opt = opt("attn_patch_tokens") != 0;
   for (int k = 0; k < 4; ++k) {
     const int lk2 = (lh >> k) * (lw >> k), nt = sdm_cdiv(lk2, 64);
+    patch_lvl[k] = level_patch_tokens(e, k, lh >> k, lw >> k, patch_opt);
     biasbuf[k] = talloc(e, B, 1, 1, lk2, 1);
     tilebuf[k] = talloc(e, B, 1, 1, nt + 1, 1);
     bias_lvl[k] = (float*)biasbuf[k].p;
     tiles_lvl[k] = (int*)tilebuf[k].p;
     if (!e->dry && use_mask) {
       SDM_LAUNCH(mask_bias_kernel, dim3(sdm_cdiv(B * lk2, 256)), dim3(256), 0, e->stream, (const float*)plane.p, bias_lvl[k], B, SH, SW, k,
-                 c.attn_mask_value, SDM_LOG2E);
+                 c.attn_mask_value, SDM_LOG2E, patch_lvl[k] ? 1 : 0);
       SDM_LAUNCH(attn_active_tiles_kernel, dim3(B), dim3(256), 0, e->stream, (const float*)bias_lvl[k], lk2, nt, tiles_lvl[k], nt + 1,
                  SDM_ATTN_SKIP_MARGIN);
     }
@@ -2345,7 +2390,7 @@ static int run_model(sdm_ctx* e, const T& x16, const T& plane, int B, int SH, in
   // cross-attention context (meta_arch.py:215-218: aux_conv_in(trimap latent) as [B, l*l, ctx]) is never materialised:
   // every block's K|V comes straight from the latent through the folded 3x3 conv (transformer())
   T lat;
-  TRY(unet_forward(e, uin, use_mask, bias_lvl, tiles_lvl, &lat));
+  TRY(unet_forward(e, uin, use_mask, bias_lvl, tiles_lvl, patch_lvl, &lat));
   tfree(e, uin);
   for (int k = 3; k >= 0; --k) { tfree(e, tilebuf[k]); tfree(e, biasbuf[k]); }
   // post_quant_conv + decoder (meta_arch.py:255-256)

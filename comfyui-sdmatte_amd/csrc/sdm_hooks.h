@@ -115,8 +115,8 @@ int sdm_op_conv_ex(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1,
  * when ln_gamma is given), w fp32 [O][K] is packed to K16 -> W3 exactly as a model layer.  mode 0: fp32 out (+bias, +fp32 residual); 1: GEGLU (O = 2 x outputs);
  * 3: linear (+residual) to P3; both P3 results are decoded to fp32 (hi + xl * 2^-11) into `out`; 2: raw q | k | v operand planes (fp16 hi [rows][O] then the
  * e5m2 pair plane, pair plane for channels < lo_cols only); 4: mode 0 + the consumer's GroupNorm statistics, [N][*srows][O][2] floats into `stats`. */
-int sdm_op_gemm_p3(sdm_ctx* e, const float* x, int N, int H, int W, int K, const float* w, const float* bias, int O, int mode, const float* res,
-                   const float* ln_gamma, const float* ln_beta, float ln_eps, int lo_cols, void* out, float* stats, int* srows) {
+static int gemm_p3_hook(sdm_ctx* e, const float* x, int N, int H, int W, int K, const float* w, const float* bias, int O, int mode, const float* res,
+                        const float* ln_gamma, const float* ln_beta, float ln_eps, int lo_cols, void* out, float* stats, int* srows, bool patch_tokens) {
   if (e) dev_use(e->device);
   if (!e || !x || !w || !out) return SDM_ERR_INVALID;
   const int geglu = mode == 1;
@@ -139,7 +139,7 @@ int sdm_op_gemm_p3(sdm_ctx* e, const float* x, int N, int H, int W, int K, const
     if (planes) to = talloc(e, N, H, W, Cst, kFmtP3);
     else to = view(out, N, H, W, Cst, (mode == 2) ? 3 : 1);
     to.want_stats = (mode == 4);
-    TRY(op_gemm_p3(e, L, xp, &to, res ? &tres : nullptr, lo_cols));
+    TRY(op_gemm_p3(e, L, xp, &to, res ? &tres : nullptr, lo_cols, patch_tokens));
     if (!e->dry) {
       if (planes) SDM_LAUNCH(from_p3_kernel, dim3((unsigned)std::min<long>((to.rows() * Cst + 255) / 256, 1 << 20)), dim3(256), 0, e->stream, (const unsigned char*)to.p, (float*)out, to.rows(), Cst);
       if (mode == 4 && stats) {
@@ -152,6 +152,54 @@ int sdm_op_gemm_p3(sdm_ctx* e, const float* x, int N, int H, int W, int K, const
     tfree(e, xp);
     return 0;
   });
+}
+
+int sdm_op_gemm_p3(sdm_ctx* e, const float* x, int N, int H, int W, int K, const float* w, const float* bias, int O, int mode, const float* res,
+                   const float* ln_gamma, const float* ln_beta, float ln_eps, int lo_cols, void* out, float* stats, int* srows) {
+  return gemm_p3_hook(e, x, N, H, W, K, w, bias, O, mode, res, ln_gamma, ln_beta, ln_eps, lo_cols, out, stats, srows, false);
+}
+
+/* The way out of a transformer in patch token order (proj_out): mode 0 / 4 of sdm_op_gemm_p3 where row t of image n of x is TOKEN t (sdm_common.h), and `out` / `res`
+ * are pixel-order rows [N][H][W][O] - the result of token t lands at (and its residual comes from) the token's pixel.  patch_tokens = 0: the plain launch. */
+int sdm_op_gemm_p3_tokens(sdm_ctx* e, const float* x, int N, int H, int W, int K, const float* w, const float* bias, int O, int mode, const float* res,
+                          int patch_tokens, float* out, float* stats, int* srows) {
+  if (mode != 0 && mode != 4) return SDM_ERR_INVALID;
+  return gemm_p3_hook(e, x, N, H, W, K, w, bias, O, mode, res, nullptr, nullptr, 0.0f, -1, out, stats, srows, patch_tokens != 0);
+}
+
+/* The way in (GroupNorm -> the P3 operand planes of proj_in): x fp32 [N][H][W][C] -> planes (ceil(N*H*W / 32) * 32 * C * 3 bytes each: fp16 hi plane, then the xl
+ * plane) in row-major order (planes_rows) and / or with row t of an image = token t (planes_tokens); either may be NULL.  Both come from ONE statistics pass: the
+ * statistics kernel adds with atomics, so two passes may differ in the last bit. */
+int sdm_op_groupnorm_p3(sdm_ctx* e, const float* x, int N, int H, int W, int C, int groups, const float* gamma, const float* beta, float eps, int silu,
+                        void* planes_rows, void* planes_tokens) {
+  if (e) dev_use(e->device);
+  if (!e || !x || (!planes_rows && !planes_tokens) || C % 32) return SDM_ERR_INVALID;
+  if (planes_tokens && !sdm_patch_tokens_ok(H, W)) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_groupnorm_p3: %dx%d does not take the patch token order", H, W);
+  return run_two_pass(e, [&]() -> int {
+    T scratch; float* scale; float* shift;
+    TRY(gn_scale_shift(e, x, nullptr, C, 0, 1, N, H * W, groups, gamma, beta, eps, nullptr, 0, nullptr, 0, false, &scratch, &scale, &shift));
+    if (!e->dry) {
+      GnSrc s; s.in0 = x; s.in1 = nullptr; s.C0 = C; s.C1 = 0; s.in_f32 = 1; s.HW = H * W;
+      const long rows = (long)N * H * W;
+      if (planes_rows)
+        SDM_LAUNCH(gn_apply_p3_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, e->stream, s, (const float*)scale, (const float*)shift, (unsigned char*)planes_rows, silu, rows, 0);
+      if (planes_tokens)
+        SDM_LAUNCH(gn_apply_p3_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, e->stream, s, (const float*)scale, (const float*)shift, (unsigned char*)planes_tokens, silu, rows, W);
+    }
+    tfree(e, scratch);
+    return 0;
+  });
+}
+
+/* The helper pair of the patch token order as the kernels use it: token_of_pixel[y * W + x] and pixel_of_token[t] (HOST, H * W ints each) of one image.
+ * Returns 1 if an H x W latent takes the order (sdm_patch_tokens_ok), else 0 with both maps the identity (row-major), < 0 on bad arguments. */
+int sdm_debug_patch_token_map(int H, int W, int32_t* token_of_pixel, int32_t* pixel_of_token) {
+  if (H < 1 || W < 1 || !token_of_pixel || !pixel_of_token) return SDM_ERR_INVALID;
+  const bool on = sdm_patch_tokens_ok(H, W);
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) token_of_pixel[y * W + x] = on ? (int32_t)sdm_patch_token_of_pixel((unsigned int)y, (unsigned int)x, (unsigned int)W) : y * W + x;
+  for (int t = 0; t < H * W; ++t) pixel_of_token[t] = on ? (int32_t)sdm_patch_pixel_of_token((unsigned int)t, (unsigned int)W) : t;
+  return on ? 1 : 0;
 }
 
 /* Upsample2D (nearest x2 + 3x3 conv, split precision, fp32 NHWC in and out) with the consumer's GroupNorm statistics, as the model's up-sampling layers run
@@ -680,7 +728,30 @@ int sdm_op_mask_bias(sdm_ctx* e, const float* plane, int B, int S, int level, fl
   if (e) dev_use(e->device);
   if (!e || !plane || !out) return SDM_ERR_INVALID;
   const int lk = (S / 8) >> level;
-  SDM_LAUNCH(mask_bias_kernel, dim3(sdm_cdiv(B * lk * lk, 256)), dim3(256), 0, e->stream, plane, out, B, S, S, level, e->cfg.attn_mask_value, 1.0f);
+  SDM_LAUNCH(mask_bias_kernel, dim3(sdm_cdiv(B * lk * lk, 256)), dim3(256), 0, e->stream, plane, out, B, S, S, level, e->cfg.attn_mask_value, 1.0f, 0);
+  SDM_CHECK_DEV(e, dev_sync(e->stream));
+  return 0;
+}
+
+/* The level's key bias as the U-Net passes it to its self-attentions, on a rectangle: log2 domain, and in patch token order if patch_tokens != 0 and the level's
+ * latent takes it (sdm_patch_tokens_ok; otherwise row-major).  Returns 1 / 0 = the order written, < 0 on error. */
+int sdm_op_mask_bias_tokens(sdm_ctx* e, const float* plane, int B, int SH, int SW, int level, int patch_tokens, float* out) {
+  if (e) dev_use(e->device);
+  if (!e || !plane || !out || level < 0 || level > 3) return SDM_ERR_INVALID;
+  const int hk = (SH / 8) >> level, wk = (SW / 8) >> level;
+  if (hk < 1 || wk < 1) return SDM_ERR_INVALID;
+  const int pt = (patch_tokens && sdm_patch_tokens_ok(hk, wk)) ? 1 : 0;
+  SDM_LAUNCH(mask_bias_kernel, dim3(sdm_cdiv(B * hk * wk, 256)), dim3(256), 0, e->stream, plane, out, B, SH, SW, level, e->cfg.attn_mask_value, SDM_LOG2E, pt);
+  SDM_CHECK_DEV(e, dev_sync(e->stream));
+  return pt;
+}
+
+/* The list of active 64-key tiles the engine builds from a key bias [B][Lk] (log2 domain): tiles int [B][ceil(Lk / 64) + 1] = count, then ascending tile indices. */
+int sdm_op_active_tiles(sdm_ctx* e, const float* bias, int B, int Lk, int32_t* tiles) {
+  if (e) dev_use(e->device);
+  if (!e || !bias || !tiles || B < 1 || Lk < 1) return SDM_ERR_INVALID;
+  const int nt = sdm_cdiv(Lk, 64);
+  SDM_LAUNCH(attn_active_tiles_kernel, dim3(B), dim3(256), 0, e->stream, bias, Lk, nt, (int*)tiles, nt + 1, SDM_ATTN_SKIP_MARGIN);
   SDM_CHECK_DEV(e, dev_sync(e->stream));
   return 0;
 }

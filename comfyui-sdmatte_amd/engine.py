@@ -86,7 +86,8 @@ EXPORTS = [
     "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
-    "sdm_op_mask_bias", "sdm_op_cross_patch_planes", "sdm_op_cross_patch_planes_ex", "sdm_op_attention_shared", "sdm_debug_cross_attention", "sdm_op_cross_core",
+    "sdm_op_mask_bias", "sdm_debug_patch_token_map", "sdm_op_groupnorm_p3", "sdm_op_gemm_p3_tokens", "sdm_op_mask_bias_tokens", "sdm_op_active_tiles",
+    "sdm_op_cross_patch_planes", "sdm_op_cross_patch_planes_ex", "sdm_op_attention_shared", "sdm_debug_cross_attention", "sdm_op_cross_core",
     "sdm_set_option", "sdm_get_option", "sdm_reset_options", "sdm_option_name", "sdm_option_help", "sdm_kernel_counts", "sdm_kernel_counts_reset",
 ]
 
@@ -163,6 +164,11 @@ class Bindings:
             "sdm_debug_attn_plan": (i32, [i32] * 10 + [C.c_char_p, i32, C.POINTER(i32)]),
             "sdm_op_resize_aa": (i32, [vp, vp, i32, i32, i32, vp, i32, i32]),
             "sdm_op_mask_bias": (i32, [vp, vp, i32, i32, i32, vp]),
+            "sdm_debug_patch_token_map": (i32, [i32, i32, vp, vp]),
+            "sdm_op_groupnorm_p3": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp]),
+            "sdm_op_gemm_p3_tokens": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, C.POINTER(i32)]),
+            "sdm_op_mask_bias_tokens": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+            "sdm_op_active_tiles": (i32, [vp, vp, i32, i32, vp]),
             "sdm_op_cross_patch_planes": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
             "sdm_op_cross_patch_planes_ex": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, i32]),
             "sdm_op_cross_core": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
@@ -1183,6 +1189,64 @@ class Engine:
         P, Hin, Win = planes.shape
         out = torch.empty(P, Hout, Wout, dtype=torch.float32, device=planes.device)
         self._check(self.lib.sdm_op_resize_aa(self.h, _ptr(planes), P, Hin, Win, _ptr(out), Hout, Wout), "sdm_op_resize_aa")
+        return out
+
+    def patch_token_map(self, H, W_):
+        """Test hook: the engine's own helper pair of the patch token order for one H x W image -> (takes the order, token_of_pixel [H*W], pixel_of_token [H*W])."""
+        t_of_p = np.zeros(H * W_, np.int32); p_of_t = np.zeros(H * W_, np.int32)
+        rc = self.lib.sdm_debug_patch_token_map(H, W_, t_of_p.ctypes.data_as(C.c_void_p), p_of_t.ctypes.data_as(C.c_void_p))
+        if rc < 0:
+            raise RuntimeError("sdm_debug_patch_token_map: bad arguments")
+        return bool(rc), t_of_p, p_of_t
+
+    def op_groupnorm_p3(self, x, gamma, beta, eps, groups=32, silu=False, tokens=True):
+        """Test hook: GroupNorm of x fp32 [N,H,W,C] as the operand planes of proj_in, from ONE statistics pass -> (row-major planes, patch-order planes or None),
+        each uint8 [ceil(N*H*W/32)*32 * C * 3] (fp16 hi plane, then the xl plane); in the patch-order planes row t of an image is token t."""
+        N, H, W_, Cc = x.shape
+        x = x.float().contiguous()
+        rows_pad = (N * H * W_ + 31) // 32 * 32
+        a = torch.full((rows_pad * Cc * 3,), 0x5A, dtype=torch.uint8, device=x.device)
+        b = torch.full((rows_pad * Cc * 3,), 0x5A, dtype=torch.uint8, device=x.device) if tokens else None
+        self._check(self.lib.sdm_op_groupnorm_p3(self.h, _ptr(x), N, H, W_, Cc, groups, _ptr(gamma.float().contiguous()), _ptr(beta.float().contiguous()), float(eps),
+                                                 int(silu), _ptr(a), _ptr(b)), "sdm_op_groupnorm_p3")
+        return a, b
+
+    def op_gemm_p3_tokens(self, x, w, bias=None, mode=0, res=None, patch_tokens=False, out=None):
+        """Test hook: the plane-fed GEMM mode 0 / 4 on x fp32 [N,H,W,K] whose rows are tokens; out / res are pixel-order [N,H,W,O] (patch_tokens) or plain rows.
+        out: an fp32 [N,H,W,O] tensor to write into (may be a view inside a larger buffer: guard rows).  -> out, or (out, stats [N,srows,O,2]) for mode 4."""
+        N, H, W_, K = x.shape
+        O = w.shape[0]
+        x = x.float().contiguous(); w = w.float().contiguous()
+        b = bias.float().contiguous() if bias is not None else None
+        r = res.float().contiguous() if res is not None else None
+        if out is None:
+            out = torch.empty(N, H, W_, O, dtype=torch.float32, device=x.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == N * H * W_ * O
+        srows_max = 2 * ((H * W_ + 63) // 64)
+        stats = torch.zeros(N * srows_max * O * 2, dtype=torch.float32, device=x.device) if mode == 4 else None
+        srows = C.c_int(0)
+        self._check(self.lib.sdm_op_gemm_p3_tokens(self.h, _ptr(x), N, H, W_, K, _ptr(w), _ptr(b), O, mode, _ptr(r), int(patch_tokens), _ptr(out), _ptr(stats),
+                                                   C.byref(srows)), "sdm_op_gemm_p3_tokens")
+        if mode == 4:
+            return out, stats[:N * srows.value * O * 2].view(N, srows.value, O, 2)
+        return out
+
+    def op_mask_bias_tokens(self, plane, level, patch_tokens=True):
+        """Test hook: the key bias of U-Net level `level` from the trimap plane fp32 [B,SH,SW] as the self-attentions get it (log2 domain) -> (fp32 [B, hk*wk],
+        written in patch order?)."""
+        B, SH, SW = plane.shape
+        hk, wk = (SH // 8) >> level, (SW // 8) >> level
+        out = torch.empty(B, hk * wk, dtype=torch.float32, device=plane.device)
+        rc = self.lib.sdm_op_mask_bias_tokens(self.h, _ptr(plane.float().contiguous()), B, SH, SW, level, int(patch_tokens), _ptr(out))
+        if rc < 0:
+            self._check(rc, "sdm_op_mask_bias_tokens")
+        return out, bool(rc)
+
+    def op_active_tiles(self, bias):
+        """Test hook: the engine's list of active 64-key tiles of a key bias fp32 [B,Lk] -> int32 [B, ceil(Lk/64) + 1] (count, then ascending tile indices)."""
+        B, Lk = bias.shape
+        out = torch.full((B, (Lk + 63) // 64 + 1), -1, dtype=torch.int32, device=bias.device)
+        self._check(self.lib.sdm_op_active_tiles(self.h, _ptr(bias.float().contiguous()), B, Lk, _ptr(out)), "sdm_op_active_tiles")
         return out
 
     def op_mask_bias(self, plane_bss, level):

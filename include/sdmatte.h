@@ -621,6 +621,23 @@ int sdm_debug_attn_plan(int B, int heads, int Lq, int Lk, int D, int prec, int o
 int sdm_op_resize_aa(sdm_ctx* ctx, const float* in, int P, int Hin, int Win, float* out, int Hout, int Wout);
 /* Level-k additive key bias (natural-log domain) from the [-1,1] trimap plane [B,S,S] -> [B,(S/8>>k)^2]. */
 int sdm_op_mask_bias(sdm_ctx* ctx, const float* trimap_plane, int B, int S, int level, float* bias_out);
+/* Test hooks of the patch token order of the U-Net transformers (engine option attn_patch_tokens): inside a transformer of a level whose
+ * latent H x W is whole 8x8 patches and at least 64 wide, token ((y>>3)*(W>>3) + (x>>3))*64 + (y&7)*8 + (x&7) is pixel (y, x) of its image.
+ * sdm_debug_patch_token_map: the helper pair the kernels use, for one image (HOST arrays of H*W ints); returns 1 if H x W takes the order, 0 (identity maps) if not.
+ * sdm_op_groupnorm_p3: the way in - GroupNorm of x fp32 [N][H][W][C] (DEVICE, C % 32 == 0) as the operand planes of proj_in (ceil(N*H*W/32)*32 * C * 3 bytes
+ * each: fp16 hi plane, then the e5m2 xl plane), in row-major order into planes_rows and / or with row t of an image = token t into planes_tokens (either may be
+ * NULL), both from one statistics pass.
+ * sdm_op_gemm_p3_tokens: the way out - sdm_op_gemm_p3 mode 0 / 4 where the rows of x are tokens and out / res are pixel-order [N][H][W][O]; patch_tokens = 0:
+ * the plain launch.  sdm_op_mask_bias_tokens: the key bias of a level as the U-Net passes it to its self-attentions (log2 domain, rectangles allowed), in patch
+ * order where patch_tokens != 0 and the level takes it; returns the order written (1 / 0).  sdm_op_active_tiles: the engine's list of active 64-key tiles of a
+ * bias [B][Lk] (DEVICE) -> int [B][ceil(Lk/64) + 1] (DEVICE): count, then the ascending tile indices. */
+int sdm_debug_patch_token_map(int H, int W, int32_t* token_of_pixel, int32_t* pixel_of_token);
+int sdm_op_groupnorm_p3(sdm_ctx* ctx, const float* x, int N, int H, int W, int C, int groups, const float* gamma, const float* beta, float eps, int silu,
+                        void* planes_rows, void* planes_tokens);
+int sdm_op_gemm_p3_tokens(sdm_ctx* ctx, const float* x, int N, int H, int W, int K, const float* w, const float* bias, int O, int mode, const float* res,
+                          int patch_tokens, float* out, float* stats, int* srows);
+int sdm_op_mask_bias_tokens(sdm_ctx* ctx, const float* trimap_plane, int B, int SH, int SW, int level, int patch_tokens, float* bias_out);
+int sdm_op_active_tiles(sdm_ctx* ctx, const float* bias, int B, int Lk, int32_t* tiles);
 
 #ifdef __cplusplus
 }
