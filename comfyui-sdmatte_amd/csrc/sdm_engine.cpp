@@ -139,6 +139,7 @@ static OptEntry g_opts[] = {
   {"cross_narrow", 1, 1, "cross_shared: the narrow form of the d = 64 cores on the shared operand (36 live columns: no Q.K^T step over columns 48..63, the softmax denominator from a row of ones in V^T instead of its own MFMAs; bit-identical).  0 = the full d = 64 program on an operand without the ones rows.  Read per forward"},
   {"cross_shared", 1, 1, "cross-attention on ONE key / value operand per forward, the patch matrix of the trimap latent (cross_patch_planes_kernel), with the K|V fold moved into q_shared / out_shared: 0 = every block's own kv_folded conv + transpose.  Read per forward"},
   {"attn_patch_tokens", 1, 1, "token order inside the U-Net transformers of a level whose latent is whole 8x8 patches and at least 64 wide (sdm_patch_tokens_ok): 64 consecutive tokens = an 8x8 patch, so the key tiles the trimap bias skips follow the foreground's shape (GroupNorm-apply in front of proj_in, the proj_out epilogue and the level's key bias carry the map).  0 = row-major pixel order everywhere.  Read per forward"},
+  {"dbg_stats_poison", 0, 0, "tests: every partial-row statistics buffer is filled with 0xFF bytes (NaN) in front of the launch that writes it - a row the launch forgets shows in whatever reads it (the buffers are never cleared otherwise)"},
   {"precise_mask", -1, -1, "stages in split precision (-1 = the config's own mask; per-stage attribution experiments; read at sdm_create)"},
 #ifdef SDM_EMU
   {"emu_arena_extra", 0, 0, "emulator build only, self-test of the arena check: the launch pass of a stand-alone op allocates one block its sizing pass did not"},
@@ -1236,6 +1237,13 @@ static bool conv_up_phase_ok(const ConvL& L, const ConvArgs& a) {
   const size_t tile_out = (size_t)2 * (256 / (a.in0->W + 2) + 2) * 2 * a.in0->W * a.out->C * 4;
   return p3_rows_pad(rows) * (size_t)L.Cin_pad * 2 < SDM_BUF_INVALID && tile_out < SDM_BUF_INVALID && rows < ((size_t)1 << 31);
 }
+// test option dbg_stats_poison: the partial rows of `t` start as NaN (launch pass only; nothing is allocated)
+static int stats_poison(sdm_ctx* e, const T& t) {
+  if (e->dry || !t.stats || !opt("dbg_stats_poison")) return 0;
+  SDM_CHECK_DEV(e, dev_memset(t.stats, 0xFF, (size_t)t.N * t.srows * t.C * 2 * 4, e->stream));
+  return 0;
+}
+
 static int op_conv_up_phase(sdm_ctx* e, const ConvL& L, const ConvArgs& a) {
   const T& in = *a.in0;
   T* out = a.out;
@@ -1257,6 +1265,7 @@ static int op_conv_up_phase(sdm_ctx* e, const ConvL& L, const ConvArgs& a) {
     p.stats = out->stats;
   }
   if (e->dry) { tfree(e, xp); return 0; }
+  if (epi == 4) TRY(stats_poison(e, *out));
   char d[256];
   d[0] = 0;
   if (e->prof_on) snprintf(d, sizeof(d), "%s N=%d H=%d W=%d C=%d bordered grid", L.name.c_str(), in.N, in.H, in.W, in.C);
@@ -1384,6 +1393,7 @@ static int op_conv(sdm_ctx* e, const ConvL& L, const ConvArgs& a) {
     }
   }
   if (e->dry) { if (ksplit > 1) tfree(e, ws); if (cm_skip) { tfree(e, cm_rep); tfree(e, cm_flag); } return 0; }
+  if (p.stats) TRY(stats_poison(e, *a.out));
   const double flops = 2.0 * (double)p.M * L.O * L.I * L.ntaps;
   const double bytes = (double)a.in0->rows() * L.Cin_pad * (p.in_f32 ? 4 : 2) + (double)p.M * p.Cout_valid * (p.out_f32 ? 4 : 2) +
                        (double)L.Cin_pad * L.ntaps * L.Cout_pad * 2 + (a.res ? (double)p.M * p.Cout_valid * (p.res_f32 ? 4 : 2) : 0.0);
@@ -1885,6 +1895,7 @@ static int op_gemm_p3(sdm_ctx* e, const ConvL& L, const T& in, T* out, const T* 
     if (span >= (double)SDM_BUF_INVALID) SDM_FAIL(e, SDM_ERR_INVALID, "gemm %s: a tile's pixel rows exceed the buffer descriptor range", L.name.c_str());
   }
   if (e->dry) return 0;
+  if (epi == 4) TRY(stats_poison(e, *out));
   const double flops = 2.0 * (double)p.M * L.O * L.I;
   const double bytes = (double)p.M * p.K * 3 + (double)p.M * p.n_valid * (double)fmt_bytes(out->f32) + (double)p.K * p.N * 4 + (res ? (double)p.M * p.n_valid * 4 : 0.0);
   if (e->prof_on) {

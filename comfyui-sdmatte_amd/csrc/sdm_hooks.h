@@ -69,12 +69,18 @@ extern "C" {
 // ---- single-operator entry points ----
 int sdm_conv_num_cfgs(int ntaps, int stride) { return conv_num_cfgs(ntaps, stride); }
 
-int sdm_op_conv_ex(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1, int in_f32, int N, int Hin, int Win, int up, int stride,
-                   int pad_mode, int ntaps, const float* w, const float* bias, int O, void* out, int out_f32, const void* res, int res_f32,
-                   int geglu, float out_scale, int tile_cfg, int split, const float* gn_gamma, const float* gn_beta, float gn_eps,
-                   int gn_groups, int gn_silu) {
+// One conv through op_conv, for sdm_op_conv_ex and sdm_op_conv_stats.  in_st0 (+ in_st1 for a concat): partial statistics rows of the input - the
+// fused GroupNorm then takes its table from gn_partials_scale_shift_kernel as the model does, not from the stand-alone statistics kernel.
+// stats: the output's own partial rows are wanted ([N][*srows][Cst][2], Cst = the stored channel count; room for stats_cap rows per image).
+static int conv_hook(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1, int in_f32, int N, int Hin, int Win, int up, int stride,
+                     int pad_mode, int ntaps, const float* w, const float* bias, int O, void* out, int out_f32, const void* res, int res_f32,
+                     int geglu, float out_scale, int tile_cfg, int split, const float* gn_gamma, const float* gn_beta, float gn_eps,
+                     int gn_groups, int gn_silu, const float* in_st0, int in_rows0, const float* in_st1, int in_rows1, float* stats, int stats_cap,
+                     int* srows) {
   if (e) dev_use(e->device);
   if (!e || !in0 || !w || !out) return SDM_ERR_INVALID;
+  if (stats && !srows) return SDM_ERR_INVALID;
+  if (in_st0 && (!gn_gamma || (in1 && !in_st1))) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv_stats: input statistics go with a fused GroupNorm, one set of rows per source");
   if (C0 % 16 || C1 % 16) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv: channel counts must be multiples of 16");
   if (split && !in_f32) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv_ex: split precision takes fp32 activations");
   TempLayer tl(e);      // every layout a layer of this shape can carry but W3: the conv launchers never read it
@@ -88,27 +94,73 @@ int sdm_op_conv_ex(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1,
   if (e->dbg_cmask) { tin0.cmask = const_cast<unsigned char*>(e->dbg_cmask); tin0.cm_bytes = 1; e->dbg_cmask = nullptr; }      // (borrowed: tin0 is never tfree'd)
   ConvArgs a; a.in0 = &tin0; a.in1 = in1 ? &tin1 : nullptr; a.out = &tout; a.stride = stride; a.pad_mode = pad_mode; a.up = up;
   a.res = res ? &tres : nullptr; a.out_scale = out_scale; a.force_cfg = tile_cfg; a.cout_valid = Cst;
-  int rc;
+  tout.want_stats = stats != nullptr;
   if (gn_gamma) {
-    // GroupNorm(+SiLU) of the input applied inside the conv's operand staging (the production path of every ResBlock conv):
-    // statistics by the stand-alone kernel, scale/shift table, then the fused-GN instantiation of tile cfg 0 / 4 / 5
+    // GroupNorm(+SiLU) of the input applied inside the conv's operand staging (the production path of every ResBlock conv): statistics by the
+    // stand-alone kernel or from the caller's partial rows, scale/shift table, then the fused-GN instantiation of tile cfg 0 / 4 / 5
     if (ntaps != 9 || stride != 1 || up) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv_ex: fused GroupNorm needs a 3x3 stride-1 conv");
     if (a.force_cfg != 0 && a.force_cfg != 4 && a.force_cfg != 5) a.force_cfg = (L.Cout_pad <= 32) ? 4 : 0;
-    RestoreInt keep_act{e->act_f32, e->act_f32};
-    rc = run_two_pass(e, [&]() {
-      T scratch; float* scale; float* shift;
-      TRY(gn_scale_shift(e, in0, in1, C0, C1, in_f32, N, Hin * Win, gn_groups, gn_gamma, gn_beta, gn_eps, nullptr, 0, nullptr, 0, false, &scratch,
-                         &scale, &shift));
-      ConvArgs b = a;
-      b.gn_scale = e->dry ? (const float*)16 : scale; b.gn_shift = shift; b.gn_silu = gn_silu;
-      int r2 = op_conv(e, L, b);
-      tfree(e, scratch);
-      return r2;
-    });
-  } else {
-    rc = run_two_pass(e, [&]() { return op_conv(e, L, a); });      // (the arena holds the split-K workspace, if the layer is split)
   }
-  return rc;
+  RestoreInt keep_act{e->act_f32, e->act_f32};
+  return run_two_pass(e, [&]() -> int {      // (the arena holds the split-K workspace, if the layer is split)
+    T scratch;
+    ConvArgs b = a;
+    if (gn_gamma) {
+      float* scale; float* shift;
+      TRY(gn_scale_shift(e, in0, in1, C0, C1, in_f32, N, Hin * Win, gn_groups, gn_gamma, gn_beta, gn_eps, in_st0, in_rows0, in_st1, in_rows1,
+                         in_st0 != nullptr, &scratch, &scale, &shift));
+      b.gn_scale = e->dry ? (const float*)16 : scale; b.gn_shift = shift; b.gn_silu = gn_silu;
+    }
+    TRY(op_conv(e, L, b));
+    if (stats && !e->dry) {
+      if (tout.srows > stats_cap) SDM_FAIL(e, SDM_ERR_INVALID, "sdm_op_conv_stats: %d partial rows per image, room for %d", tout.srows, stats_cap);
+      SDM_CHECK_DEV(e, dev_memcpy_d2d(stats, tout.stats, (size_t)N * tout.srows * Cst * 2 * 4, e->stream));
+      *srows = tout.srows;
+    }
+    if (tout.sbytes) { tfree_raw(e, tout.soff, tout.sbytes); tout.sbytes = 0; }
+    if (gn_gamma) tfree(e, scratch);
+    return 0;
+  });
+}
+
+int sdm_op_conv_ex(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1, int in_f32, int N, int Hin, int Win, int up, int stride,
+                   int pad_mode, int ntaps, const float* w, const float* bias, int O, void* out, int out_f32, const void* res, int res_f32,
+                   int geglu, float out_scale, int tile_cfg, int split, const float* gn_gamma, const float* gn_beta, float gn_eps,
+                   int gn_groups, int gn_silu) {
+  return conv_hook(e, in0, in1, C0, C1, in_f32, N, Hin, Win, up, stride, pad_mode, ntaps, w, bias, O, out, out_f32, res, res_f32, geglu, out_scale,
+                   tile_cfg, split, gn_gamma, gn_beta, gn_eps, gn_groups, gn_silu, nullptr, 0, nullptr, 0, nullptr, 0, nullptr);
+}
+
+/* sdm_op_conv_ex that also returns the partial {sum, sumsq} rows its epilogue writes for the next GroupNorm (`stats`, [N][*srows][Cst][2] with Cst = O
+ * rounded up to 4; room for stats_cap rows per image) and, with in_st0 / in_rows0 (+ in_st1 / in_rows1 for a concat input) and gn_gamma, takes the fused
+ * GroupNorm's scale | shift table from those rows through gn_partials_scale_shift_kernel - the chain every ResBlock conv of the model runs. */
+int sdm_op_conv_stats(sdm_ctx* e, const void* in0, const void* in1, int C0, int C1, int in_f32, int N, int Hin, int Win, int up, int stride,
+                      int pad_mode, int ntaps, const float* w, const float* bias, int O, void* out, int out_f32, const void* res, int res_f32,
+                      int geglu, float out_scale, int tile_cfg, int split, const float* gn_gamma, const float* gn_beta, float gn_eps,
+                      int gn_groups, int gn_silu, const float* in_st0, int in_rows0, const float* in_st1, int in_rows1, float* stats, int stats_cap,
+                      int* srows) {
+  if (!stats || !srows || stats_cap < 1) return SDM_ERR_INVALID;
+  return conv_hook(e, in0, in1, C0, C1, in_f32, N, Hin, Win, up, stride, pad_mode, ntaps, w, bias, O, out, out_f32, res, res_f32, geglu, out_scale,
+                   tile_cfg, split, gn_gamma, gn_beta, gn_eps, gn_groups, gn_silu, in_st0, in_rows0, in_st1, in_rows1, stats, stats_cap, srows);
+}
+
+/* The reducer alone: partial rows st0 [N][rows0][C0][2] (+ st1 [N][rows1][C1][2], the second source of a channel concat; C1 = 0: none) of images of HW pixels ->
+ * scale [N][C0 + C1] = rstd * gamma and shift [N][C0 + C1] = beta - mean * rstd * gamma (gn_partials_scale_shift_kernel, as gn_scale_shift launches it). */
+int sdm_op_gn_partials(sdm_ctx* e, const float* st0, int rows0, const float* st1, int rows1, int C0, int C1, int N, int HW, int groups,
+                       const float* gamma, const float* beta, float eps, float* scale_out, float* shift_out) {
+  if (e) dev_use(e->device);
+  if (!e || !st0 || rows0 < 1 || (C1 > 0 && (!st1 || rows1 < 1)) || !gamma || !beta || !scale_out || !shift_out || N < 1 || HW < 1 || groups < 1) return SDM_ERR_INVALID;
+  return run_two_pass(e, [&]() -> int {
+    T scratch; float* scale; float* shift;
+    TRY(gn_scale_shift(e, nullptr, nullptr, C0, C1, 1, N, HW, groups, gamma, beta, eps, st0, rows0, C1 > 0 ? st1 : nullptr, C1 > 0 ? rows1 : 0, true,
+                       &scratch, &scale, &shift));
+    if (!e->dry) {
+      SDM_CHECK_DEV(e, dev_memcpy_d2d(scale_out, scale, (size_t)N * (C0 + C1) * 4, e->stream));
+      SDM_CHECK_DEV(e, dev_memcpy_d2d(shift_out, shift, (size_t)N * (C0 + C1) * 4, e->stream));
+    }
+    tfree(e, scratch);
+    return 0;
+  });
 }
 
 /* Plane-fed GEMM (k_gemm.h) as a stand-alone operator: x fp32 [N*H*W][K] (device) is converted to P3 planes (to_p3_kernel, or LayerNorm with P3 output
@@ -225,7 +277,7 @@ int sdm_op_conv_up_stats(sdm_ctx* e, const float* x, int N, int H, int W, int C,
   });
 }
 
-/* Test hook: `mask` (device, [N][Hin][Win] bytes, class ids 0..4; k_misc.h cmask_*) is the class plane of the input of the NEXT sdm_op_conv_ex call -
+/* Test hook: `mask` (device, [N][Hin][Win] bytes, class ids 0..4; k_misc.h cmask_*) is the class plane of the input of the NEXT sdm_op_conv_ex / sdm_op_conv_stats call -
  * the conv then leaves the output tiles of constant regions to const_tile_fill_kernel, as the VAE encoder does for the trimap images. */
 int sdm_debug_set_input_cmask(sdm_ctx* e, const unsigned char* mask) {
   if (!e) return SDM_ERR_INVALID;

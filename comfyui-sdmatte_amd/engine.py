@@ -85,7 +85,7 @@ EXPORTS = [
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
     "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
-    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
+    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_stats", "sdm_op_gn_partials", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias", "sdm_debug_patch_token_map", "sdm_op_groupnorm_p3", "sdm_op_gemm_p3_tokens", "sdm_op_mask_bias_tokens", "sdm_op_active_tiles",
     "sdm_op_cross_patch_planes", "sdm_op_cross_patch_planes_ex", "sdm_op_attention_shared", "sdm_debug_cross_attention", "sdm_op_cross_core",
     "sdm_set_option", "sdm_get_option", "sdm_reset_options", "sdm_option_name", "sdm_option_help", "sdm_kernel_counts", "sdm_kernel_counts_reset",
@@ -146,6 +146,9 @@ class Bindings:
                                   f32, i32]),
             "sdm_op_conv_ex": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32,
                                      f32, i32, i32, vp, vp, f32, i32, i32]),
+            "sdm_op_conv_stats": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32,
+                                        f32, i32, i32, vp, vp, f32, i32, i32, vp, i32, vp, i32, vp, i32, C.POINTER(i32)]),
+            "sdm_op_gn_partials": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp]),
             "sdm_op_gemm_p3": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, f32, i32, vp, vp, C.POINTER(i32)]),
             "sdm_op_conv_up_stats": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, C.POINTER(i32)]),
             "sdm_debug_run_layer": (i32, [vp, C.c_char_p, vp, i32, i32, i32, vp, i32]),
@@ -1021,6 +1024,57 @@ class Engine:
                                             int(gn[3]) if gn is not None else 32, int(gn[4]) if gn is not None else 0),
                     "sdm_op_conv_ex")
         return out[..., :Creal]
+
+    def op_conv_stats(self, x0, w, bias=None, x1=None, stride=1, pad_mode=0, up=0, res=None, out_f32=False, out_scale=1.0, tile_cfg=-1, split=False,
+                      gn=None, cmask=None, in_stats=None):
+        """Test hook: op_conv that also returns the partial {sum, sumsq} rows the conv's epilogue writes for the next GroupNorm -> (out NHWC,
+        stats [N,srows,Cst,2] with Cst = O rounded up to 4; channels >= O unspecified).  in_stats = (st0,) or (st0, st1), with gn: the fused GroupNorm's
+        scale | shift table comes from these partial rows of the input(s) (gn_partials_scale_shift_kernel, the model's path), not from the stand-alone
+        statistics kernel."""
+        N, H, W_, C0 = x0.shape
+        C1 = x1.shape[-1] if x1 is not None else 0
+        ntaps = 9 if (w.dim() == 4 and w.shape[-1] == 3) else 1
+        O = w.shape[0]
+        Ho, Wo = (H << up), (W_ << up)
+        if stride == 2:
+            Ho, Wo = Ho // 2, Wo // 2
+        Cst = (O + 3) // 4 * 4
+        out = torch.empty(N, Ho, Wo, Cst, dtype=torch.float32 if out_f32 else torch.float16, device=x0.device)
+        w = w.float().contiguous()
+        b = bias.float().contiguous() if bias is not None else None
+        gam = gn[0].float().contiguous() if gn is not None else None
+        bet = gn[1].float().contiguous() if gn is not None else None
+        st0 = in_stats[0].float().contiguous() if in_stats is not None else None
+        st1 = in_stats[1].float().contiguous() if in_stats is not None and len(in_stats) > 1 else None
+        # one row per 32 output pixels at most (the 4 x 32 tile on four wave rows, the 8 x 8 tile on two), tiles counted per dimension; the phase path's own bound
+        cap = max(4 * ((Ho + 3) // 4) * ((Wo + 7) // 8), 4 * ((Ho * Wo + 63) // 64), 8 * (((H + 2) * (W_ + 2) + 63) // 64))
+        stats = torch.zeros(N * cap * Cst * 2, dtype=torch.float32, device=x0.device)
+        srows = C.c_int(0)
+        if cmask is not None:
+            cmask = cmask.to(torch.uint8).contiguous()
+            self._check(self.lib.sdm_debug_set_input_cmask(self.h, _ptr(cmask)), "sdm_debug_set_input_cmask")
+        self._check(self.lib.sdm_op_conv_stats(self.h, _ptr(x0), _ptr(x1), C0, C1, int(x0.dtype == torch.float32), N, H, W_, up, stride,
+                                               pad_mode, ntaps, _ptr(w), _ptr(b), O, _ptr(out), int(out_f32), _ptr(res),
+                                               int(res is not None and res.dtype == torch.float32), 0, float(out_scale), tile_cfg,
+                                               int(split), _ptr(gam), _ptr(bet), float(gn[2]) if gn is not None else 0.0,
+                                               int(gn[3]) if gn is not None else 32, int(gn[4]) if gn is not None else 0,
+                                               _ptr(st0), st0.shape[1] if st0 is not None else 0, _ptr(st1), st1.shape[1] if st1 is not None else 0,
+                                               _ptr(stats), cap, C.byref(srows)), "sdm_op_conv_stats")
+        return out[..., :O], stats[:N * srows.value * Cst * 2].view(N, srows.value, Cst, 2)
+
+    def op_gn_partials(self, st0, gamma, beta, eps, HW, groups=32, st1=None):
+        """Test hook: the reducer of the fused GroupNorm statistics alone.  st0 [N,rows0,C0,2] (+ st1 [N,rows1,C1,2], the second concat source) partial rows
+        of images of HW pixels -> (scale [N,C0+C1], shift [N,C0+C1])."""
+        st0 = st0.float().contiguous()
+        st1 = st1.float().contiguous() if st1 is not None else None
+        N, rows0, C0, _ = st0.shape
+        rows1, C1 = (st1.shape[1], st1.shape[2]) if st1 is not None else (0, 0)
+        gamma, beta = gamma.float().contiguous(), beta.float().contiguous()
+        scale = torch.empty(N, C0 + C1, dtype=torch.float32, device=st0.device)
+        shift = torch.empty(N, C0 + C1, dtype=torch.float32, device=st0.device)
+        self._check(self.lib.sdm_op_gn_partials(self.h, _ptr(st0), rows0, _ptr(st1), rows1, C0, C1, N, int(HW), groups, _ptr(gamma), _ptr(beta), float(eps),
+                                                _ptr(scale), _ptr(shift)), "sdm_op_gn_partials")
+        return scale, shift
 
     def op_conv_up_stats(self, x, w, bias=None):
         """Test hook: Upsample2D (nearest x2 + 3x3 conv, split precision) on x fp32 [N,H,W,C] with the consumer's GroupNorm statistics, as the model's

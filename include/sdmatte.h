@@ -540,6 +540,20 @@ int sdm_op_conv_ex(sdm_ctx* ctx, const void* in0, const void* in1, int C0, int C
                    int stride, int pad_mode, int ntaps, const float* w, const float* bias, int O, void* out, int out_f32,
                    const void* res, int res_f32, int geglu, float out_scale, int tile_cfg, int split, const float* gn_gamma,
                    const float* gn_beta, float gn_eps, int gn_groups, int gn_silu);
+/* Test hook: sdm_op_conv_ex that also hands back the partial {sum, sumsq} rows its epilogue writes for the NEXT GroupNorm - `stats`, [N][*srows][Cst][2] floats
+ * with Cst = the stored channel count (O rounded up to 4), one row per (tile, wave row) of an image (split-K: per 64 rows; DESIGN.md 4, "partial rows"); channels
+ * >= O of a row are unspecified; room for stats_cap rows per image, more is an error.  in_st0 / in_rows0 (+ in_st1 / in_rows1 for a concat input; NULL: none), with
+ * gn_gamma: the fused GroupNorm takes its scale | shift table from these partial rows of the input through gn_partials_scale_shift_kernel, as the model does
+ * (sdm_op_conv_ex computes the statistics with the stand-alone kernel).  Honours sdm_debug_set_input_cmask. */
+int sdm_op_conv_stats(sdm_ctx* ctx, const void* in0, const void* in1, int C0, int C1, int in_f32, int N, int Hin, int Win, int up,
+                      int stride, int pad_mode, int ntaps, const float* w, const float* bias, int O, void* out, int out_f32,
+                      const void* res, int res_f32, int geglu, float out_scale, int tile_cfg, int split, const float* gn_gamma,
+                      const float* gn_beta, float gn_eps, int gn_groups, int gn_silu, const float* in_st0, int in_rows0, const float* in_st1,
+                      int in_rows1, float* stats, int stats_cap, int* srows);
+/* Test hook: gn_partials_scale_shift_kernel alone.  st0 [N][rows0][C0][2] (+ st1 [N][rows1][C1][2]: second source of a channel concat, C1 = 0 for none) partial
+ * rows of images of HW pixels -> scale [N][C0 + C1] = rstd * gamma, shift [N][C0 + C1] = beta - mean * rstd * gamma.  C0 % 8 == 0, (C0 + C1) % 8 == 0. */
+int sdm_op_gn_partials(sdm_ctx* ctx, const float* st0, int rows0, const float* st1, int rows1, int C0, int C1, int N, int HW, int groups,
+                       const float* gamma, const float* beta, float eps, float* scale, float* shift);
 /* bench only (tools/gemm_p3_bench.py): ms per launch of the plane-fed GEMM on random operands; epi_flags = epilogue (0 fp32, 1 GEGLU, 2 q|k|v planes, 3 planes,
  * 4 fp32 + statistics) | 256 for an fp32 residual */
 float sdm_bench_gemm_p3(sdm_ctx* ctx, long M, int K, int O, int epi_flags, int iters);

@@ -26,13 +26,14 @@ def h16(x):
 
 
 def check_conv(eng, dev, N, H, W, Cin, Cout, ntaps=9, stride=1, pad_mode=0, up=0, C1=0, in_f32=False, res=None, out_f32=False,
-               geglu=False, out_scale=1.0, tile_cfg=-1, seed=0, atol=4e-3, split=False, gn=None, f8=False, xscale=1.0, wscale=1.0, rel=False):
+               geglu=False, out_scale=1.0, tile_cfg=-1, seed=0, atol=4e-3, split=False, gn=None, f8=False, xscale=1.0, wscale=1.0, rel=False, op=None):
     """gn = (eps, silu): GroupNorm(32)(+SiLU) of the input fused into the conv's operand staging (the ResBlock path).
     split = True: split-fp16 operands (precise mode) - the reference then sees the un-rounded fp32 operands.
     f8 = True: the residual terms of the split product on fp8 operands (F8 kernel: 3x3 stride 1, Cin % 32 == 0, tile cfg 0);
     False pins them to fp16 (option conv_f8 = 0) so that the 2e-5 checks of the fp16x3 arithmetic keep their meaning.
     xscale / wscale multiply the N(0,1) activations / the N(0, 1/fan_in) weights (range robustness of the fp8 residual operands);
-    rel = True compares max|d| / max|ref| with atol."""
+    rel = True compares max|d| / max|ref| with atol.
+    op: the operator call in place of eng.op_conv (same arguments, returns the NHWC output; gn_chain_suite passes the hook that also returns statistics)."""
     g = _g(seed)
     rnd = (lambda t: t) if split else h16
     x = torch.randn(N, Cin + C1, H, W, generator=g) * xscale
@@ -83,8 +84,8 @@ def check_conv(eng, dev, N, H, W, Cin, Cout, ntaps=9, stride=1, pad_mode=0, up=0
     prev = eng.lib.get_option("conv_f8")      # (the stand-alone operator packs its weights per call: the option is read there)
     eng.lib.set_option("conv_f8", 1 if f8 else 0)
     try:
-        out = eng.op_conv(x0, w.to(dev), b.to(dev), x1=x1, stride=stride, pad_mode=pad_mode, up=up, res=rr, geglu=geglu, out_f32=out_f32,
-                          out_scale=out_scale, tile_cfg=tile_cfg, split=split, gn=gn_arg)
+        out = (op or eng.op_conv)(x0, w.to(dev), b.to(dev), x1=x1, stride=stride, pad_mode=pad_mode, up=up, res=rr, geglu=geglu, out_f32=out_f32,
+                                  out_scale=out_scale, tile_cfg=tile_cfg, split=split, gn=gn_arg)
     finally:
         eng.lib.set_option("conv_f8", prev)
     got = nchw(out.float().cpu())
@@ -128,11 +129,8 @@ def check_conv_splitk(eng, dev, set_option):
     set_option(eng, "conv_splitk", -1)
 
 
-def check_conv_const_tiles(eng, dev, N=2, H=48, W=160, Cin=128, Cout=128, gn=True, res=True, seed=7):
-    """The F8 3x3 kernel on a piecewise-constant input with a class plane (what the VAE encoder sees for the trimap images): output tiles inside
-    one region are filled from the region's representative tile instead of being multiplied (k_misc.h cmask_*, ConvParams::tile_flag).  The
-    result has to be BIT-IDENTICAL to the same launch without the class plane - every output pixel of a region is the same chain of operations
-    on the same operands - and the launch counter proves that the skipping path ran."""
+def const_tiles_inputs(N=2, H=48, W=160, Cin=128, Cout=128, gn=True, res=True, seed=7):
+    """Inputs of check_conv_const_tiles: a piecewise-constant activation with its class plane -> (cls, x, w, b, gn_arg or None, residual or None)."""
     g = _g(seed)
     cls = torch.zeros(N, H, W, dtype=torch.uint8)
     # image 0: class 1 everywhere except a noisy blob in a corner and a class-2 band; image 1: nothing known (an "rgb" image)
@@ -152,6 +150,15 @@ def check_conv_const_tiles(eng, dev, N=2, H=48, W=160, Cin=128, Cout=128, gn=Tru
         r = torch.randn(N, H, W, Cout, generator=g)
         for c in (1, 2):
             r[cls == c] = rv[c]
+    return cls, x, w, b, gn_arg, r
+
+
+def check_conv_const_tiles(eng, dev, N=2, H=48, W=160, Cin=128, Cout=128, gn=True, res=True, seed=7):
+    """The F8 3x3 kernel on a piecewise-constant input with a class plane (what the VAE encoder sees for the trimap images): output tiles inside
+    one region are filled from the region's representative tile instead of being multiplied (k_misc.h cmask_*, ConvParams::tile_flag).  The
+    result has to be BIT-IDENTICAL to the same launch without the class plane - every output pixel of a region is the same chain of operations
+    on the same operands - and the launch counter proves that the skipping path ran."""
+    cls, x, w, b, gn_arg, r = const_tiles_inputs(N, H, W, Cin, Cout, gn, res, seed)
     kw = dict(tile_cfg=0, split=True, out_f32=True, gn=tuple(t.to(dev) if torch.is_tensor(t) else t for t in gn_arg) if gn else None,
               res=r.to(dev) if res else None)
     prev = eng.lib.get_option("conv_f8")
