@@ -22,6 +22,7 @@
 #include "k_foreground.h"
 #include "k_guided.h"
 #include "k_temporal.h"
+#include "k_motion.h"
 #include "k_roi.h"
 #include "k_canvas.h"
 #include "k_boxes.h"
@@ -2582,7 +2583,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -3498,11 +3499,8 @@ int sdm_refine_alpha_guided(sdm_ctx* e, const float* image, const float* alpha, 
 // ------------------------------------------------------------------------------------------------
 // temporal smoothing of the alpha, guided by the frames (k_temporal.h): the batch axis is time
 // ------------------------------------------------------------------------------------------------
-/* Nothing in the arena.  One launch, whatever the arguments. */
-int sdm_smooth_alpha_temporal(sdm_ctx* e, const float* image, const float* alpha, int B, int H, int W, int clip_len, int radius, int patch,
-                              float color_tolerance, float strength, float max_change, float* out, int ptr_kind, void* stream_arg) {
-  if (e) dev_use(e->device);
-  if (!e || !image || !alpha || !out) return SDM_ERR_INVALID;
+/* The argument limits that sdm_smooth_alpha_temporal and sdm_smooth_alpha_motion share. */
+static int ts_check(sdm_ctx* e, int B, int H, int W, int clip_len, int radius, int patch, float color_tolerance, float strength, float max_change) {
   if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: bad image size %dx%dx%d", B, H, W);
   if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
     SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: %dx%dx%d is too large (sides up to %d, %d pixels in all)", B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
@@ -3515,6 +3513,15 @@ int sdm_smooth_alpha_temporal(sdm_ctx* e, const float* image, const float* alpha
     SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: strength = %g must be a finite number in [0, 1]", (double)strength);
   if (!std::isfinite(max_change) || !(max_change >= 0.0f) || !(max_change <= 1.0f))
     SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: max_change = %g must be a finite number in [0, 1]", (double)max_change);
+  return 0;
+}
+
+/* Nothing in the arena.  One launch, whatever the arguments. */
+int sdm_smooth_alpha_temporal(sdm_ctx* e, const float* image, const float* alpha, int B, int H, int W, int clip_len, int radius, int patch,
+                              float color_tolerance, float strength, float max_change, float* out, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !alpha || !out) return SDM_ERR_INVALID;
+  if (int rc = ts_check(e, B, H, W, clip_len, radius, patch, color_tolerance, strength, max_change)) return rc;
   const size_t px = (size_t)B * H * W;
   IoSpan in[] = {{(void*)image, px * 12}, {(void*)alpha, px * 4}}, outs[] = {{out, px * 4}};
   const int L = clip_len ? clip_len : B;
@@ -3533,6 +3540,53 @@ int sdm_smooth_alpha_temporal(sdm_ctx* e, const float* image, const float* alpha
         SDM_TS_CASE(3, 0); SDM_TS_CASE(3, 1); SDM_TS_CASE(3, 2); SDM_TS_CASE(4, 0); SDM_TS_CASE(4, 1); SDM_TS_CASE(4, 2);
       }
 #undef SDM_TS_CASE
+      prof_end(e);
+    }
+    return 0;
+  });
+}
+
+/* The pixels of [lo - halo, lo + len + halo) that lie in [0, n), summed over the tiles lo = 0, len, 2 len, .. of n: what tsm_smooth_kernel's blocks fetch
+ * along one axis. */
+static double tsm_axis_px(int n, int len, int halo) {
+  double s = 0;
+  for (int lo = 0; lo < n; lo += len) s += std::min(n, lo + len + halo) - std::max(0, lo - halo);
+  return s;
+}
+
+/* The same filter along a block-matched displacement (k_motion.h).  Nothing in the arena.  One launch for search >= 1; search == 0 IS the call above. */
+int sdm_smooth_alpha_motion(sdm_ctx* e, const float* image, const float* alpha, int B, int H, int W, int clip_len, int radius, int patch, int search,
+                            float color_tolerance, float motion_penalty, float strength, float max_change, float* out, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !alpha || !out) return SDM_ERR_INVALID;
+  if (search < 0 || search > SDM_TSM_MAX_SEARCH) SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: search = %d outside 0 .. %d", search, SDM_TSM_MAX_SEARCH);
+  if (search == 0) return sdm_smooth_alpha_temporal(e, image, alpha, B, H, W, clip_len, radius, patch, color_tolerance, strength, max_change, out, ptr_kind, stream_arg);
+  if (int rc = ts_check(e, B, H, W, clip_len, radius, patch, color_tolerance, strength, max_change)) return rc;
+  if (!std::isfinite(motion_penalty) || !(motion_penalty >= 0.0f) || !(motion_penalty <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "smooth alpha: motion_penalty = %g must be a finite number in [0, 1]", (double)motion_penalty);
+  static_assert(SDM_TSM_S == SDM_TSM_MAX_SEARCH && SDM_TS_MAX_PATCH == 2, "k_motion.h sizes its LDS region for these");
+  const size_t px = (size_t)B * H * W;
+  IoSpan in[] = {{(void*)image, px * 12}, {(void*)alpha, px * 4}}, outs[] = {{out, px * 4}};
+  const int L = clip_len ? clip_len : B;
+  const float tau2 = color_tolerance * color_tolerance;
+  const float pt = motion_penalty * tau2;
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_img = (const float*)in[0].p; const float* d_alpha = (const float*)in[1].p; float* d_out = (float*)outs[0].p;
+    if (!e->dry) {
+      const int vec = W % 4 == 0 && aligned16(d_img) && aligned16(d_alpha) ? 1 : 0;
+      const int tw = tsm_tile_w(patch);
+      const dim3 grid((unsigned)(B * sdm_cdiv(H, SDM_TSM_TH) * sdm_cdiv(W, tw))), blk(256);
+      // bytes: every block fetches its target region once and a larger region of each neighbour of its frame (16 bytes per pixel), and writes its tile
+      double pairs = 0;
+      for (int t = 0; t < B; ++t) pairs += std::min(t + radius, std::min(B, (t / L) * L + L) - 1) - std::max(t - radius, (t / L) * L);
+      const double bytes = 16.0 * (B * tsm_axis_px(H, SDM_TSM_TH, patch) * tsm_axis_px(W, tw, patch) +
+                                   pairs * tsm_axis_px(H, SDM_TSM_TH, patch + search) * tsm_axis_px(W, tw, patch + search)) + 4.0 * (double)px;
+      prof_begin(e, "tsm_smooth", 0, bytes);
+      count_kernel("tsm_smooth");
+#define SDM_TSM_CASE(P) \
+  case P: SDM_LAUNCH((tsm_smooth_kernel<P>), grid, blk, 0, e->stream, d_img, d_alpha, B, H, W, L, radius, search, tau2, pt, strength, max_change, vec, d_out); break
+      switch (patch) { SDM_TSM_CASE(0); SDM_TSM_CASE(1); SDM_TSM_CASE(2); }
+#undef SDM_TSM_CASE
       prof_end(e);
     }
     return 0;

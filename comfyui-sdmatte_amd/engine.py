@@ -83,7 +83,7 @@ EXPORTS = [
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
-    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal",
+    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_stats", "sdm_op_gn_partials", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias", "sdm_debug_patch_token_map", "sdm_op_groupnorm_p3", "sdm_op_gemm_p3_tokens", "sdm_op_mask_bias_tokens", "sdm_op_active_tiles",
@@ -132,6 +132,7 @@ class Bindings:
             "sdm_offset_mask": (i32, [vp, vp, i32, i32, i32, f32, f32, f32, vp, i32, vp]),
             "sdm_outline": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, f32, f32, vp, f32, vp, vp, i32, vp]),
             "sdm_smooth_alpha_temporal": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, i32, vp]),
+            "sdm_smooth_alpha_motion": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
             "sdm_resident_bytes": (i64, [vp]),
@@ -958,6 +959,47 @@ class Engine:
         stream = self._check_io("smooth_alpha_temporal", image_bhwc, alpha_bhw, out)
         self._check(self.lib.sdm_smooth_alpha_temporal(self.h, _ptr(image_bhwc), _ptr(alpha_bhw), B, H, W, clip_len, radius, patch, color_tolerance,
                                                        strength, max_change, _ptr(out), self._kind(image_bhwc), stream), "sdm_smooth_alpha_temporal")
+        if sync:
+            self.synchronize()
+        return out
+
+    # SDM_TSM_* (include/sdmatte.h)
+    TSM_DEFAULTS = dict(TS_DEFAULTS, search=4, motion_penalty=0.02)
+    TSM_MAX_SEARCH = 8
+
+    @classmethod
+    def _check_tsm_params(cls, what, B, radius, patch, search, color_tolerance, motion_penalty, strength, max_change, clip_len):
+        """The argument limits of sdm_smooth_alpha_motion; returns the values that cross the C ABI (the floats rounded to fp32)."""
+        if isinstance(search, str) or int(search) != search or not 0 <= int(search) <= cls.TSM_MAX_SEARCH:
+            raise ValueError(f"{what}: search must be an integer in 0 .. {cls.TSM_MAX_SEARCH}, got {search!r}")
+        radius, patch, color_tolerance, strength, max_change, clip_len = cls._check_ts_params(what, B, radius, patch, color_tolerance, strength, max_change,
+                                                                                              clip_len)
+        motion_penalty = cls._check_f32_range(what, "motion_penalty", motion_penalty, 0, 1) if int(search) else 0.0
+        return radius, patch, int(search), color_tolerance, motion_penalty, strength, max_change, clip_len
+
+    def smooth_alpha_motion(self, image_bhwc, alpha_bhw, radius=2, patch=1, search=4, color_tolerance=0.1, motion_penalty=0.02, strength=1.0, max_change=1.0,
+                            clip_len=0, sync=True):
+        """`smooth_alpha_temporal` along the motion (sdm_smooth_alpha_motion, defined in include/sdmatte.h): every pixel looks for the patch around it in the
+        neighbouring frame among the integer displacements within `search` (the cost is the patch distance plus `motion_penalty` * color_tolerance^2 per
+        squared pixel of displacement) and is filtered with the alpha found there, so the soft edge of a moving subject is smoothed too.  search = 0 is
+        `smooth_alpha_temporal`, bit for bit.  Returns fp32 [B,H,W] in [0,1] on the inputs' device.  One kernel launch.  Needs no loaded weights.
+        `sdmatte_nodes.temporal_smooth_alpha_motion` is the same function in torch."""
+        if image_bhwc.dim() != 4 or image_bhwc.shape[-1] != 3 or image_bhwc.numel() == 0:
+            raise ValueError(f"smooth_alpha_motion: image must be a non-empty [B,H,W,3], got {tuple(image_bhwc.shape)}")
+        B, H, W, _ = (int(v) for v in image_bhwc.shape)
+        if tuple(alpha_bhw.shape) != (B, H, W):
+            raise ValueError(f"smooth_alpha_motion: alpha must be [B,H,W] = {(B, H, W)}, got {tuple(alpha_bhw.shape)}")
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"smooth_alpha_motion: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        radius, patch, search, color_tolerance, motion_penalty, strength, max_change, clip_len = self._check_tsm_params(
+            "smooth_alpha_motion", B, radius, patch, search, color_tolerance, motion_penalty, strength, max_change, clip_len)
+        image_bhwc = image_bhwc.float().contiguous()
+        alpha_bhw = alpha_bhw.float().contiguous()
+        out = torch.empty(B, H, W, dtype=torch.float32, device=image_bhwc.device)
+        stream = self._check_io("smooth_alpha_motion", image_bhwc, alpha_bhw, out)
+        self._check(self.lib.sdm_smooth_alpha_motion(self.h, _ptr(image_bhwc), _ptr(alpha_bhw), B, H, W, clip_len, radius, patch, search, color_tolerance,
+                                                     motion_penalty, strength, max_change, _ptr(out), self._kind(image_bhwc), stream),
+                    "sdm_smooth_alpha_motion")
         if sync:
             self.synchronize()
         return out

@@ -305,6 +305,13 @@ class MultiGpuEngine:
         return self.engines[0].smooth_alpha_temporal(self._to_host(image_bhwc), self._to_host(alpha_bhw), radius, patch, color_tolerance, strength,
                                                      max_change, clip_len)
 
+    def smooth_alpha_motion(self, image_bhwc, alpha_bhw, radius=2, patch=1, search=4, color_tolerance=0.1, motion_penalty=0.02, strength=1.0,
+                            max_change=1.0, clip_len=0):
+        """The alpha filtered along time and along the motion (no model involved): on the first engine, as `smooth_alpha_temporal`; inputs on the host or
+        any device -> alpha [B,H,W] on the HOST."""
+        return self.engines[0].smooth_alpha_motion(self._to_host(image_bhwc), self._to_host(alpha_bhw), radius, patch, search, color_tolerance,
+                                                   motion_penalty, strength, max_change, clip_len)
+
     def apply_matte_mask(self, image_bhwc, mask_bhw, S, is_transparent, output_mode, mask_refine, trimap_constraint, threshold=0.5, erode_px=10,
                          dilate_px=10):
         """`apply_matte_node` with the trimap made from the mask on each GPU (images are independent: so are their trimaps); returns

@@ -27,6 +27,8 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
     restatement of its placement and `compose_canvas` its torch restatement;
   * and one registered only with SDMATTE_VIDEO_NODE=1: `SDMatteTemporalSmooth` takes the batch as a clip and filters the alpha along time, guided by
     the frames themselves, in one kernel launch; `temporal_smooth_alpha` below is its torch restatement;
+  * and one registered only with SDMATTE_MOTION_NODE=1: `SDMatteTemporalSmoothMotion` is the same filter along a block-matched displacement, so the
+    soft edge of a moving subject is smoothed too; `temporal_smooth_alpha_motion` below is its torch restatement;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -928,6 +930,72 @@ def temporal_smooth_alpha(image, alpha, radius=2, patch=1, color_tolerance=0.1, 
     return (a + torch.minimum(torch.maximum(num / den - a, -limit), limit)).clamp(0.0, 1.0)
 
 
+def temporal_smooth_alpha_motion(image, alpha, radius=2, patch=1, search=4, color_tolerance=0.1, motion_penalty=0.02, strength=1.0, max_change=1.0,
+                                 clip_len=0):
+    """`Engine.smooth_alpha_motion` in torch fp32, on the tensors' own device (the block-matched temporal filter defined in include/sdmatte.h): the alpha
+    [B,H,W] of B consecutive frames [B,H,W,3] -> fp32 [B,H,W] in [0,1].  Equal to the kernel to fp32 rounding wherever the best two candidates are not
+    within rounding of each other; the identities of the header hold exactly here too.  search = 0 is `temporal_smooth_alpha`.  One pass over padded
+    tensors per offset k and displacement d, the candidates in the order of the choice rule (dy^2 + dx^2, dy, dx), so 'strictly smaller cost' keeps
+    the lexicographic minimum."""
+    import torch.nn.functional as F
+    from .engine import Engine
+    if image.dim() != 4 or image.shape[-1] != 3 or image.numel() == 0:
+        raise ValueError(f"temporal_smooth_alpha_motion: image must be a non-empty [B,H,W,3], got {tuple(image.shape)}")
+    if tuple(alpha.shape) != tuple(image.shape[:3]):
+        raise ValueError(f"temporal_smooth_alpha_motion: alpha must be [B,H,W] = {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+    B, H, W = (int(v) for v in image.shape[:3])
+    radius, patch, search, color_tolerance, motion_penalty, strength, max_change, clip_len = Engine._check_tsm_params(
+        "temporal_smooth_alpha_motion", B, radius, patch, search, color_tolerance, motion_penalty, strength, max_change, clip_len)
+    if search == 0:
+        return temporal_smooth_alpha(image, alpha, radius, patch, color_tolerance, strength, max_change, clip_len)
+    dev = image.device
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
+    img = image.detach().float()
+    a = torch.nan_to_num(alpha.detach().float(), nan=0.0).clamp(0.0, 1.0)
+    tau2 = f32(color_tolerance) * f32(color_tolerance)
+    pt = f32(motion_penalty) * tau2
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    S = search
+    box = lambda v: F.avg_pool2d(v.unsqueeze(1), 2 * patch + 1, 1, patch, divisor_override=1).squeeze(1) if patch else v      # sums; beyond the border: 0
+    inside = F.pad(torch.ones(1, H, W, device=dev), (S, S, S, S))                 # 1 where a pixel of the padded neighbour exists
+    order = sorted(((dy * dy + dx * dx, dy, dx) for dy in range(-S, S + 1) for dx in range(-S, S + 1)))
+    frames = torch.arange(B, device=dev)
+    clip = frames // (clip_len if clip_len else B)
+    num, den = a.clone(), torch.ones_like(a)
+    for k in [-j for j in range(1, radius + 1)] + list(range(1, radius + 1)):
+        t = frames[(frames + k >= 0) & (frames + k < B)]
+        t = t[clip[t] == clip[t + k]]
+        if t.numel() == 0:
+            continue
+        It = img[t]
+        Is = F.pad(img[t + k], (0, 0, S, S, S, S))
+        As = F.pad(a[t + k], (S, S, S, S))
+        best_c = torch.zeros(t.numel(), H, W, device=dev)
+        best_d, best_a = torch.zeros_like(best_c), torch.zeros_like(best_c)
+        got = torch.zeros_like(best_c, dtype=torch.bool)
+        for dd, dy, dx in order:
+            ys, xs = slice(S + dy, S + dy + H), slice(S + dx, S + dx + W)
+            ok = inside[:, ys, xs] > 0                                            # q + d exists (q does: it is a pixel of the frame)
+            diff = Is[:, ys, xs] - It
+            e = torch.where(ok, (diff * diff).sum(-1), zero)
+            n = box(ok.float())
+            D = box(e) / (3.0 * n)
+            C = D + pt * float(dd)
+            take = ok & (C == C) & (~got | (C < best_c))
+            best_c = torch.where(take, C, best_c)
+            best_d = torch.where(take, D, best_d)
+            best_a = torch.where(take, As[:, ys, xs], best_a)
+            got = got | take
+        u = 1.0 - best_d / tau2
+        u = torch.where(u > 0, u, zero)
+        ck = f32(strength) * (1.0 - f32(float(abs(k))) / float(radius + 1))
+        w = torch.where(got, ck * (u * u), zero)
+        num[t] += w * best_a
+        den[t] += w
+    limit = f32(max_change)
+    return (a + torch.minimum(torch.maximum(num / den - a, -limit), limit)).clamp(0.0, 1.0)
+
+
 class SDMatteApply:
 
     @classmethod
@@ -1444,12 +1512,57 @@ class SDMatteTemporalSmooth:
         return (_trimap_engine(_torch_device()).smooth_alpha_temporal(*args), )
 
 
+class SDMatteTemporalSmoothMotion:
+    """Frames + their alphas -> the alphas filtered along time AND along the motion on the GPU: the batch is a clip.  Every pixel looks for the patch around
+    it in the neighbouring frames (integer displacements up to `search`) and is averaged with the alpha found there, so the soft edge and the hair of a
+    moving subject stop shimmering too; cuts still keep their own alpha.  One kernel launch, no optical flow.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE", {"tooltip": "the frames of the clip, in order (the batch axis is time)"}),
+                             "alpha": ("MASK", {"tooltip": "the alpha matte of every frame"})},
+                "optional": {"radius": ("INT", {"default": 2, "min": 1, "max": 4, "tooltip": "frames on either side that may contribute"}),
+                             "patch": ("INT", {"default": 1, "min": 0, "max": 2,
+                                               "tooltip": "the picture is compared over a (2 patch + 1)^2 neighbourhood of the pixel"}),
+                             "search": ("INT", {"default": 4, "min": 0, "max": 8,
+                                                "tooltip": "the largest displacement, in pixels per frame step, that is looked for (0: no motion search)"}),
+                             "color_tolerance": ("FLOAT", {"default": 0.1, "min": 0.001, "max": 1.0, "step": 0.005,
+                                                           "tooltip": "RMS colour change at which a neighbouring frame stops contributing"}),
+                             "motion_penalty": ("FLOAT", {"default": 0.02, "min": 0.0, "max": 1.0, "step": 0.005,
+                                                          "tooltip": "what a squared pixel of displacement costs, in units of color_tolerance squared"}),
+                             "strength": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.05, "tooltip": "0 returns the alpha unchanged"}),
+                             "max_change": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.01,
+                                                      "tooltip": "the most a pixel's alpha may move away from its own frame's value"}),
+                             "clip_len": ("INT", {"default": 0, "min": 0, "max": 1 << 20,
+                                                  "tooltip": "0: the batch is one clip; otherwise independent clips of this many frames"}),
+                             "force_cpu": ("BOOLEAN", {"default": False, "tooltip": "evaluate the torch restatement on the CPU instead of the GPU call"})}}
+
+    RETURN_TYPES = ("MASK", )
+    RETURN_NAMES = ("alpha", )
+    FUNCTION = "smooth"
+    CATEGORY = "Matting/SDMatte"
+
+    def smooth(self, image, alpha, radius=2, patch=1, search=4, color_tolerance=0.1, motion_penalty=0.02, strength=1.0, max_change=1.0, clip_len=0,
+               force_cpu=False):
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        if alpha.dim() == 2:
+            alpha = alpha.unsqueeze(0)
+        if tuple(alpha.shape) != tuple(image.shape[:3]):
+            raise ValueError(f"[SDMatte] alpha must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+        args = (image.detach().cpu(), alpha.detach().cpu(), int(radius), int(patch), int(search), float(color_tolerance), float(motion_penalty),
+                float(strength), float(max_change), int(clip_len))
+        if force_cpu:      # an explicit request, never a silent substitute: the same function in torch
+            return (temporal_smooth_alpha_motion(*args), )
+        return (_trimap_engine(_torch_device()).smooth_alpha_motion(*args), )
+
+
 def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False, canvas: bool = False,
-                  subjects: bool = False, edge: bool = False, video: bool = False):
+                  subjects: bool = False, edge: bool = False, video: bool = False, motion: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
     node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`, plus the subject-box node when `roi`,
     plus the canvas node when `canvas`, plus the box-per-subject node when `subjects`, plus the two
-    distance-field nodes (mask offset, outline) when `edge`, plus the temporal smoothing node when `video`."""
+    distance-field nodes (mask offset, outline) when `edge`, plus the temporal smoothing node when `video`, plus the motion-compensated one when `motion`."""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
@@ -1479,10 +1592,13 @@ def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, c
     if video:
         classes["SDMatteTemporalSmooth"] = SDMatteTemporalSmooth
         names["SDMatteTemporalSmooth"] = "SDMatte Temporal Smooth"
+    if motion:
+        classes["SDMatteTemporalSmoothMotion"] = SDMatteTemporalSmoothMotion
+        names["SDMatteTemporalSmoothMotion"] = "SDMatte Temporal Smooth (Motion)"
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1), like the multi-GPU fan-out
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
 NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
@@ -1492,4 +1608,5 @@ NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("
                                                                 os.environ.get("SDMATTE_CANVAS_NODE") == "1",
                                                                 os.environ.get("SDMATTE_SUBJECTS_NODE") == "1",
                                                                 os.environ.get("SDMATTE_EDGE_NODES") == "1",
-                                                                os.environ.get("SDMATTE_VIDEO_NODE") == "1")
+                                                                os.environ.get("SDMATTE_VIDEO_NODE") == "1",
+                                                                os.environ.get("SDMATTE_MOTION_NODE") == "1")

@@ -483,6 +483,42 @@ int sdm_outline(sdm_ctx* ctx, const float* fg_bhw3, const float* alpha_bhw, int 
 int sdm_smooth_alpha_temporal(sdm_ctx* ctx, const float* image_bhwc, const float* alpha_bhw, int B, int H, int W, int clip_len, int radius, int patch,
                               float color_tolerance, float strength, float max_change, float* out_bhw, int ptr_kind, void* stream);
 
+/* The same filter along the motion (beyond the reference): sdm_smooth_alpha_temporal compares a pixel with the SAME pixel of the neighbouring frames, so
+ * where the subject moves - its soft edge, its hair: the pixels that shimmer most - the weight is 0 and nothing is smoothed.  Here every pixel first looks
+ * for the patch around it in the neighbouring frame, among the integer displacements within `search`, and is filtered with the alpha found there.  No
+ * optical flow, no weights: a search with the patch distance of the call above.  Unchanged from that call: the batch axis is time; the sanitising (a), the
+ * clips, tau2 = color_tolerance * color_tolerance, the filter and the limit; everything fp32, true fp32 divisions, no FMA contraction.  New, per target
+ * frame t, neighbour s = t + k (same clip, 0 < |k| <= radius) and pixel p:
+ *   candidates d = (dy, dx) with |dy|, |dx| <= search for which p + d lies in the frame
+ *   distance   e_d(q) = sum over the 3 channels of (I_s(q + d, c) - I_t(q, c))^2;  D_d(p) = (sum of e_d(q) over the q within Chebyshev distance `patch` of p
+ *              for which q and q + d both exist) / (3 * n_d), n_d the number of those q (n_d >= 1: q = p counts).  Pixels beyond the border do not exist.
+ *   cost       C_d = D_d + pt * (float)(dy*dy + dx*dx), pt = motion_penalty * tau2 (one fp32 product)
+ *   choice     a candidate is eligible iff C_d == C_d (not NaN); d* is the eligible candidate with the lexicographically smallest
+ *              (C_d, dy*dy + dx*dx, dy, dx).  If none is eligible the pair contributes nothing.
+ *   weight     u = 1 - D_d* / tau2 (the distance, not the cost); u = u > 0 ? u : 0; w_k = (strength * (1 - |k| / (radius + 1))) * (u*u); the sample is
+ *              a_s(p + d*)
+ *   filter     f = (a_t + sum_k w_k * a_s(p + d*_k)) / (1 + sum_k w_k), in the order k = -1 .. -radius, then +1 .. +radius; out as in the call above
+ * The order in which the terms of a patch are summed is not part of the contract; the choice rule is.
+ * search == 0 is accepted and IS sdm_smooth_alpha_temporal: the same launch (`ts_smooth`) and the same bits; motion_penalty is not looked at.
+ * These hold bit for bit:
+ *   out equals a when strength == 0, or max_change == 0, or B == 1, or clip_len == 1, or every D_d of every candidate is >= tau2;
+ *   a clip with a hard cut gives the bits of its two shots, if every pixel of one shot differs by >= color_tolerance per channel from every pixel of the
+ *   other (then every D_d across the cut is >= tau2, whatever the displacement);
+ *   a call with clip_len = L gives the bits of one call per clip;
+ *   two calls, host and device pointers, aligned and unaligned pointers all give the same bits.
+ * sdmatte_nodes.temporal_smooth_alpha_motion is the same function in torch (equal to fp32 rounding wherever the choice is not a near-tie).
+ * Limits: search in 0 .. SDM_TSM_MAX_SEARCH; motion_penalty finite in [0, 1]; every other limit is that of sdm_smooth_alpha_temporal: SDM_ERR_INVALID
+ * otherwise, with a message that names the argument, and then nothing is queued or written.  Stream contract and pointer kinds as sdm_make_trimap;
+ * sdm_last_forward_ms covers the launch.  Needs no weights.  For search >= 1 ONE kernel launch (csrc/k_motion.h), `tsm_smooth` in sdm_kernel_counts and
+ * the per-launch profile, whatever the arguments and the content; no host readback.  The call keeps nothing in the arena; host pointers go through the
+ * I/O staging. */
+#define SDM_TSM_MAX_SEARCH 8
+#define SDM_TSM_SEARCH 4
+#define SDM_TSM_MOTION_PENALTY 0.02f
+int sdm_smooth_alpha_motion(sdm_ctx* ctx, const float* image_bhwc, const float* alpha_bhw, int B, int H, int W, int clip_len, int radius, int patch,
+                            int search, float color_tolerance, float motion_penalty, float strength, float max_change, float* out_bhw,
+                            int ptr_kind, void* stream);
+
 /* Memory the engine holds outside any framework allocator: packed weights + activation arena (sized by the largest batch /
  * resolution seen) + I/O staging.  sdm_release_memory frees everything but the weights (the next forward re-allocates). */
 int64_t sdm_resident_bytes(sdm_ctx* ctx);
@@ -508,7 +544,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal: their launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal / sdm_smooth_alpha_motion: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
