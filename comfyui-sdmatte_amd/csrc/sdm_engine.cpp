@@ -23,6 +23,7 @@
 #include "k_guided.h"
 #include "k_temporal.h"
 #include "k_motion.h"
+#include "k_defocus.h"
 #include "k_roi.h"
 #include "k_canvas.h"
 #include "k_boxes.h"
@@ -2583,7 +2584,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -3589,6 +3590,65 @@ int sdm_smooth_alpha_motion(sdm_ctx* e, const float* image, const float* alpha, 
 #undef SDM_TSM_CASE
       prof_end(e);
     }
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// the subject over its own background out of focus (k_defocus.h)
+// ------------------------------------------------------------------------------------------------
+/* The prefix plane (16 bytes per pixel) lives in the activation arena.  Two launches, whatever the arguments. */
+int sdm_defocus_background(sdm_ctx* e, const float* image, const float* alpha, const float* fg, const float* bg, int B, int H, int W, int radius_px,
+                           float highlight_gain, float highlight_threshold, float* out, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !alpha || !out) return SDM_ERR_INVALID;
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "defocus background: bad image size %dx%dx%d", B, H, W);
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "defocus background: %dx%dx%d is too large (sides up to %d, %d pixels in all)", B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  if (radius_px < 1 || radius_px > SDM_DEFOCUS_MAX_RADIUS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "defocus background: radius_px = %d outside 1 .. %d", radius_px, SDM_DEFOCUS_MAX_RADIUS);
+  if (!std::isfinite(highlight_gain) || !(highlight_gain >= 0.0f) || !(highlight_gain <= (float)SDM_DEFOCUS_MAX_GAIN))
+    SDM_FAIL(e, SDM_ERR_INVALID, "defocus background: highlight_gain = %g must be a finite number in [0, %d]", (double)highlight_gain, SDM_DEFOCUS_MAX_GAIN);
+  if (!std::isfinite(highlight_threshold) || !(highlight_threshold >= 0.0f) || !(highlight_threshold <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "defocus background: highlight_threshold = %g must be a finite number in [0, 1]", (double)highlight_threshold);
+  static_assert(SDM_DOF_R == SDM_DEFOCUS_MAX_RADIUS && 2 * SDM_DOF_R + 1 < SDM_DOF_SEG && SDM_DOF_FLOOR == SDM_DEFOCUS_FLOOR, "k_defocus.h is sized for these");
+  DofDisc disc;
+  memset(&disc, 0, sizeof(disc));
+  disc.r = radius_px;
+  for (int dy = 0, h = radius_px; dy <= radius_px; ++dy) {      // the largest h with h h <= R R - dy dy, in integers
+    while (h * h > radius_px * radius_px - dy * dy) --h;
+    disc.hw[dy] = (unsigned char)h;
+  }
+  const size_t px = (size_t)B * H * W;
+  // (an absent plane is an empty span behind a valid pointer: the staging copies 0 bytes of it)
+  IoSpan in[] = {{(void*)image, px * 12}, {(void*)alpha, px * 4}, {(void*)(fg ? fg : image), fg ? px * 12 : 0}, {(void*)(bg ? bg : image), bg ? px * 12 : 0}};
+  IoSpan outs[] = {{out, px * 12}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_img = (const float*)in[0].p; const float* d_alpha = (const float*)in[1].p; float* d_out = (float*)outs[0].p;
+    const float* d_F = fg ? (const float*)in[2].p : d_img; const float* d_C = bg ? (const float*)in[3].p : d_img;
+    T plane = talloc(e, B, H, W, 4, 1);
+    if (!e->dry) {
+      const int vec = W % 4 == 0 && aligned16(d_C) && aligned16(d_alpha) ? 1 : 0;
+      const long long units = (long long)B * H * sdm_cdiv(W, SDM_DOF_SEG);
+      prof_begin(e, "dof_prefix", 0, (double)px * 32);
+      count_kernel("dof_prefix");
+      SDM_LAUNCH(dof_prefix_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, e->stream, d_C, d_alpha, B, H, W, highlight_gain, highlight_threshold, vec,
+                 (f32x4*)plane.p);
+      prof_end(e);
+      // bytes: every tile fetches its window of the prefix plane (rows and columns within radius_px of it, 16 bytes per pixel); the epilogue reads C, F
+      // and the alpha and writes the result
+      double win_px = 0;
+      for (int y0 = 0; y0 < H; y0 += SDM_DOF_TH) {
+        const double rows = std::min(H - 1, y0 + SDM_DOF_TH - 1 + radius_px) - std::max(0, y0 - radius_px) + 1;
+        for (int x0 = 0; x0 < W; x0 += SDM_DOF_TW) win_px += rows * (std::min(W - 1, x0 + SDM_DOF_TW - 1 + radius_px) - std::max(0, x0 - radius_px - 1) + 1);
+      }
+      prof_begin(e, "dof_gather", 0, 16.0 * B * win_px + (double)px * (4 + 12 + (d_F != d_C ? 12 : 0) + 12));
+      count_kernel("dof_gather");
+      SDM_LAUNCH(dof_gather_kernel, dim3((unsigned)(B * sdm_cdiv(H, SDM_DOF_TH) * sdm_cdiv(W, SDM_DOF_TW))), dim3(256), 0, e->stream, (const f32x4*)plane.p, d_C, d_F,
+                 d_alpha, B, H, W, disc, d_out);
+      prof_end(e);
+    }
+    tfree(e, plane);
     return 0;
   });
 }

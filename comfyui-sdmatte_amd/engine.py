@@ -83,7 +83,7 @@ EXPORTS = [
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
-    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion",
+    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_stats", "sdm_op_gn_partials", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias", "sdm_debug_patch_token_map", "sdm_op_groupnorm_p3", "sdm_op_gemm_p3_tokens", "sdm_op_mask_bias_tokens", "sdm_op_active_tiles",
@@ -133,6 +133,7 @@ class Bindings:
             "sdm_outline": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, f32, f32, vp, f32, vp, vp, i32, vp]),
             "sdm_smooth_alpha_temporal": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, i32, vp]),
             "sdm_smooth_alpha_motion": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, vp, i32, vp]),
+            "sdm_defocus_background": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
             "sdm_resident_bytes": (i64, [vp]),
@@ -1000,6 +1001,50 @@ class Engine:
         self._check(self.lib.sdm_smooth_alpha_motion(self.h, _ptr(image_bhwc), _ptr(alpha_bhw), B, H, W, clip_len, radius, patch, search, color_tolerance,
                                                      motion_penalty, strength, max_change, _ptr(out), self._kind(image_bhwc), stream),
                     "sdm_smooth_alpha_motion")
+        if sync:
+            self.synchronize()
+        return out
+
+    # SDM_DEFOCUS_* (include/sdmatte.h)
+    DEFOCUS_DEFAULTS = {"radius_px": 16, "highlight_gain": 0.0, "highlight_threshold": 0.8}
+    DEFOCUS_MAX_RADIUS = 64
+    DEFOCUS_MAX_GAIN = 64
+
+    @classmethod
+    def _check_defocus_params(cls, what, radius_px, highlight_gain, highlight_threshold):
+        """The argument limits of sdm_defocus_background; returns the values that cross the C ABI (the floats rounded to fp32)."""
+        if isinstance(radius_px, str) or int(radius_px) != radius_px or not 1 <= int(radius_px) <= cls.DEFOCUS_MAX_RADIUS:
+            raise ValueError(f"{what}: radius_px must be an integer in 1 .. {cls.DEFOCUS_MAX_RADIUS}, got {radius_px!r}")
+        highlight_gain = cls._check_f32_range(what, "highlight_gain", highlight_gain, 0, cls.DEFOCUS_MAX_GAIN)
+        highlight_threshold = cls._check_f32_range(what, "highlight_threshold", highlight_threshold, 0, 1)
+        return int(radius_px), highlight_gain, highlight_threshold
+
+    def defocus_background(self, image_bhwc, alpha_bhw, fg=None, bg=None, radius_px=16, highlight_gain=0.0, highlight_threshold=0.8, sync=True):
+        """The subject over its own background out of focus (sdm_defocus_background, defined in include/sdmatte.h): the background colours (`bg` if given,
+        else the image) are blurred by a disc of `radius_px` pixels with the weight 1 - alpha, so the blur is normalised and does not see the subject (no
+        halo), highlights above `highlight_threshold` weigh `highlight_gain` times their excess more, and the foreground colours (`fg` if given, else the
+        image) are composed over the result with the alpha.  `fg` and `bg` are the two planes of `estimate_foreground`.  Returns fp32 [B,H,W,3] on the
+        inputs' device.  Two kernel launches.  Needs no loaded weights.  `sdmatte_nodes.defocus_background` is the same function in torch, equal to fp32
+        rounding."""
+        if image_bhwc.dim() != 4 or image_bhwc.shape[-1] != 3 or image_bhwc.numel() == 0:
+            raise ValueError(f"defocus_background: image must be a non-empty [B,H,W,3], got {tuple(image_bhwc.shape)}")
+        B, H, W, _ = (int(v) for v in image_bhwc.shape)
+        if tuple(alpha_bhw.shape) != (B, H, W):
+            raise ValueError(f"defocus_background: alpha must be [B,H,W] = {(B, H, W)}, got {tuple(alpha_bhw.shape)}")
+        for name, t in (("fg", fg), ("bg", bg)):
+            if t is not None and tuple(t.shape) != (B, H, W, 3):
+                raise ValueError(f"defocus_background: {name} must be [B,H,W,3] = {(B, H, W, 3)}, got {tuple(t.shape)}")
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"defocus_background: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        radius_px, highlight_gain, highlight_threshold = self._check_defocus_params("defocus_background", radius_px, highlight_gain, highlight_threshold)
+        image_bhwc = image_bhwc.float().contiguous()
+        alpha_bhw = alpha_bhw.float().contiguous()
+        fg = fg.float().contiguous() if fg is not None else None
+        bg = bg.float().contiguous() if bg is not None else None
+        out = torch.empty(B, H, W, 3, dtype=torch.float32, device=image_bhwc.device)
+        stream = self._check_io("defocus_background", image_bhwc, alpha_bhw, fg, bg, out)
+        self._check(self.lib.sdm_defocus_background(self.h, _ptr(image_bhwc), _ptr(alpha_bhw), _ptr(fg), _ptr(bg), B, H, W, radius_px, highlight_gain,
+                                                    highlight_threshold, _ptr(out), self._kind(image_bhwc), stream), "sdm_defocus_background")
         if sync:
             self.synchronize()
         return out

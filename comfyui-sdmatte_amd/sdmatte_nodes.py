@@ -29,6 +29,8 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
     the frames themselves, in one kernel launch; `temporal_smooth_alpha` below is its torch restatement;
   * and one registered only with SDMATTE_MOTION_NODE=1: `SDMatteTemporalSmoothMotion` is the same filter along a block-matched displacement, so the
     soft edge of a moving subject is smoothed too; `temporal_smooth_alpha_motion` below is its torch restatement;
+  * and one registered only with SDMATTE_DEFOCUS_NODE=1: `SDMatteDefocus` puts the subject back over its own background out of focus (a normalised
+    disc blur that does not see the subject, so no halo), in two kernel launches; `defocus_background` below is its torch restatement;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -996,6 +998,38 @@ def temporal_smooth_alpha_motion(image, alpha, radius=2, patch=1, search=4, colo
     return (a + torch.minimum(torch.maximum(num / den - a, -limit), limit)).clamp(0.0, 1.0)
 
 
+
+def defocus_background(image, alpha, fg=None, bg=None, radius_px=16, highlight_gain=0.0, highlight_threshold=0.8):
+    """`Engine.defocus_background` in torch fp32, on the tensors' own device (the function defined in include/sdmatte.h): image [B,H,W,3], alpha
+    [B,H,W], optional foreground / background colours [B,H,W,3] -> fp32 [B,H,W,3], the subject over its own background out of focus.  Equal to the
+    kernels to fp32 rounding; the identities of the header hold here too (a sum of zeros is zero in a convolution as well).  One depthwise convolution
+    of the four planes (w C.r, w C.g, w C.b, w) with the 0 / 1 kernel of the closed disc, zero padding: pixels beyond the border do not exist."""
+    import torch.nn.functional as F
+    from .engine import Engine
+    if image.dim() != 4 or image.shape[-1] != 3 or image.numel() == 0:
+        raise ValueError(f"defocus_background: image must be a non-empty [B,H,W,3], got {tuple(image.shape)}")
+    if tuple(alpha.shape) != tuple(image.shape[:3]):
+        raise ValueError(f"defocus_background: alpha must be [B,H,W] = {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+    for name, t in (("fg", fg), ("bg", bg)):
+        if t is not None and tuple(t.shape) != tuple(image.shape):
+            raise ValueError(f"defocus_background: {name} must be [B,H,W,3] = {tuple(image.shape)}, got {tuple(t.shape)}")
+    R, gain, threshold = Engine._check_defocus_params("defocus_background", radius_px, highlight_gain, highlight_threshold)
+    dev = image.device
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
+    img = image.detach().float()
+    a = torch.nan_to_num(alpha.detach().float(), nan=0.0).clamp(0.0, 1.0)
+    C = bg.detach().float() if bg is not None else img
+    Fg = fg.detach().float() if fg is not None else img
+    Y = ((C[..., 0] + C[..., 1]) + C[..., 2]) / 3.0
+    w = (1.0 - a) * (1.0 + f32(gain) * (Y - f32(threshold)).clamp(min=0.0))
+    planes = torch.cat([w.unsqueeze(-1) * C, w.unsqueeze(-1)], -1).permute(0, 3, 1, 2).contiguous()
+    d = torch.arange(-R, R + 1, device=dev)
+    disc = ((d.view(-1, 1) ** 2 + d.view(1, -1) ** 2) <= R * R).float()
+    sums = F.conv2d(planes, disc.expand(4, 1, 2 * R + 1, 2 * R + 1).contiguous(), padding=R, groups=4).permute(0, 2, 3, 1)
+    e = f32(2.0 ** -10)      # SDM_DEFOCUS_FLOOR
+    blur = (sums[..., :3] + e * C) / (sums[..., 3:].clamp(min=0.0) + e)
+    return a.unsqueeze(-1) * Fg + (1.0 - a).unsqueeze(-1) * blur
+
 class SDMatteApply:
 
     @classmethod
@@ -1557,12 +1591,68 @@ class SDMatteTemporalSmoothMotion:
         return (_trimap_engine(_torch_device()).smooth_alpha_motion(*args), )
 
 
+class SDMatteDefocus:
+    """Image + alpha -> the subject over its own background out of focus ("portrait mode", background blur) on the GPU.  The blur is a disc, as a lens's
+    is, it is normalised and does not see the subject, so the subject's colours leave no halo around the silhouette; bright background points can be
+    boosted into round highlights.  Two kernel launches.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE", {"tooltip": "the photo"}),
+                             "alpha": ("MASK", {"tooltip": "alpha matte of the photo (alpha_mask of Apply SDMatte)"})},
+                "optional": {"foreground": ("IMAGE", {"tooltip": "foreground colours (SDMatte Foreground Colours); default: the photo"}),
+                             "background": ("IMAGE", {"tooltip": "background colours (SDMatte Foreground Colours); default: the photo"}),
+                             "radius_px": ("INT", {"default": 16, "min": 1, "max": 64, "tooltip": "radius of the blur disc in pixels"}),
+                             "highlight_gain": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 64.0, "step": 0.5,
+                                                          "tooltip": "extra weight of background pixels per unit of brightness above the threshold"}),
+                             "highlight_threshold": ("FLOAT", {"default": 0.8, "min": 0.0, "max": 1.0, "step": 0.01,
+                                                               "tooltip": "brightness (mean of r, g, b) above which a pixel counts as a highlight"}),
+                             "decontaminate": ("BOOLEAN", {"default": False,
+                                                           "tooltip": "with neither foreground nor background connected: estimate both from the photo first"}),
+                             "force_cpu": ("BOOLEAN", {"default": False, "tooltip": "evaluate the torch restatement on the CPU instead of the GPU call"})}}
+
+    RETURN_TYPES = ("IMAGE", )
+    RETURN_NAMES = ("image", )
+    FUNCTION = "defocus"
+    CATEGORY = "Matting/SDMatte"
+
+    def defocus(self, image, alpha, foreground=None, background=None, radius_px=16, highlight_gain=0.0, highlight_threshold=0.8, decontaminate=False,
+                force_cpu=False):
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        if alpha.dim() == 2:
+            alpha = alpha.unsqueeze(0)
+        if tuple(alpha.shape) != tuple(image.shape[:3]):
+            raise ValueError(f"[SDMatte] alpha must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+        for name, t in (("foreground", foreground), ("background", background)):
+            if t is not None and tuple(t.shape) != tuple(image.shape):
+                raise ValueError(f"[SDMatte] {name} must be [B,H,W,3] of the image {tuple(image.shape)}, got {tuple(t.shape)}")
+        params = (int(radius_px), float(highlight_gain), float(highlight_threshold))
+        estimate = bool(decontaminate) and foreground is None and background is None
+        if force_cpu:      # an explicit request, never a silent substitute: the same functions in torch
+            image, alpha = image.detach().cpu(), alpha.detach().cpu()
+            fg = foreground.detach().cpu() if foreground is not None else None
+            bg = background.detach().cpu() if background is not None else None
+            if estimate:
+                fg, bg, _ = estimate_foreground(image, alpha)
+            return (defocus_background(image, alpha, fg, bg, *params), )
+        device = _torch_device()
+        eng = _trimap_engine(device)
+        image, alpha = image.detach().to(device), alpha.detach().to(device)
+        fg = foreground.detach().to(device) if foreground is not None else None
+        bg = background.detach().to(device) if background is not None else None
+        if estimate:       # both planes stay on the device: the two calls are ordered on torch's current stream
+            fg, bg = eng.estimate_foreground(image, alpha, sync=False)
+        return (eng.defocus_background(image, alpha, fg, bg, *params, sync=False).cpu(), )
+
+
 def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False, canvas: bool = False,
-                  subjects: bool = False, edge: bool = False, video: bool = False, motion: bool = False):
+                  subjects: bool = False, edge: bool = False, video: bool = False, motion: bool = False, defocus: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
     node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`, plus the subject-box node when `roi`,
     plus the canvas node when `canvas`, plus the box-per-subject node when `subjects`, plus the two
-    distance-field nodes (mask offset, outline) when `edge`, plus the temporal smoothing node when `video`, plus the motion-compensated one when `motion`."""
+    distance-field nodes (mask offset, outline) when `edge`, plus the temporal smoothing node when `video`, plus the motion-compensated one when `motion`,
+    plus the background defocus node when `defocus`."""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
@@ -1595,10 +1685,13 @@ def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, c
     if motion:
         classes["SDMatteTemporalSmoothMotion"] = SDMatteTemporalSmoothMotion
         names["SDMatteTemporalSmoothMotion"] = "SDMatte Temporal Smooth (Motion)"
+    if defocus:
+        classes["SDMatteDefocus"] = SDMatteDefocus
+        names["SDMatteDefocus"] = "SDMatte Defocus Background"
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1), like the multi-GPU fan-out
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
 NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
@@ -1609,4 +1702,5 @@ NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("
                                                                 os.environ.get("SDMATTE_SUBJECTS_NODE") == "1",
                                                                 os.environ.get("SDMATTE_EDGE_NODES") == "1",
                                                                 os.environ.get("SDMATTE_VIDEO_NODE") == "1",
-                                                                os.environ.get("SDMATTE_MOTION_NODE") == "1")
+                                                                os.environ.get("SDMATTE_MOTION_NODE") == "1",
+                                                                os.environ.get("SDMATTE_DEFOCUS_NODE") == "1")

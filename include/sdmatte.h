@@ -519,6 +519,46 @@ int sdm_smooth_alpha_motion(sdm_ctx* ctx, const float* image_bhwc, const float* 
                             int search, float color_tolerance, float motion_penalty, float strength, float max_change, float* out_bhw,
                             int ptr_kind, void* stream);
 
+/* The subject over its own background, out of focus (beyond the reference): "portrait mode", background blur.  Blurring the photo and mixing it back by
+ * alpha blurs the subject's colours into the background, where they show as a halo around the silhouette; here the blur is normalised and does not see
+ * the subject, and its kernel is a disc, as a lens's is, with an optional boost of the highlights.  No weights.
+ * image, fg, bg and out are fp32 [B,H,W,3], alpha is fp32 [B,H,W]; fg_bhwc and bg_bhwc may each be NULL; all of one pointer kind.  Colours are used as
+ * they are.  They must be finite: a non-finite colour gives an unspecified value in every pixel whose disc contains it, never an out-of-bounds access.
+ *   a      the alpha with NaN -> 0, then clamped to [0, 1]
+ *   C, F   C = bg if given, else image; F = fg if given, else image.  (With the two planes of sdm_estimate_foreground the soft edge pixels are clean on
+ *          both sides; without them the call still works.)
+ *   weight Y(q) = (C.r + C.g + C.b) / 3;  w(q) = (1 - a(q)) * (1 + highlight_gain * max(0, Y(q) - highlight_threshold)).  With highlight_gain == 0 the
+ *          second factor is exactly 1.
+ *   disc   D(p) = the pixels q = p + (dy, dx) with dy*dy + dx*dx <= R*R that exist, R = radius_px: the closed disc, the membership rule of
+ *          sdm_make_trimap.  Pixels beyond the border do not exist.  The half widths hw(dy) = the largest h with h*h <= R*R - dy*dy are computed in
+ *          integers on the host.
+ *   sums   S(p) = sum over q in D(p) of w(q) * C(q), per channel;  N(p) = sum over q in D(p) of w(q)
+ *   blur   Bb(p) = (S(p) + e * C(p)) / (N(p) + e), e = SDM_DEFOCUS_FLOOR = 2^-10, a true fp32 division.  The floor removes the 0 / 0 deep inside a subject
+ *          larger than the disc; it has no branch, so the function is continuous.  (N >= 0; an implementation may clamp a computed N at 0 so that a
+ *          rounding error cannot take the denominator below e.)
+ *   out    out(p) = a * F(p) + (1 - a) * Bb(p)
+ * Everything is fp32, no FMA contraction.  The order in which the terms of a disc are summed is not part of the contract (the rule of
+ * sdm_smooth_alpha_motion for its patch sums), but it depends on the pixel's position only, so these hold bit for bit:
+ *   1. where a(p) == 1, out(p) == F(p);
+ *   2. if w(q) * C_c(q) == 0 for every pixel q of an image and a channel c, then out_c == a * F_c in that image (no halo: every partial sum of whatever
+ *      summation scheme is a sum of zeros.  This is a statement about the whole image, not about one disc);
+ *   3. an image's result does not depend on the batch it is in; two calls, host and device pointers, and pointers 4 bytes off a 16-byte boundary all give
+ *      the same bits.
+ * sdmatte_nodes.defocus_background is the same function in torch (equal to fp32 rounding).
+ * Limits: B, H, W >= 1 within SDM_FG_MAX_SIDE / SDM_FG_MAX_PIXELS; radius_px in 1 .. SDM_DEFOCUS_MAX_RADIUS; highlight_gain finite in [0, 64];
+ * highlight_threshold finite in [0, 1]: SDM_ERR_INVALID otherwise, with a message that names the argument, and then nothing is queued or written.  Stream
+ * contract and pointer kinds as sdm_make_trimap; sdm_last_forward_ms covers the launches.  Needs no weights.  TWO kernel launches (csrc/k_defocus.h),
+ * `dof_prefix` then `dof_gather` in sdm_kernel_counts and the per-launch profile, whatever the arguments, the sizes and the content; no host readback.
+ * One plane of 16 bytes per pixel lives in the activation arena; host pointers go through the I/O staging. */
+#define SDM_DEFOCUS_MAX_RADIUS 64
+#define SDM_DEFOCUS_MAX_GAIN 64
+#define SDM_DEFOCUS_FLOOR 0.0009765625f
+#define SDM_DEFOCUS_RADIUS 16
+#define SDM_DEFOCUS_HIGHLIGHT_GAIN 0.0f
+#define SDM_DEFOCUS_HIGHLIGHT_THRESHOLD 0.8f
+int sdm_defocus_background(sdm_ctx* ctx, const float* image_bhwc, const float* alpha_bhw, const float* fg_bhwc, const float* bg_bhwc, int B, int H, int W,
+                           int radius_px, float highlight_gain, float highlight_threshold, float* out_bhwc, int ptr_kind, void* stream);
+
 /* Memory the engine holds outside any framework allocator: packed weights + activation arena (sized by the largest batch /
  * resolution seen) + I/O staging.  sdm_release_memory frees everything but the weights (the next forward re-allocates). */
 int64_t sdm_resident_bytes(sdm_ctx* ctx);
@@ -544,7 +584,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal / sdm_smooth_alpha_motion: their launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal / sdm_smooth_alpha_motion / sdm_defocus_background: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
