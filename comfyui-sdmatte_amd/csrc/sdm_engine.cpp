@@ -24,6 +24,7 @@
 #include "k_temporal.h"
 #include "k_motion.h"
 #include "k_defocus.h"
+#include "k_harmonize.h"
 #include "k_roi.h"
 #include "k_canvas.h"
 #include "k_boxes.h"
@@ -2584,7 +2585,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background, sdm_harmonize) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -3649,6 +3650,88 @@ int sdm_defocus_background(sdm_ctx* e, const float* image, const float* alpha, c
       prof_end(e);
     }
     tfree(e, plane);
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// the cut-out in its new scene: colour match and light wrap (k_harmonize.h)
+// ------------------------------------------------------------------------------------------------
+/* The partial sums (14 floats per run of 4096 pixels), the map (12 floats per image) and, with the wrap, the row-blurred plane (16 bytes per pixel) live in
+ * the activation arena.  hz_stats and hz_finalize run when the match is on, hz_rows when the wrap is on, hz_compose always. */
+int sdm_harmonize(sdm_ctx* e, const float* fg, const float* alpha, const float* bg_image, int bg_batch, int B, int H, int W, float luma_strength,
+                  float chroma_strength, float contrast_strength, float wrap_strength, float wrap_sigma, float* out, float* fg_out, float* map_out,
+                  int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !fg || !alpha || !bg_image || !out) return SDM_ERR_INVALID;
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "harmonize: bad image size %dx%dx%d", B, H, W);
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "harmonize: %dx%dx%d is too large (sides up to %d, %d pixels in all)", B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  if (bg_batch != 1 && bg_batch != B) SDM_FAIL(e, SDM_ERR_INVALID, "harmonize: bg_batch = %d must be 1 or %d", bg_batch, B);
+  const struct { const char* name; float v; } strengths[] = {{"luma_strength", luma_strength}, {"chroma_strength", chroma_strength},
+                                                             {"contrast_strength", contrast_strength}, {"wrap_strength", wrap_strength}};
+  for (const auto& s : strengths)
+    if (!std::isfinite(s.v) || !(s.v >= 0.0f) || !(s.v <= 1.0f))
+      SDM_FAIL(e, SDM_ERR_INVALID, "harmonize: %s = %g must be a finite number in [0, 1]", s.name, (double)s.v);
+  const bool match = luma_strength > 0.0f || chroma_strength > 0.0f, wrap = wrap_strength > 0.0f;
+  if (wrap && (!std::isfinite(wrap_sigma) || !(wrap_sigma > 0.0f) || !(wrap_sigma <= (float)SDM_HZ_MAX_WRAP_SIGMA)))
+    SDM_FAIL(e, SDM_ERR_INVALID, "harmonize: wrap_sigma = %g must be a finite number in (0, %d]", (double)wrap_sigma, SDM_HZ_MAX_WRAP_SIGMA);
+  static_assert(SDM_HZ_R == 3 * SDM_HZ_MAX_WRAP_SIGMA && SDM_HZ_R % 4 == 0 && SDM_HZ_RUN_PX == SDM_HZ_RUN, "k_harmonize.h is sized for these");
+  HzBlur blur;
+  memset(&blur, 0, sizeof(blur));
+  if (wrap) {      // w_i = exp(-i^2 / (2 sigma^2)) / sum, in double, rounded to fp32 (as the shadow of sdm_compose_canvas)
+    const double s = (double)wrap_sigma;
+    blur.r = std::min(SDM_HZ_R, std::max(1, (int)std::ceil(3.0 * s)));
+    double g[2 * SDM_HZ_R + 1], sum = 0.0;
+    for (int k = 0; k <= 2 * blur.r; ++k) { const double i = (double)(k - blur.r); g[k] = std::exp(-(i * i) / (2.0 * s * s)); sum += g[k]; }
+    for (int k = 0; k <= 2 * blur.r; ++k) blur.w[k] = (float)(g[k] / sum);
+  }
+  const HzParams prm = {luma_strength, chroma_strength, contrast_strength, wrap_strength};
+  const size_t px = (size_t)B * H * W;
+  const int runs = sdm_cdiv(H * W, SDM_HZ_RUN_PX);
+  IoSpan in[] = {{(void*)fg, px * 12}, {(void*)alpha, px * 4}, {(void*)bg_image, (size_t)bg_batch * H * W * 12}};
+  IoSpan outs[] = {{out, px * 12}, {fg_out, fg_out ? px * 12 : 0}, {map_out, map_out ? (size_t)B * 48 : 0}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_fg = (const float*)in[0].p; const float* d_alpha = (const float*)in[1].p; const float* d_bg = (const float*)in[2].p;
+    float* d_out = (float*)outs[0].p; float* d_fg_out = fg_out ? (float*)outs[1].p : nullptr; float* d_map_out = map_out ? (float*)outs[2].p : nullptr;
+    T partials, map, tplane;
+    if (match) { partials = talloc(e, B, runs, 1, SDM_HZ_NSUM, 1); map = talloc(e, B, 1, 1, 12, 1); }
+    if (wrap) tplane = talloc(e, B, H, W, 4, 1);
+    if (!e->dry) {
+      const double bg_px = (double)bg_batch * H * W;
+      if (match) {
+        const int vec = (H * W) % 4 == 0 && aligned16(d_fg) && aligned16(d_alpha) && aligned16(d_bg) ? 1 : 0;
+        prof_begin(e, "hz_stats", 0, (double)px * 16 + bg_px * 12 + (double)B * runs * 56);
+        count_kernel("hz_stats");
+        SDM_LAUNCH(hz_stats_kernel, dim3((unsigned)(B * runs)), dim3(256), 0, e->stream, d_fg, d_alpha, d_bg, bg_batch, B, H, W, vec, (float*)partials.p);
+        prof_end(e);
+        prof_begin(e, "hz_finalize", 0, (double)B * runs * 56);
+        count_kernel("hz_finalize");
+        SDM_LAUNCH(hz_finalize_kernel, dim3((unsigned)B), dim3(64), 0, e->stream, (const float*)partials.p, B, runs, prm, (double)SDM_HZ_VAR_FLOOR,
+                   (double)SDM_HZ_MAX_GAIN, (double)SDM_HZ_MIN_WEIGHT, (float*)map.p, d_map_out);
+        prof_end(e);
+      }
+      if (wrap) {
+        const int vec = W % 4 == 0 && aligned16(d_alpha) && aligned16(d_bg) ? 1 : 0;
+        const long long units = (long long)B * H * sdm_cdiv(W, SDM_HZ_SEG);
+        prof_begin(e, "hz_rows", 0, (double)px * (4 + 12 + 16));
+        count_kernel("hz_rows");
+        SDM_LAUNCH(hz_rows_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, e->stream, d_alpha, d_bg, bg_batch, B, H, W, blur, vec, (f32x4*)tplane.p);
+        prof_end(e);
+      }
+      // bytes: fg, alpha, bg and the results once; every tile fetches the rows of T within r of it
+      double win_rows = 0;
+      if (wrap)
+        for (int y0 = 0; y0 < H; y0 += SDM_HZ_TH) win_rows += std::min(H - 1, y0 + SDM_HZ_TH - 1 + blur.r) - std::max(0, y0 - blur.r) + 1;
+      prof_begin(e, "hz_compose", 0, (double)px * (12 + 4 + 12 + 12 + (d_fg_out ? 12 : 0)) + 16.0 * B * win_rows * W);
+      count_kernel("hz_compose");
+      SDM_LAUNCH(hz_compose_kernel, dim3((unsigned)(B * sdm_cdiv(H, SDM_HZ_TH) * sdm_cdiv(W, SDM_HZ_TW))), dim3(256), 0, e->stream,
+                 wrap ? (const f32x4*)tplane.p : (const f32x4*)nullptr, d_fg, d_alpha, d_bg, bg_batch, B, H, W, blur, wrap_strength,
+                 match ? (const float*)map.p : (const float*)nullptr, match ? (float*)nullptr : d_map_out, d_out, d_fg_out);
+      prof_end(e);
+    }
+    if (wrap) tfree(e, tplane);
+    if (match) { tfree(e, map); tfree(e, partials); }
     return 0;
   });
 }

@@ -83,7 +83,7 @@ EXPORTS = [
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
-    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background",
+    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background", "sdm_harmonize",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_stats", "sdm_op_gn_partials", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias", "sdm_debug_patch_token_map", "sdm_op_groupnorm_p3", "sdm_op_gemm_p3_tokens", "sdm_op_mask_bias_tokens", "sdm_op_active_tiles",
@@ -134,6 +134,7 @@ class Bindings:
             "sdm_smooth_alpha_temporal": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, i32, vp]),
             "sdm_smooth_alpha_motion": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, vp, i32, vp]),
             "sdm_defocus_background": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, vp]),
+            "sdm_harmonize": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
             "sdm_resident_bytes": (i64, [vp]),
@@ -1048,6 +1049,62 @@ class Engine:
         if sync:
             self.synchronize()
         return out
+
+    # SDM_HZ_* (include/sdmatte.h)
+    HARMONIZE_DEFAULTS = {"luma_strength": 0.6, "chroma_strength": 0.8, "contrast_strength": 0.5, "wrap_strength": 0.5, "wrap_sigma": 6.0}
+    HARMONIZE_MAX_WRAP_SIGMA = 16
+
+    @classmethod
+    def _check_harmonize_params(cls, what, luma_strength, chroma_strength, contrast_strength, wrap_strength, wrap_sigma):
+        """The argument limits of sdm_harmonize; returns the values that cross the C ABI (rounded to fp32).  wrap_sigma is not looked at without the
+        wrap (it crosses as the default then)."""
+        luma_strength = cls._check_f32_range(what, "luma_strength", luma_strength, 0, 1)
+        chroma_strength = cls._check_f32_range(what, "chroma_strength", chroma_strength, 0, 1)
+        contrast_strength = cls._check_f32_range(what, "contrast_strength", contrast_strength, 0, 1)
+        wrap_strength = cls._check_f32_range(what, "wrap_strength", wrap_strength, 0, 1)
+        if wrap_strength > 0:
+            wrap_sigma = cls._check_f32_range(what, "wrap_sigma", wrap_sigma, 0, cls.HARMONIZE_MAX_WRAP_SIGMA, lo_open=True)
+        else:
+            wrap_sigma = cls.HARMONIZE_DEFAULTS["wrap_sigma"]
+        return luma_strength, chroma_strength, contrast_strength, wrap_strength, wrap_sigma
+
+    @staticmethod
+    def _check_harmonize_shapes(what, fg, alpha, bg):
+        if fg.dim() != 4 or fg.shape[-1] != 3 or fg.numel() == 0:
+            raise ValueError(f"{what}: fg must be a non-empty [B,H,W,3], got {tuple(fg.shape)}")
+        B, H, W, _ = (int(v) for v in fg.shape)
+        if tuple(alpha.shape) != (B, H, W):
+            raise ValueError(f"{what}: alpha must be [B,H,W] = {(B, H, W)}, got {tuple(alpha.shape)}")
+        if bg.dim() != 4 or tuple(bg.shape[1:]) != (H, W, 3) or int(bg.shape[0]) not in (1, B):
+            raise ValueError(f"{what}: bg must be [1 or {B},{H},{W},3], got {tuple(bg.shape)}")
+        return B, H, W
+
+    def harmonize(self, fg_bhw3, alpha_bhw, bg, luma_strength=0.6, chroma_strength=0.8, contrast_strength=0.5, wrap_strength=0.5, wrap_sigma=6.0,
+                  return_fg=False, return_map=False, sync=True):
+        """The cut-out in its new scene (sdm_harmonize, defined in include/sdmatte.h): the straight foreground colours `fg_bhw3` [B,H,W,3] are moved
+        towards the colour statistics of the scene `bg` ([1 or B,H,W,3]) in opponent coordinates (mean by `luma_strength` / `chroma_strength`, spread by
+        `contrast_strength` times them), the scene's visible light is wrapped over the subject's edge (a Gaussian of `wrap_sigma` pixels, `wrap_strength`),
+        and the result is composed over the scene with the alpha.  Returns fp32 [B,H,W,3] on the inputs' device; with return_fg also the adjusted
+        foreground colours [B,H,W,3], with return_map also the colour map [B,12] (M row-major, then t).  One to four kernel launches, by the stages that
+        are on.  Needs no loaded weights.  `sdmatte_nodes.harmonize_cutout` / `harmonize_map` are the same function in torch, equal to fp32 rounding."""
+        B, H, W = self._check_harmonize_shapes("harmonize", fg_bhw3, alpha_bhw, bg)
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"harmonize: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        params = self._check_harmonize_params("harmonize", luma_strength, chroma_strength, contrast_strength, wrap_strength, wrap_sigma)
+        fg_bhw3 = fg_bhw3.float().contiguous()
+        alpha_bhw = alpha_bhw.float().contiguous()
+        bg = bg.float().contiguous()
+        dev = fg_bhw3.device
+        out = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
+        fg_out = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev) if return_fg else None
+        map_out = torch.empty(B, 12, dtype=torch.float32, device=dev) if return_map else None
+        stream = self._check_io("harmonize", fg_bhw3, alpha_bhw, bg, out)
+        self._check(self.lib.sdm_harmonize(self.h, _ptr(fg_bhw3), _ptr(alpha_bhw), _ptr(bg), int(bg.shape[0]), B, H, W, *params, _ptr(out), _ptr(fg_out),
+                                           _ptr(map_out), self._kind(fg_bhw3), stream), "sdm_harmonize")
+        if sync:
+            self.synchronize()
+        res = (out, ) + ((fg_out, ) if return_fg else ()) + ((map_out, ) if return_map else ())
+        return res[0] if len(res) == 1 else res
 
     def synchronize(self):
         self._check(self.lib.sdm_synchronize(self.h), "sdm_synchronize")

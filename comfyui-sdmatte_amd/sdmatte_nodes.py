@@ -31,6 +31,8 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
     soft edge of a moving subject is smoothed too; `temporal_smooth_alpha_motion` below is its torch restatement;
   * and one registered only with SDMATTE_DEFOCUS_NODE=1: `SDMatteDefocus` puts the subject back over its own background out of focus (a normalised
     disc blur that does not see the subject, so no halo), in two kernel launches; `defocus_background` below is its torch restatement;
+  * and one registered only with SDMATTE_HARMONIZE_NODE=1: `SDMatteHarmonize` sits the cut-out in a new scene (colour match in opponent coordinates,
+    light wrap along the edge, then "over"), in one to four kernel launches; `harmonize_map` / `harmonize_cutout` below are its torch restatement;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -1030,6 +1032,98 @@ def defocus_background(image, alpha, fg=None, bg=None, radius_px=16, highlight_g
     blur = (sums[..., :3] + e * C) / (sums[..., 3:].clamp(min=0.0) + e)
     return a.unsqueeze(-1) * Fg + (1.0 - a).unsqueeze(-1) * blur
 
+
+def _harmonize_opponent(c):
+    return torch.stack([((c[..., 0] + c[..., 1]) + c[..., 2]) / 3.0, c[..., 0] - c[..., 1], (c[..., 0] + c[..., 1]) / 2.0 - c[..., 2]], -1)
+
+
+def harmonize_map(fg, alpha, bg, luma_strength=0.6, chroma_strength=0.8, contrast_strength=0.5):
+    """The colour map of `Engine.harmonize` in torch (the function defined in include/sdmatte.h): fg [B,H,W,3], alpha [B,H,W], bg [1 or B,H,W,3] ->
+    fp32 [B,12] on the tensors' device, per image the nine entries of M row-major, then the three of t.  The per-pixel terms are fp32; they are summed
+    per image row in fp32, and the row sums and everything after them in fp64 (the kernels sum runs of 4096 pixels instead: equal to fp32 rounding)."""
+    from .engine import Engine
+    B, H, W = Engine._check_harmonize_shapes("harmonize_map", fg, alpha, bg)
+    luma, chroma, contrast, _, _ = Engine._check_harmonize_params("harmonize_map", luma_strength, chroma_strength, contrast_strength, 0.0, 1.0)
+    dev = fg.device
+    out = torch.zeros(B, 12, dtype=torch.float64, device=dev)
+    out[:, 0] = out[:, 4] = out[:, 8] = 1.0
+    if luma == 0.0 and chroma == 0.0:
+        return out.float()
+    F = fg.detach().float()
+    a = torch.nan_to_num(alpha.detach().float(), nan=0.0).clamp(0.0, 1.0)
+    Bg = bg.detach().float().expand(B, H, W, 3)
+    oF, oB = _harmonize_opponent(F), _harmonize_opponent(Bg)
+    ao = a.unsqueeze(-1) * oF
+    rows = lambda t: t.sum(2).double().sum(1)               # fp32 per row, then fp64
+    Wf, n = rows(a), float(H * W)
+    ok = Wf >= 1.0                                          # SDM_HZ_MIN_WEIGHT
+    Wd = torch.where(ok, Wf, torch.ones_like(Wf)).unsqueeze(-1)
+    mf, mb = rows(ao) / Wd, rows(oB) / n
+    vf, vb = rows(ao * oF) / Wd - mf * mf, rows(oB * oB) / n - mb * mb
+    e = 2.0 ** -20                                          # SDM_HZ_VAR_FLOOR
+    s = torch.tensor([luma, chroma, chroma], dtype=torch.float64, device=dev)
+    rho = torch.sqrt((vb.clamp(min=0.0) + e) / (vf.clamp(min=0.0) + e)).clamp(0.25, 4.0)      # SDM_HZ_MAX_GAIN; the variances clamped at 0 first
+    g = 1.0 + contrast * s * (rho - 1.0)
+    h = mf * (1.0 - g) + s * (mb - mf)
+    P = torch.tensor([[[1, 1, 1], [1, 1, 1], [1, 1, 1]], [[1.5, -1.5, 0], [-1.5, 1.5, 0], [0, 0, 0]], [[.5, .5, -1], [.5, .5, -1], [-1, -1, 2]]],
+                     dtype=torch.float64, device=dev) / 3.0
+    K = torch.tensor([[1, 1, 1], [.5, -.5, 0], [1 / 3, 1 / 3, -2 / 3]], dtype=torch.float64, device=dev)
+    M = torch.eye(3, dtype=torch.float64, device=dev) + torch.einsum("bc,cij->bij", g - 1.0, P)
+    t = torch.einsum("bc,ci->bi", h, K)
+    full = torch.cat([M.reshape(B, 9), t], 1)
+    return torch.where(ok.unsqueeze(-1), full, out).float()
+
+
+def harmonize_cutout(fg, alpha, bg, luma_strength=0.6, chroma_strength=0.8, contrast_strength=0.5, wrap_strength=0.5, wrap_sigma=6.0, return_fg=False,
+                     return_map=False):
+    """`Engine.harmonize` in torch fp32, on the tensors' own device (the function defined in include/sdmatte.h): the straight colours `fg` [B,H,W,3]
+    moved towards the colour statistics of the scene `bg` [1 or B,H,W,3], the scene's visible light wrapped over the subject's edge, composed over the
+    scene with `alpha` [B,H,W] -> fp32 [B,H,W,3] (and the adjusted colours, and the map [B,12]).  Equal to the kernels to fp32 rounding; the
+    identities of the header hold here too.  The wrap is two 1-D convolutions with zero padding, rows first."""
+    import math
+    import torch.nn.functional as Fn
+    from .engine import Engine
+    B, H, W = Engine._check_harmonize_shapes("harmonize_cutout", fg, alpha, bg)
+    luma, chroma, contrast, wrap, sigma = Engine._check_harmonize_params("harmonize_cutout", luma_strength, chroma_strength, contrast_strength,
+                                                                         wrap_strength, wrap_sigma)
+    m = harmonize_map(fg, alpha, bg, luma, chroma, contrast)
+    F = fg.detach().float()
+    a = torch.nan_to_num(alpha.detach().float(), nan=0.0).clamp(0.0, 1.0)
+    Bg = bg.detach().float().expand(B, H, W, 3)
+    M, t = m[:, :9].view(B, 1, 1, 3, 3), m[:, 9:].view(B, 1, 1, 3)
+    Fp = (((t + M[..., 0] * F[..., 0:1]) + M[..., 1] * F[..., 1:2]) + M[..., 2] * F[..., 2:3]).clamp(0.0, 1.0)
+    if wrap > 0.0:
+        r = int(math.ceil(3.0 * sigma))
+        i = torch.arange(-r, r + 1, dtype=torch.float64)
+        w = torch.exp(-(i * i) / (2.0 * sigma * sigma))
+        w = (w / w.sum()).float().to(F.device)
+        v = 1.0 - a
+        X = torch.cat([v.unsqueeze(-1) * Bg, v.unsqueeze(-1)], -1).permute(0, 3, 1, 2).contiguous()
+        T = Fn.conv2d(X, w.view(1, 1, 1, -1).expand(4, 1, 1, 2 * r + 1).contiguous(), padding=(0, r), groups=4)
+        Wm = Fn.conv2d(T, w.view(1, 1, -1, 1).expand(4, 1, 2 * r + 1, 1).contiguous(), padding=(r, 0), groups=4).permute(0, 2, 3, 1)
+        Fp = (Fp + wrap * (Wm[..., :3] - Wm[..., 3:] * Fp)).clamp(0.0, 1.0)
+    out = a.unsqueeze(-1) * Fp + (1.0 - a).unsqueeze(-1) * Bg
+    res = (out, ) + ((Fp, ) if return_fg else ()) + ((m, ) if return_map else ())
+    return res[0] if len(res) == 1 else res
+
+
+def fit_background(bg, H, W):
+    """bg [N,h,w,3] -> [N,H,W,3]: scaled (bilinear, antialiased) to cover H x W, then centre-cropped; returned as it is when the size is right."""
+    import torch.nn.functional as Fn
+    if bg.dim() != 4 or bg.shape[-1] != 3 or bg.numel() == 0:
+        raise ValueError(f"[SDMatte] background must be a non-empty [N,h,w,3], got {tuple(bg.shape)}")
+    h, w = int(bg.shape[1]), int(bg.shape[2])
+    if (h, w) == (H, W):
+        return bg.float()
+    scale = max(H / h, W / w)
+    nh, nw = max(H, int(round(h * scale))), max(W, int(round(w * scale)))
+    t = bg.float()
+    if (nh, nw) != (h, w):
+        t = Fn.interpolate(t.permute(0, 3, 1, 2), size=(nh, nw), mode="bilinear", align_corners=False, antialias=True).permute(0, 2, 3, 1)
+    y0, x0 = (nh - H) // 2, (nw - W) // 2
+    return t[:, y0:y0 + H, x0:x0 + W].clamp(0.0, 1.0).contiguous()
+
+
 class SDMatteApply:
 
     @classmethod
@@ -1646,13 +1740,56 @@ class SDMatteDefocus:
         return (eng.defocus_background(image, alpha, fg, bg, *params, sync=False).cpu(), )
 
 
+class SDMatteHarmonize:
+    """Foreground + alpha + a new background -> the cut-out sitting in that scene on the GPU: its colours matched to the scene's light (mean and spread of
+    brightness and of the two colour axes), the scene's light wrapped around its edge, then composed.  One to four kernel launches.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        unit = lambda d, tip: ("FLOAT", {"default": d, "min": 0.0, "max": 1.0, "step": 0.05, "tooltip": tip})
+        return {"required": {"foreground": ("IMAGE", {"tooltip": "foreground colours of the cut-out (foreground of SDMatte Foreground Colours, or the image)"}),
+                             "alpha": ("MASK", {"tooltip": "alpha matte of the foreground"}),
+                             "background": ("IMAGE", {"tooltip": "the new scene (one image, or one per foreground); another size is scaled to cover and centre-cropped"})},
+                "optional": {"luma_strength": unit(0.6, "how far the subject's brightness moves to the scene's (0 = not at all)"),
+                             "chroma_strength": unit(0.8, "how far the subject's colour cast moves to the scene's"),
+                             "contrast_strength": unit(0.5, "how far the spread of brightness and colour follows the scene's"),
+                             "wrap_strength": unit(0.5, "how much of the scene's light spills over the subject's edge (0 = no light wrap)"),
+                             "wrap_sigma": ("FLOAT", {"default": 6.0, "min": 0.1, "max": 16.0, "step": 0.1, "tooltip": "reach of the light wrap in pixels (Gaussian sigma)"}),
+                             "force_cpu": ("BOOLEAN", {"default": False, "tooltip": "evaluate the torch restatement on the CPU instead of the GPU call"})}}
+
+    RETURN_TYPES = ("IMAGE", "IMAGE")
+    RETURN_NAMES = ("image", "foreground")
+    FUNCTION = "harmonize"
+    CATEGORY = "Matting/SDMatte"
+
+    def harmonize(self, foreground, alpha, background, luma_strength=0.6, chroma_strength=0.8, contrast_strength=0.5, wrap_strength=0.5, wrap_sigma=6.0,
+                  force_cpu=False):
+        if foreground.dim() != 4 or foreground.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] foreground must be [B,H,W,3], got {tuple(foreground.shape)}")
+        if alpha.dim() == 2:
+            alpha = alpha.unsqueeze(0)
+        if tuple(alpha.shape) != tuple(foreground.shape[:3]):
+            raise ValueError(f"[SDMatte] alpha must be [B,H,W] of the foreground {tuple(foreground.shape[:3])}, got {tuple(alpha.shape)}")
+        B, H, W = (int(v) for v in foreground.shape[:3])
+        if background.dim() != 4 or background.shape[-1] != 3 or int(background.shape[0]) not in (1, B):
+            raise ValueError(f"[SDMatte] background must be [1 or {B},h,w,3], got {tuple(background.shape)}")
+        params = (float(luma_strength), float(chroma_strength), float(contrast_strength), float(wrap_strength), float(wrap_sigma))
+        bg = fit_background(background.detach().cpu(), H, W)
+        if force_cpu:      # an explicit request, never a silent substitute: the same function in torch
+            return harmonize_cutout(foreground.detach().cpu(), alpha.detach().cpu(), bg, *params, return_fg=True)
+        device = _torch_device()
+        out, fg_out = _trimap_engine(device).harmonize(foreground.detach().to(device), alpha.detach().to(device), bg.to(device), *params, return_fg=True,
+                                                       sync=False)
+        return (out.cpu(), fg_out.cpu())
+
+
 def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False, canvas: bool = False,
                   subjects: bool = False, edge: bool = False, video: bool = False, motion: bool = False, defocus: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
     node when `foreground`, plus the alpha refinement node when `refine`, plus the mask clean-up node when `clean`, plus the subject-box node when `roi`,
     plus the canvas node when `canvas`, plus the box-per-subject node when `subjects`, plus the two
     distance-field nodes (mask offset, outline) when `edge`, plus the temporal smoothing node when `video`, plus the motion-compensated one when `motion`,
-    plus the background defocus node when `defocus`."""
+    plus the background defocus node when `defocus`.  (The harmonize node is added by `with_harmonize_node`.)"""
     classes = {"SDMatteApply": SDMatteApply}
     names = {"SDMatteApply": "Apply SDMatte"}
     if extra:
@@ -1691,9 +1828,19 @@ def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, c
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1), like the multi-GPU fan-out
+def with_harmonize_node(mappings, harmonize: bool = True):
+    """(classes, names) of `node_mappings` plus `SDMatteHarmonize` when `harmonize`; the argument is not modified.  A function of its own: the argument
+    list of `node_mappings` is pinned by its callers."""
+    classes, names = dict(mappings[0]), dict(mappings[1])
+    if harmonize:
+        classes["SDMatteHarmonize"] = SDMatteHarmonize
+        names["SDMatteHarmonize"] = "SDMatte Harmonize"
+    return classes, names
+
+
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1, SDMATTE_HARMONIZE_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
-NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
+NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_harmonize_node(node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
                                                                 os.environ.get("SDMATTE_REFINE_NODE") == "1",
                                                                 os.environ.get("SDMATTE_CLEAN_NODE") == "1",
@@ -1703,4 +1850,5 @@ NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = node_mappings(os.environ.get("
                                                                 os.environ.get("SDMATTE_EDGE_NODES") == "1",
                                                                 os.environ.get("SDMATTE_VIDEO_NODE") == "1",
                                                                 os.environ.get("SDMATTE_MOTION_NODE") == "1",
-                                                                os.environ.get("SDMATTE_DEFOCUS_NODE") == "1")
+                                                                os.environ.get("SDMATTE_DEFOCUS_NODE") == "1"),
+                                                                      os.environ.get("SDMATTE_HARMONIZE_NODE") == "1")

@@ -559,6 +559,64 @@ int sdm_smooth_alpha_motion(sdm_ctx* ctx, const float* image_bhwc, const float* 
 int sdm_defocus_background(sdm_ctx* ctx, const float* image_bhwc, const float* alpha_bhw, const float* fg_bhwc, const float* bg_bhwc, int B, int H, int W,
                            int radius_px, float highlight_gain, float highlight_threshold, float* out_bhwc, int ptr_kind, void* stream);
 
+/* The cut-out in its new scene (beyond the reference): colour match and light wrap.  A subject shot under one light and placed over a scene under another
+ * looks pasted on with a plain "over": its colours do not match the scene's light, and its edge carries none of it.  This call moves the subject's colour
+ * statistics towards the scene's, lets the scene's light spill over the subject's edge, and composes.  No weights.
+ * fg is fp32 [B,H,W,3] straight colours (sdm_estimate_foreground), alpha is fp32 [B,H,W], bg_image is fp32 [bg_batch,H,W,3] with bg_batch 1 or B (the rule of
+ * sdm_compose_canvas), out and fg_out are fp32 [B,H,W,3], map_out is fp32 [B,12]; fg_out and map_out may each be NULL; all of one pointer kind.  Colours
+ * are used as they are.  They must be finite: a non-finite colour gives unspecified values, never an out-of-bounds access.
+ *   a       the alpha with NaN -> 0, then clamped to [0, 1].  Bg = image b of bg_image, or image 0 when bg_batch == 1.
+ *   o(c)    the opponent coordinates of a colour (r, g, b):  l = ((r + g) + b) / 3 (a true fp32 division), p = r - g, q = (r + g) / 2 - b
+ *   moments per image.  Subject: Wf = sum of a;  mf_c = sum of a o_c(F) / Wf;  vf_c = sum of (a o_c(F)) o_c(F) / Wf - mf_c^2.  Scene, over all H W pixels
+ *           of Bg with weight 1 (the scene's light is a property of the scene, its hidden part included): mb_c and vb_c, formed the same way.  The
+ *           per-pixel terms are fp32; they are summed in fp32 over runs of at most SDM_HZ_RUN = 4096 consecutive pixels (row-major) of one image; the
+ *           partials and everything after them are fp64.  The order of summation depends on H and W only, never on B or on the image's index.  A variance
+ *           formed this way from rounded sums may come out a rounding error below 0 (a flat-coloured subject): vf_c and vb_c are clamped at 0.
+ *   map     s_0 = luma_strength, s_1 = s_2 = chroma_strength;  rho_c = sqrt((vb_c + e) / (vf_c + e)), e = SDM_HZ_VAR_FLOOR = 2^-20, clamped to
+ *           [1 / SDM_HZ_MAX_GAIN, SDM_HZ_MAX_GAIN];  g_c = 1 + contrast_strength s_c (rho_c - 1);  h_c = mf_c (1 - g_c) + s_c (mb_c - mf_c).  In RGB:
+ *           M = I + sum over c of (g_c - 1) P_c,  t = sum over c of h_c k_c, with the projectors of the coordinates above,
+ *             P_l = all 1/3;  P_p = [[1/2, -1/2, 0], [-1/2, 1/2, 0], [0, 0, 0]];  P_q = [[1/6, 1/6, -1/3], [1/6, 1/6, -1/3], [-1/3, -1/3, 2/3]];
+ *             k_l = (1, 1, 1);  k_p = (1/2, -1/2, 0);  k_q = (1/3, 1/3, -2/3)
+ *           (P_l + P_p + P_q = I, and g = 1 gives exactly I).  All fp64, rounded to fp32 at the end.  If Wf < SDM_HZ_MIN_WEIGHT = 1 (less than one pixel
+ *           of subject) or luma_strength == chroma_strength == 0: M = I and t = 0.  map_out[b] = the nine entries of M row-major, then the three of t.
+ *   match   F'_r = clamp(((t_r + M_r0 F.r) + M_r1 F.g) + M_r2 F.b, 0, 1), likewise g and b: fp32, in that order, no FMA contraction.
+ *   wrap    skipped entirely when wrap_strength == 0 (wrap_sigma is then not looked at).  v = 1 - a;  X = (v Bg.r, v Bg.g, v Bg.b, v): the visible
+ *           background only, premultiplied as in sdm_defocus_background.  r = ceil(3 wrap_sigma);  w_i = exp(-i^2 / (2 sigma^2)) for |i| <= r, normalised,
+ *           computed in double and rounded to fp32 (the shadow of sdm_compose_canvas).  X and T are 0 beyond the frame.
+ *             T(y, x) = sum over i = -r .. r (ascending) of w_i X(y, x + i);  (Wr, Wg, Wb, m)(y, x) = sum over j = -r .. r (ascending) of w_j T(y + j, x)
+ *             F''_c = clamp(F'_c + wrap_strength (W_c - m F'_c), 0, 1).  Without the wrap F'' = F'.
+ *   out     out = a F'' + (1 - a) Bg;  fg_out = F''.
+ * These hold bit for bit:
+ *   1. where a(p) == 0, out(p) == Bg(p);
+ *   2. where a(p) == 1, out(p) == fg_out(p);
+ *   3. with all five strengths 0 and F in [0, 1]: fg_out == F and out == a F + (1 - a) Bg (fp32, no contraction);
+ *   4. if every existing pixel within Chebyshev distance r of p has a == 1, fg_out(p) equals the fg_out(p) of the same call with wrap_strength = 0 (every
+ *      term of both passes is a zero);
+ *   5. an image's result does not depend on the batch it is in; two calls, host and device pointers, and pointers 4 bytes off a 16-byte boundary all give
+ *      the same bits;
+ *   6. bg_batch = 1 gives the bits of the same background repeated B times.
+ * sdmatte_nodes.harmonize_map and sdmatte_nodes.harmonize_cutout are the same function in torch (equal to fp32 rounding).
+ * Limits: B, H, W >= 1 within SDM_FG_MAX_SIDE / SDM_FG_MAX_PIXELS; luma_strength, chroma_strength, contrast_strength and wrap_strength finite in [0, 1];
+ * wrap_sigma finite in (0, SDM_HZ_MAX_WRAP_SIGMA] when wrap_strength > 0 (so r <= 48); bg_batch 1 or B: SDM_ERR_INVALID otherwise, with a message that
+ * names the argument, and then nothing is queued or written.  Stream contract and pointer kinds as sdm_make_trimap; sdm_last_forward_ms covers the
+ * launches.  Needs no weights.  Kernel launches (csrc/k_harmonize.h), by these names in sdm_kernel_counts and the per-launch profile: `hz_stats` and
+ * `hz_finalize` when luma_strength > 0 or chroma_strength > 0, `hz_rows` when wrap_strength > 0, `hz_compose` always - 4 with everything on, 3 without
+ * the wrap, 2 without the match, 1 with neither; the count never depends on sizes or content; no host readback.  The partial sums (56 bytes per run), the
+ * map and, with the wrap, one plane of 16 bytes per pixel live in the activation arena; host pointers go through the I/O staging. */
+#define SDM_HZ_RUN 4096
+#define SDM_HZ_VAR_FLOOR 9.5367431640625e-07
+#define SDM_HZ_MAX_GAIN 4
+#define SDM_HZ_MIN_WEIGHT 1.0
+#define SDM_HZ_MAX_WRAP_SIGMA 16
+#define SDM_HZ_LUMA_STRENGTH 0.6f
+#define SDM_HZ_CHROMA_STRENGTH 0.8f
+#define SDM_HZ_CONTRAST_STRENGTH 0.5f
+#define SDM_HZ_WRAP_STRENGTH 0.5f
+#define SDM_HZ_WRAP_SIGMA 6.0f
+int sdm_harmonize(sdm_ctx* ctx, const float* fg_bhw3, const float* alpha_bhw, const float* bg_image, int bg_batch, int B, int H, int W,
+                  float luma_strength, float chroma_strength, float contrast_strength, float wrap_strength, float wrap_sigma, float* out_bhw3,
+                  float* fg_out_bhw3, float* map_out_b12, int ptr_kind, void* stream);
+
 /* Memory the engine holds outside any framework allocator: packed weights + activation arena (sized by the largest batch /
  * resolution seen) + I/O staging.  sdm_release_memory frees everything but the weights (the next forward re-allocates). */
 int64_t sdm_resident_bytes(sdm_ctx* ctx);
@@ -584,7 +642,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal / sdm_smooth_alpha_motion / sdm_defocus_background: their launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal / sdm_smooth_alpha_motion / sdm_defocus_background / sdm_harmonize: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
