@@ -25,6 +25,7 @@
 #include "k_motion.h"
 #include "k_defocus.h"
 #include "k_harmonize.h"
+#include "k_metrics.h"
 #include "k_roi.h"
 #include "k_canvas.h"
 #include "k_boxes.h"
@@ -2585,7 +2586,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background, sdm_harmonize) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background, sdm_harmonize, sdm_matte_metrics) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -3816,6 +3817,129 @@ int sdm_clean_mask(sdm_ctx* e, const float* mask, int B, int H, int W, float thr
       }
     }
     if (label_a || stage_b) { tfree(e, sel); tfree(e, area); tfree(e, root); tfree(e, label); }
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// SAD, MSE, Grad and Conn of a matte over the trimap band (k_metrics.h)
+// ------------------------------------------------------------------------------------------------
+extern "C++" {
+template <int R>
+static void mm_launch_pixel(sdm_ctx* e, dim3 grid, const float* pred, const float* gt, const float* trimap, int B, int H, int W, const MmWeights& w, float* rec,
+                            float* q) {
+  auto k = mm_pixel_kernel<R>;
+  SDM_SET_SMEM(k, mm_pixel_smem(R));
+  SDM_LAUNCH(k, grid, dim3(256), mm_pixel_smem(R), e->stream, pred, gt, trimap, B, H, W, w, rec, q);
+}
+}
+
+/* The tile records (32 bytes per tile of 64 x 32 pixels) and, with Conn, the plane Q, the label, root and area planes, the level plane (4 bytes per pixel
+ * each: 20 in all), the selection words and the run partials live in the activation arena.  2 launches without Conn; with it 63: mm_pixel, ten times
+ * (cc_tile, cc_seam, cc_flatten, cc_select x 2, mm_level), mm_conn, mm_finalize - the levels are labelled one after the other on the same three planes. */
+int sdm_matte_metrics(sdm_ctx* e, const float* pred, const float* gt, const float* trimap, int B, int H, int W, float grad_sigma, int with_conn,
+                      double* stats, int32_t* level, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !pred || !gt || !stats) return SDM_ERR_INVALID;
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "matte metrics: bad image size %dx%dx%d", B, H, W);
+  // (with Conn the labels are global pixel indices in an int; the levels are labelled one at a time, so B H W is the labelled pixel count)
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "matte metrics: %dx%dx%d is too large (sides up to %d, %d pixels in all)", B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  if (!std::isfinite(grad_sigma) || !(grad_sigma >= 0.25f) || !(grad_sigma <= 4.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "matte metrics: grad_sigma = %g must be a finite number in [0.25, 4]", (double)grad_sigma);
+  if (with_conn != 0 && with_conn != 1) SDM_FAIL(e, SDM_ERR_INVALID, "matte metrics: with_conn = %d must be 0 or 1", with_conn);
+  if (!with_conn && level) SDM_FAIL(e, SDM_ERR_INVALID, "matte metrics: level_bhw needs with_conn = 1");
+  static_assert(SDM_MM_R == SDM_MM_MAX_GRAD_RADIUS && SDM_MM_LEVELS == SDM_MM_CONN_LEVELS && SDM_MM_NSTAT == SDM_MM_STATS && SDM_MM_REC >= 8, "k_metrics.h is sized for these");
+  // the Gaussian and its derivative, in double from the fp32 sigma, G (x) D scaled to unit L2 norm, rounded to fp32
+  MmWeights wts;
+  memset(&wts, 0, sizeof(wts));
+  {
+    const double s = (double)grad_sigma, kPi = 3.14159265358979323846;
+    const int r = (int)std::ceil(s * std::sqrt(-2.0 * std::log(std::sqrt(2.0 * kPi) * s * 0.01)));
+    wts.r = std::min(SDM_MM_R, std::max(1, r));
+    double g[2 * SDM_MM_R + 1], d[2 * SDM_MM_R + 1], ng = 0.0, nd = 0.0;
+    for (int k = 0; k <= 2 * wts.r; ++k) {
+      const double i = (double)(k - wts.r);
+      g[k] = std::exp(-(i * i) / (2.0 * s * s)) / (s * std::sqrt(2.0 * kPi));
+      d[k] = -i * g[k] / (s * s);
+      ng += g[k] * g[k]; nd += d[k] * d[k];
+    }
+    const double norm = std::sqrt(std::sqrt(ng * nd));
+    for (int k = 0; k <= 2 * wts.r; ++k) { wts.g[k] = (float)(g[k] / norm); wts.d[k] = (float)(d[k] / norm); }
+  }
+  const size_t px = (size_t)B * H * W;
+  const int tiles = sdm_cdiv(H, SDM_MM_TH) * sdm_cdiv(W, SDM_MM_TW), runs = sdm_cdiv(H * W, SDM_MM_RUN_PX);
+  IoSpan in[] = {{(void*)pred, px * 4}, {(void*)gt, px * 4}, {(void*)(trimap ? trimap : pred), trimap ? px * 4 : 0}};      // (an absent plane: no bytes, a valid address)
+  IoSpan outs[] = {{stats, (size_t)B * SDM_MM_STATS * 8}, {level, level ? px * 4 : 0}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_pred = (const float*)in[0].p; const float* d_gt = (const float*)in[1].p; const float* d_tri = trimap ? (const float*)in[2].p : nullptr;
+    double* d_stats = (double*)outs[0].p; int* d_level = level ? (int*)outs[1].p : nullptr;
+    T rec = talloc(e, B, tiles, 1, SDM_MM_REC, 1), q, label, root, area, lev, sel, part;
+    if (with_conn) {
+      q = talloc(e, B, H, W, 1, 1); label = talloc(e, B, H, W, 1, 1); root = talloc(e, B, H, W, 1, 1); area = talloc(e, B, H, W, 1, 1);
+      lev = talloc(e, B, H, W, 1, 1); sel = talloc(e, B, 1, 1, 2, 1); part = talloc(e, B, runs, 1, 1, 1);
+    }
+    if (!e->dry) {
+      const dim3 pgrid((unsigned)(B * tiles));
+      float* d_rec = (float*)rec.p; float* d_q = with_conn ? (float*)q.p : nullptr;
+      prof_begin(e, "mm_pixel", 0, (double)px * (d_tri ? 12 : 8) + (double)B * tiles * 32 + (with_conn ? (double)px * 4 : 0.0));
+      count_kernel("mm_pixel");
+      switch (wts.r) {
+        case 1: mm_launch_pixel<1>(e, pgrid, d_pred, d_gt, d_tri, B, H, W, wts, d_rec, d_q); break;
+        case 2: mm_launch_pixel<2>(e, pgrid, d_pred, d_gt, d_tri, B, H, W, wts, d_rec, d_q); break;
+        case 3: mm_launch_pixel<3>(e, pgrid, d_pred, d_gt, d_tri, B, H, W, wts, d_rec, d_q); break;
+        case 4: mm_launch_pixel<4>(e, pgrid, d_pred, d_gt, d_tri, B, H, W, wts, d_rec, d_q); break;
+        case 5: mm_launch_pixel<5>(e, pgrid, d_pred, d_gt, d_tri, B, H, W, wts, d_rec, d_q); break;
+        case 6: mm_launch_pixel<6>(e, pgrid, d_pred, d_gt, d_tri, B, H, W, wts, d_rec, d_q); break;
+        case 7: mm_launch_pixel<7>(e, pgrid, d_pred, d_gt, d_tri, B, H, W, wts, d_rec, d_q); break;
+        case 8: mm_launch_pixel<8>(e, pgrid, d_pred, d_gt, d_tri, B, H, W, wts, d_rec, d_q); break;
+        default: mm_launch_pixel<9>(e, pgrid, d_pred, d_gt, d_tri, B, H, W, wts, d_rec, d_q); break;
+      }
+      prof_end(e);
+      if (with_conn) {
+        const int cc_tiles = B * sdm_cdiv(H, SDM_CC_T) * sdm_cdiv(W, SDM_CC_T), chunks = B * sdm_cdiv(H * W, SDM_CC_PX);
+        const int vec = (H * W) % 4 == 0 ? 1 : 0;      // (the planes start on arena boundaries of 256 bytes)
+        int* d_label = (int*)label.p; int* d_root = (int*)root.p; int* d_area = (int*)area.p; int* d_sel = (int*)sel.p; int* d_lev = (int*)lev.p;
+        for (int k = 1; k <= SDM_MM_LEVELS; ++k) {
+          // S_k = { Q >= k } = { Q > k - 0.5 }, 4-connected; the first tile of every image resets the selection words
+          prof_begin(e, "cc_tile", 0, (double)px * 12);
+          count_kernel("cc_tile");
+          SDM_LAUNCH(cc_tile_kernel, dim3((unsigned)cc_tiles), dim3(256), 0, e->stream, (const float*)d_q, d_label, d_area, B, H, W, (float)k - 0.5f, 0, 0, d_sel,
+                     (int*)nullptr);
+          prof_end(e);
+          prof_begin(e, "cc_seam", 0, (double)px * 4 * 3 / SDM_CC_T);
+          count_kernel("cc_seam");
+          SDM_LAUNCH(cc_seam_kernel, dim3((unsigned)cc_tiles), dim3(256), 0, e->stream, d_label, B, H, W, 0);
+          prof_end(e);
+          prof_begin(e, "cc_flatten", 0, (double)px * 8);
+          count_kernel("cc_flatten");
+          SDM_LAUNCH(cc_flatten_kernel, dim3((unsigned)(B * sdm_cdiv(H * W, SDM_CC_FLAT_PX))), dim3(256), 0, e->stream, (const int*)d_label, d_root, d_area, B, H, W,
+                     0, vec, (int*)nullptr);
+          prof_end(e);
+          for (int phase = 0; phase < 2; ++phase) {
+            prof_begin(e, "cc_select", 0, (double)px * 4);
+            count_kernel("cc_select");
+            SDM_LAUNCH(cc_select_kernel, dim3((unsigned)chunks), dim3(256), 0, e->stream, (const int*)d_root, (const int*)d_area, B, H, W, phase, vec, d_sel);
+            prof_end(e);
+          }
+          prof_begin(e, "mm_level", 0, (double)px * (k > 1 ? 12 : 8));
+          count_kernel("mm_level");
+          SDM_LAUNCH(mm_level_kernel, dim3((unsigned)chunks), dim3(256), 0, e->stream, (const int*)d_root, (const int*)d_sel, d_lev, B, H, W, k, vec);
+          prof_end(e);
+        }
+        prof_begin(e, "mm_conn", 0, (double)px * ((d_tri ? 16 : 12) + (d_level ? 4 : 0)));
+        count_kernel("mm_conn");
+        SDM_LAUNCH(mm_conn_kernel, dim3((unsigned)(B * runs)), dim3(256), 0, e->stream, d_pred, d_gt, d_tri, (const int*)d_lev, B, H, W, (float*)part.p, d_level);
+        prof_end(e);
+      }
+      prof_begin(e, "mm_finalize", 0, (double)B * tiles * 32 + (with_conn ? (double)B * runs * 4 : 0.0));
+      count_kernel("mm_finalize");
+      SDM_LAUNCH(mm_finalize_kernel, dim3((unsigned)B), dim3(256), 0, e->stream, (const float*)d_rec, tiles, with_conn ? (const float*)part.p : (const float*)nullptr,
+                 runs, B, d_stats);
+      prof_end(e);
+    }
+    if (with_conn) { tfree(e, part); tfree(e, sel); tfree(e, lev); tfree(e, area); tfree(e, root); tfree(e, label); tfree(e, q); }
+    tfree(e, rec);
     return 0;
   });
 }

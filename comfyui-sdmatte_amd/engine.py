@@ -83,7 +83,7 @@ EXPORTS = [
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
-    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background", "sdm_harmonize",
+    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background", "sdm_harmonize", "sdm_matte_metrics",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_stats", "sdm_op_gn_partials", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias", "sdm_debug_patch_token_map", "sdm_op_groupnorm_p3", "sdm_op_gemm_p3_tokens", "sdm_op_mask_bias_tokens", "sdm_op_active_tiles",
@@ -135,6 +135,7 @@ class Bindings:
             "sdm_smooth_alpha_motion": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, vp, i32, vp]),
             "sdm_defocus_background": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, vp]),
             "sdm_harmonize": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
+            "sdm_matte_metrics": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
             "sdm_resident_bytes": (i64, [vp]),
@@ -1105,6 +1106,51 @@ class Engine:
             self.synchronize()
         res = (out, ) + ((fg_out, ) if return_fg else ()) + ((map_out, ) if return_map else ())
         return res[0] if len(res) == 1 else res
+
+    # SDM_MM_* (include/sdmatte.h)
+    METRICS_GRAD_SIGMA = 1.4
+    METRICS_KEYS = ("n", "sad", "mse", "grad", "conn", "max_abs", "sad_frame", "mse_frame")
+
+    @staticmethod
+    def metrics_from_raw(raw, hw):
+        """The literature's units from the [B,8] raw sums of sdm_matte_metrics: SAD, Grad and Conn in thousands, the squared error as a mean (over the
+        band for `mse`, 0 when the band is empty; over the `hw` pixels of the frame for `mse_frame`), n and max|e| as they are."""
+        n = raw[:, 0]
+        return {"n": n, "sad": raw[:, 1] / 1000.0, "mse": raw[:, 2] / torch.clamp(n, min=1.0), "grad": raw[:, 3] / 1000.0, "conn": raw[:, 4] / 1000.0,
+                "max_abs": raw[:, 5], "sad_frame": raw[:, 6] / 1000.0, "mse_frame": raw[:, 7] / float(hw), "raw": raw}
+
+    def matte_metrics(self, pred, gt, trimap=None, grad_sigma=1.4, conn=True, return_levels=False, sync=True):
+        """Score a matte (sdm_matte_metrics, defined in include/sdmatte.h): SAD, MSE, Grad and Conn of `pred` against `gt` ([B,H,W] each) over the unknown
+        band of `trimap` ([B,H,W], or None for the whole frame).  Returns a dict of fp64 tensors [B] on the inputs' device in the literature's units:
+        `n` (pixels of the band), `sad`, `grad`, `conn` (sums / 1000), `mse` (squared error / max(n, 1)), `max_abs`, and over the whole frame `sad_frame`
+        (/ 1000) and `mse_frame` (/ (H W)); `raw` holds the [B,8] sums as they cross the C ABI.  With return_levels (needs conn) `levels` is the int32
+        [B,H,W] connectivity level map.  2 kernel launches without conn, 63 with it.  Needs no loaded weights.  `sdmatte_nodes.matte_metrics` is the
+        same function in torch."""
+        if pred.dim() != 3 or pred.numel() == 0:
+            raise ValueError(f"matte_metrics: pred must be a non-empty [B,H,W], got {tuple(pred.shape)}")
+        B, H, W = (int(v) for v in pred.shape)
+        if tuple(gt.shape) != (B, H, W) or (trimap is not None and tuple(trimap.shape) != (B, H, W)):
+            raise ValueError(f"matte_metrics: gt and trimap must be [B,H,W] = {(B, H, W)}, got {tuple(gt.shape)}"
+                             + (f" and {tuple(trimap.shape)}" if trimap is not None else ""))
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"matte_metrics: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        grad_sigma = self._check_f32_range("matte_metrics", "grad_sigma", grad_sigma, 0.25, 4.0)
+        if return_levels and not conn:
+            raise ValueError("matte_metrics: return_levels needs conn=True")
+        pred = pred.float().contiguous()
+        gt = gt.float().contiguous()
+        trimap = trimap.float().contiguous() if trimap is not None else None
+        raw = torch.empty(B, 8, dtype=torch.float64, device=pred.device)
+        levels = torch.empty(B, H, W, dtype=torch.int32, device=pred.device) if return_levels else None
+        stream = self._check_io("matte_metrics", pred, gt, trimap, raw, levels)
+        self._check(self.lib.sdm_matte_metrics(self.h, _ptr(pred), _ptr(gt), _ptr(trimap), B, H, W, grad_sigma, 1 if conn else 0, _ptr(raw), _ptr(levels),
+                                               self._kind(pred), stream), "sdm_matte_metrics")
+        if sync:
+            self.synchronize()
+        res = self.metrics_from_raw(raw, H * W)
+        if return_levels:
+            res["levels"] = levels
+        return res
 
     def synchronize(self):
         self._check(self.lib.sdm_synchronize(self.h), "sdm_synchronize")

@@ -33,6 +33,8 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
     disc blur that does not see the subject, so no halo), in two kernel launches; `defocus_background` below is its torch restatement;
   * and one registered only with SDMATTE_HARMONIZE_NODE=1: `SDMatteHarmonize` sits the cut-out in a new scene (colour match in opponent coordinates,
     light wrap along the edge, then "over"), in one to four kernel launches; `harmonize_map` / `harmonize_cutout` below are its torch restatement;
+  * and one registered only with SDMATTE_METRICS_NODE=1: `SDMatteMetrics` scores an alpha against a ground truth with the matting literature's SAD, MSE,
+    Grad and Conn over the trimap's unknown band, on the GPU; `matte_metrics` below is its torch restatement;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -1107,6 +1109,115 @@ def harmonize_cutout(fg, alpha, bg, luma_strength=0.6, chroma_strength=0.8, cont
     return res[0] if len(res) == 1 else res
 
 
+def matte_metric_weights(grad_sigma=1.4):
+    """(r, G, D) of sdm_matte_metrics: the Gaussian and its derivative for offsets -r .. r, computed in double from the fp32 sigma, scaled so that G (x) D
+    has unit L2 norm, rounded to fp32 (numpy arrays)."""
+    import numpy as np
+    s = float(np.float32(grad_sigma))
+    r = min(9, max(1, int(np.ceil(s * np.sqrt(-2.0 * np.log(np.sqrt(2.0 * np.pi) * s * 0.01))))))
+    i = np.arange(-r, r + 1, dtype=np.float64)
+    g = np.exp(-(i * i) / (2.0 * s * s)) / (s * np.sqrt(2.0 * np.pi))
+    d = -i * g / (s * s)
+    norm = np.sqrt(np.sqrt((g * g).sum() * (d * d).sum()))
+    return r, (g / norm).astype(np.float32), (d / norm).astype(np.float32)
+
+
+def _gradient_magnitude(a, r, G, D):
+    """a [B,H,W] -> m(a) of sdm_matte_metrics in a's dtype: replicate padding, the inner sums over the rows first, both sums ascending."""
+    B, H, W = a.shape
+    pad = torch.nn.functional.pad(a.unsqueeze(1), (r, r, r, r), mode="replicate")[:, 0]
+    vg = torch.zeros(B, H, W + 2 * r, dtype=a.dtype, device=a.device)
+    vd = torch.zeros_like(vg)
+    for k in range(2 * r + 1):
+        vg = vg + float(G[k]) * pad[:, k:k + H, :]
+        vd = vd + float(D[k]) * pad[:, k:k + H, :]
+    ax = torch.zeros(B, H, W, dtype=a.dtype, device=a.device)
+    ay = torch.zeros_like(ax)
+    for k in range(2 * r + 1):
+        ax = ax + float(D[k]) * vg[:, :, k:k + W]
+        ay = ay + float(G[k]) * vd[:, :, k:k + W]
+    return torch.sqrt(ax * ax + ay * ay)
+
+
+def connectivity_levels(c):
+    """c = min(p, g) [B,H,W] -> int32 [B,H,W]: the level map L of sdm_matte_metrics, exact (compares, counts and `_component_roots` only).  Level k's
+    set is c >= (float)k / 10.0f; its largest 4-connected component (the smallest root on a tie) keeps the pixels that reached level k - 1."""
+    import numpy as np
+    cn = c.detach().cpu().numpy()
+    B, H, W = cn.shape
+    L = np.zeros((B, H, W), np.int32)
+    for k in range(1, 11):
+        t = np.float32(k) / np.float32(10.0)
+        for b in range(B):
+            cls = cn[b] >= t
+            if not cls.any():
+                continue
+            roots = _component_roots(cls, False)
+            area = np.bincount(roots[cls], minlength=H * W)
+            keep = int(np.argmax(area))                       # the first maximum: the smallest root among the largest components
+            L[b][(L[b] == k - 1) & (roots == keep)] = k
+    return torch.from_numpy(L).to(c.device)
+
+
+def matte_metrics(pred, gt, trimap=None, grad_sigma=1.4, conn=True, return_levels=False):
+    """`Engine.matte_metrics` in torch, on the tensors' device (the labelling alone goes through numpy on the CPU; the definition is in include/sdmatte.h, sdm_matte_metrics), with the same return value: a dict of
+    fp64 tensors [B] `n`, `sad`, `mse`, `grad`, `conn`, `max_abs`, `sad_frame`, `mse_frame` in the literature's units, `raw` [B,8], and `levels` with
+    return_levels.  The terms and their sums are formed in the dtype of `pred` (fp32 or fp64), so the function is both the fp32 restatement and the
+    fp64 reference; the band test, the thresholds, theta and the filter weights are the fp32 values of the definition in either case, and the level map
+    is exact."""
+    import numpy as np
+    if pred.dim() != 3 or pred.numel() == 0 or gt.shape != pred.shape or (trimap is not None and trimap.shape != pred.shape):
+        raise ValueError(f"matte_metrics: pred, gt and trimap must be equal non-empty [B,H,W], got {tuple(pred.shape)}, {tuple(gt.shape)}"
+                         + (f", {tuple(trimap.shape)}" if trimap is not None else ""))
+    if return_levels and not conn:
+        raise ValueError("matte_metrics: return_levels needs conn=True")
+    sigma = float(np.float32(grad_sigma))
+    if not (np.isfinite(sigma) and 0.25 <= sigma <= 4.0):
+        raise ValueError(f"matte_metrics: grad_sigma must be a finite number in [0.25, 4], got {grad_sigma!r}")
+    dt = pred.dtype if pred.dtype in (torch.float32, torch.float64) else torch.float32
+    B, H, W = (int(v) for v in pred.shape)
+    dev = pred.device
+    clean = lambda t: torch.clamp(torch.nan_to_num(t.detach().to(dt), nan=0.0, posinf=1.0, neginf=0.0), 0.0, 1.0)
+    p, g = clean(pred), clean(gt)
+    region = torch.ones(B, H, W, dtype=torch.bool, device=dev) if trimap is None else ((trimap.detach().float() - 0.5).abs() < 0.25)
+    e = p - g
+    ae, ee = e.abs(), e * e
+    r, G, D = matte_metric_weights(sigma)
+    dm = _gradient_magnitude(p, r, G, D) - _gradient_magnitude(g, r, G, D)
+    zero = torch.zeros((), dtype=dt, device=dev)
+    over = lambda t: torch.where(region, t, zero).reshape(B, -1).sum(1)
+    raw = torch.zeros(B, 8, dtype=torch.float64, device=dev)
+    raw[:, 0] = region.reshape(B, -1).sum(1).double()
+    raw[:, 1], raw[:, 2], raw[:, 3] = over(ae).double(), over(ee).double(), over(dm * dm).double()
+    raw[:, 5] = torch.where(region, ae, zero).reshape(B, -1).max(1).values.double()
+    raw[:, 6], raw[:, 7] = ae.reshape(B, -1).sum(1).double(), ee.reshape(B, -1).sum(1).double()
+    levels = None
+    if conn:
+        levels = connectivity_levels(torch.minimum(p, g))
+        l = (levels.float() / 10.0).to(dt)                    # t_L: a true fp32 division
+        theta = float(np.float32(0.15))
+
+        def phi(a):
+            d = a - l
+            return 1.0 - torch.where(d >= theta, d, zero)
+        raw[:, 4] = over((phi(p) - phi(g)).abs()).double()
+    from .engine import Engine
+    res = Engine.metrics_from_raw(raw, H * W)              # the literature's units: one definition for the call and its restatement
+    if return_levels:
+        res["levels"] = levels
+    return res
+
+
+def metrics_report(res):
+    """(text, means) of a `matte_metrics` result: one line per image and a mean line; means = (sad, mse, grad, conn) as floats."""
+    rows = [[float(res[k][b]) for k in ("sad", "mse", "grad", "conn")] for b in range(int(res["n"].shape[0]))]
+    lines = [f"image {b}: SAD {r[0]:.4f}  MSE {r[1]:.6f}  Grad {r[2]:.4f}  Conn {r[3]:.4f}  (n = {int(res['n'][b])}, max|e| = {float(res['max_abs'][b]):.4f})"
+             for b, r in enumerate(rows)]
+    means = tuple(sum(r[i] for r in rows) / len(rows) for i in range(4))
+    lines.append(f"mean: SAD {means[0]:.4f}  MSE {means[1]:.6f}  Grad {means[2]:.4f}  Conn {means[3]:.4f}")
+    return "\n".join(lines), means
+
+
 def fit_background(bg, H, W):
     """bg [N,h,w,3] -> [N,H,W,3]: scaled (bilinear, antialiased) to cover H x W, then centre-cropped; returned as it is when the size is right."""
     import torch.nn.functional as Fn
@@ -1783,6 +1894,40 @@ class SDMatteHarmonize:
         return (out.cpu(), fg_out.cpu())
 
 
+class SDMatteMetrics:
+    """Alpha + ground truth (+ trimap) -> the matting literature's SAD, MSE, Grad and Conn over the trimap's unknown band (the whole frame without a
+    trimap), on the GPU: 2 kernel launches, 63 with connectivity.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"alpha": ("MASK", {"tooltip": "the alpha matte to score"}),
+                             "ground_truth": ("MASK", {"tooltip": "the reference alpha"})},
+                "optional": {"trimap": ("MASK", {"tooltip": "the trimap: only its unknown band (values near 0.5) is scored; without it the whole frame"}),
+                             "grad_sigma": ("FLOAT", {"default": 1.4, "min": 0.25, "max": 4.0, "step": 0.05, "tooltip": "sigma of the Grad metric's Gaussian derivative"}),
+                             "connectivity": ("BOOLEAN", {"default": True, "tooltip": "also compute Conn (ten labellings per image)"}),
+                             "force_cpu": ("BOOLEAN", {"default": False, "tooltip": "evaluate the torch restatement on the CPU instead of the GPU call"})}}
+
+    RETURN_TYPES = ("STRING", "FLOAT", "FLOAT", "FLOAT", "FLOAT")
+    RETURN_NAMES = ("report", "sad", "mse", "grad", "conn")
+    FUNCTION = "score"
+    CATEGORY = "Matting/SDMatte"
+    OUTPUT_NODE = True
+
+    def score(self, alpha, ground_truth, trimap=None, grad_sigma=1.4, connectivity=True, force_cpu=False):
+        planes = [alpha, ground_truth] + ([trimap] if trimap is not None else [])
+        planes = [t.unsqueeze(0) if t.dim() == 2 else t for t in planes]
+        if any(t.dim() != 3 or tuple(t.shape) != tuple(planes[0].shape) for t in planes):
+            raise ValueError(f"[SDMatte] alpha, ground truth and trimap must be equal [B,H,W], got {[tuple(t.shape) for t in planes]}")
+        if force_cpu:      # an explicit request, never a silent substitute: the same function in torch
+            res = matte_metrics(*(t.detach().cpu().float() for t in planes), grad_sigma=float(grad_sigma), conn=bool(connectivity))
+        else:
+            device = _torch_device()
+            res = _trimap_engine(device).matte_metrics(*(t.detach().to(device) for t in planes), grad_sigma=float(grad_sigma), conn=bool(connectivity))
+            res = {k: v.cpu() for k, v in res.items()}
+        text, means = metrics_report(res)
+        return (text, ) + means
+
+
 def node_mappings(extra: bool, foreground: bool = False, refine: bool = False, clean: bool = False, roi: bool = False, canvas: bool = False,
                   subjects: bool = False, edge: bool = False, video: bool = False, motion: bool = False, defocus: bool = False):
     """(NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS): the reference's surface, plus the two mask nodes when `extra`, plus the foreground
@@ -1838,9 +1983,18 @@ def with_harmonize_node(mappings, harmonize: bool = True):
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1, SDMATTE_HARMONIZE_NODE=1), like the multi-GPU fan-out
+def with_metrics_node(mappings, metrics: bool = True):
+    """(classes, names) of `mappings` plus `SDMatteMetrics` when `metrics`; the argument is not modified (as `with_harmonize_node`)."""
+    classes, names = dict(mappings[0]), dict(mappings[1])
+    if metrics:
+        classes["SDMatteMetrics"] = SDMatteMetrics
+        names["SDMatteMetrics"] = "SDMatte Metrics (SAD / MSE / Grad / Conn)"
+    return classes, names
+
+
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1, SDMATTE_HARMONIZE_NODE=1, SDMATTE_METRICS_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
-NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_harmonize_node(node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
+NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_metrics_node(with_harmonize_node(node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
                                                                 os.environ.get("SDMATTE_REFINE_NODE") == "1",
                                                                 os.environ.get("SDMATTE_CLEAN_NODE") == "1",
@@ -1851,4 +2005,5 @@ NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_harmonize_node(node_mappi
                                                                 os.environ.get("SDMATTE_VIDEO_NODE") == "1",
                                                                 os.environ.get("SDMATTE_MOTION_NODE") == "1",
                                                                 os.environ.get("SDMATTE_DEFOCUS_NODE") == "1"),
-                                                                      os.environ.get("SDMATTE_HARMONIZE_NODE") == "1")
+                                                                      os.environ.get("SDMATTE_HARMONIZE_NODE") == "1"),
+                                                                      os.environ.get("SDMATTE_METRICS_NODE") == "1")

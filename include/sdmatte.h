@@ -617,6 +617,50 @@ int sdm_harmonize(sdm_ctx* ctx, const float* fg_bhw3, const float* alpha_bhw, co
                   float luma_strength, float chroma_strength, float contrast_strength, float wrap_strength, float wrap_sigma, float* out_bhw3,
                   float* fg_out_bhw3, float* map_out_b12, int ptr_kind, void* stream);
 
+/* Score a matte (beyond the reference): SAD, MSE, Grad and Conn, the four numbers of the matting literature (Rhemann et al., "A perceptually motivated
+ * online benchmark for image matting"; the SDMatte paper reports them), over the unknown band of the trimap.  No weights.
+ * pred and gt are fp32 [B,H,W]; trimap is fp32 [B,H,W] in [0, 1] or NULL; stats is fp64 [B][SDM_MM_STATS]; level is int32 [B,H,W] or NULL; all of one
+ * pointer kind.
+ *   p, g    pred and gt with NaN -> 0, then clamped to [0, 1] (the rule of sdm_estimate_foreground).
+ *   R       { q : |trimap[q] - 0.5| < 0.25 }: one fp32 subtraction, fabsf and one compare, so a NaN lies outside.  With trimap == NULL R is the whole
+ *           frame, bit for bit what a plane of 0.5 gives.
+ *   terms   fp32, no FMA contraction: e = p - g;  SAD term |e|;  SSE term e e.
+ *   Grad    the Gaussian-derivative form.  r = ceil(sigma sqrt(-2 ln(sqrt(2 pi) sigma 0.01))) (4 at sigma = 1.4, at most SDM_MM_MAX_GRAD_RADIUS);
+ *           G_i = exp(-i^2 / (2 sigma^2)) / (sigma sqrt(2 pi)), D_i = -i G_i / sigma^2 for i = -r .. r, both divided by sqrt(sqrt(sum G^2 sum D^2)), so
+ *           that the 2-D kernel G (x) D has unit L2 norm; computed in double from the fp32 sigma and rounded to fp32 (as the weights of
+ *           sdm_compose_canvas and sdm_harmonize).  A pixel beyond the frame takes the value of the nearest pixel of the frame.  For a plane a:
+ *             a_x(y, x) = sum over j of D_j (sum over i of G_i a(y + i, x + j)),  a_y(y, x) = sum over j of G_j (sum over i of D_i a(y + i, x + j)),
+ *           the inner sums (over the rows, i) first, both sums ascending in their index, fp32, no FMA contraction;
+ *           m(a) = sqrtf(a_x^2 + a_y^2);  Grad term (m(p) - m(g))^2.  The planes are NOT min-max normalised first, as the common Python port does: that
+ *           step is the identity whenever a plane reaches 0 and 1, which a ground truth does.
+ *   Conn    only when with_conn != 0 (step 0.1 and theta = SDM_MM_CONN_THETA of the common code).  t_k = (float)k / 10.0f for k = 0 .. 10, true fp32
+ *           divisions (t_10 == 1.0f);  c = min(p, g);  S_k = { q : c[q] >= t_k } over the WHOLE FRAME, not over R;  Omega_k = the 4-connected component of
+ *           S_k with the largest area, on a tie the one that contains the smallest pixel index, empty when S_k is.  L(q) = the largest k in 0 .. 10 with
+ *           q in Omega_j for every 1 <= j <= k: a pixel is frozen at the first level it drops out of and stays frozen even if a later Omega contains it
+ *           again (the Omega_k are not nested).  l = t_L;  phi(a) = 1 - d [d >= 0.15f] with d = a - l;  Conn term |phi(p) - phi(g)|.  level receives L:
+ *           integers and compares only, so every implementation agrees exactly.  With with_conn == 0, level must be NULL and stats[4] is 0.
+ *   stats[b]  0: n = |R|;  1: sum over R of |e|;  2: sum over R of e e;  3: sum over R of the Grad term;  4: sum over R of the Conn term;  5: max |e| over R
+ *           (0 when R is empty);  6: sum of |e| over the frame;  7: sum of e e over the frame.  Raw sums: the literature's units (SAD / 1000, SSE / n,
+ *           Grad / 1000, Conn / 1000) are made by the caller.
+ *   sums    the fp32 terms are added in fp32 inside a unit - a tile of 64 columns x 32 rows for entries 1-3 and 5-7, a run of 4096 consecutive pixels
+ *           (row-major) for entry 4 - in a fixed order (shuffle and LDS trees, no float atomics); the units of an image are added in fp64 in ascending
+ *           order.  An image's eight numbers therefore do not depend on the batch it is in, on the pointer kind, or on the run.  n and the maximum are exact.
+ * sdmatte_nodes.matte_metrics is the same function in torch (the level map exactly, the sums to the rounding of its dtype).
+ * Limits: grad_sigma finite in [0.25, 4] (so r <= 9); with_conn 0 or 1; level NULL unless with_conn; B, H, W >= 1 within SDM_FG_MAX_SIDE /
+ * SDM_FG_MAX_PIXELS (the ten levels are labelled one after the other, labels being global pixel indices, so B H W is also the labelled pixel count):
+ * SDM_ERR_INVALID otherwise, also for an unknown ptr_kind, and then nothing is queued or written.  Stream contract, pointer kinds, staging and arena as
+ * sdm_harmonize; sdm_last_forward_ms covers the launches.  Needs no weights.  No host readback.  Kernel launches (csrc/k_metrics.h, csrc/k_cclabel.h), by
+ * these names in sdm_kernel_counts and the per-launch profile: `mm_pixel` and `mm_finalize` always; with Conn also, per level, `cc_tile`, `cc_seam`,
+ * `cc_flatten`, `cc_select` x 2 and `mm_level` (60 in all), and `mm_conn` - 2 launches without Conn, 63 with it, whether or not level is given (mm_conn
+ * writes it); the count never depends on B, H, W or the content.  With Conn five planes of 4 bytes per pixel live in the activation arena. */
+#define SDM_MM_STATS 8
+#define SDM_MM_GRAD_SIGMA 1.4f
+#define SDM_MM_MAX_GRAD_RADIUS 9
+#define SDM_MM_CONN_LEVELS 10
+#define SDM_MM_CONN_THETA 0.15f
+int sdm_matte_metrics(sdm_ctx* ctx, const float* pred_bhw, const float* gt_bhw, const float* trimap_bhw /* may be NULL */, int B, int H, int W,
+                      float grad_sigma, int with_conn, double* stats_b8, int32_t* level_bhw /* may be NULL */, int ptr_kind, void* stream);
+
 /* Memory the engine holds outside any framework allocator: packed weights + activation arena (sized by the largest batch /
  * resolution seen) + I/O staging.  sdm_release_memory frees everything but the weights (the next forward re-allocates). */
 int64_t sdm_resident_bytes(sdm_ctx* ctx);
@@ -642,7 +686,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal / sdm_smooth_alpha_motion / sdm_defocus_background / sdm_harmonize: their launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal / sdm_smooth_alpha_motion / sdm_defocus_background / sdm_harmonize / sdm_matte_metrics: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
