@@ -29,6 +29,7 @@
 #include "k_roi.h"
 #include "k_canvas.h"
 #include "k_boxes.h"
+#include "k_tiles.h"
 #include "k_distance.h"
 #include "../../include/sdmatte.h"
 
@@ -2586,7 +2587,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background, sdm_harmonize, sdm_matte_metrics) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background, sdm_harmonize, sdm_matte_metrics, sdm_band_tiles, sdm_apply_matte_tiles) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -4058,6 +4059,122 @@ int sdm_apply_matte_boxes(sdm_ctx* e, const float* image, const float* trimap, i
                  (float)tail.c, (float)(1.0 - tail.c));
     }
     tfree(e, a); tfree(e, plane); tfree(e, x16); tfree(e, list);
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// tiles along the unknown band, and the node call that blends them into the frame (k_tiles.h)
+// ------------------------------------------------------------------------------------------------
+static_assert(SDM_TL_LIST == SDM_TILES_MAX && SDM_TILES_MAX == SDM_BOXES_MAX_TOTAL && SDM_TL_WORDS * 32 == SDM_TILES_MAX_GRID && SDM_TL_AXIS >= SDM_TILES_MAX_GRID,
+              "tile limits");
+
+/* The flag words (SDM_TL_WORDS per image) live in the activation arena.  Three launches, whatever else the arguments are. */
+int sdm_band_tiles(sdm_ctx* e, const float* trimap, int B, int H, int W, float band_lo, float band_hi, int tile, int overlap, int max_tiles, int32_t* tiles,
+                   int32_t* count, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !trimap || !tiles) return SDM_ERR_INVALID;
+  TRY(roi_check(e, "band tiles", B, H, W, 0.0f, 0, 0, 0));
+  if (!std::isfinite(band_lo) || !std::isfinite(band_hi) || !(band_lo >= 0.0f) || !(band_lo < band_hi) || !(band_hi <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "band tiles: band_lo = %g, band_hi = %g must be finite with 0 <= band_lo < band_hi <= 1", (double)band_lo, (double)band_hi);
+  if (tile < 16 || tile > SDM_FG_MAX_SIDE) SDM_FAIL(e, SDM_ERR_INVALID, "band tiles: tile = %d outside 16 .. %d", tile, SDM_FG_MAX_SIDE);
+  if (overlap < 0 || overlap > tile / 2) SDM_FAIL(e, SDM_ERR_INVALID, "band tiles: overlap = %d outside 0 .. tile / 2 = %d", overlap, tile / 2);
+  if (max_tiles < 1 || max_tiles > SDM_TILES_MAX) SDM_FAIL(e, SDM_ERR_INVALID, "band tiles: max_tiles = %d outside 1 .. %d", max_tiles, SDM_TILES_MAX);
+  const TilesAxis ay = tiles_axis(H, tile, overlap), ax = tiles_axis(W, tile, overlap);
+  if ((long long)ay.n * ax.n > SDM_TILES_MAX_GRID)
+    SDM_FAIL(e, SDM_ERR_INVALID, "band tiles: a grid of %d x %d cells is more than %d (tile = %d is too small for %dx%d)", ay.n, ax.n, SDM_TILES_MAX_GRID, tile, H, W);
+  const size_t px = (size_t)B * H * W;
+  const int K = max_tiles;
+  IoSpan in[] = {{(void*)trimap, px * 4}}, outs[] = {{tiles, (size_t)B * K * 20}, {count, count ? (size_t)B * 4 : 0}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_plane = (const float*)in[0].p; int* d_tiles = (int*)outs[0].p; int* d_count = (int*)outs[1].p;
+    T flags = talloc(e, B, 1, 1, SDM_TL_WORDS, 1);
+    if (!e->dry) {
+      unsigned int* d_flags = (unsigned int*)flags.p;
+      prof_begin(e, "tiles_init", 0, (double)B * SDM_TL_WORDS * 4);
+      count_kernel("tiles_init");
+      SDM_LAUNCH(tiles_init_kernel, dim3((unsigned)sdm_cdiv(B * SDM_TL_WORDS, 256)), dim3(256), 0, e->stream, d_flags, B);
+      prof_end(e);
+      const dim3 grid((unsigned)(B * sdm_cdiv(H * W, SDM_ROI_PX)));
+      prof_begin(e, "tiles_mark", 0, (double)px * 4);
+      count_kernel("tiles_mark");
+      if (W % 4 == 0 && aligned16(d_plane)) SDM_LAUNCH((tiles_mark_kernel<true>), grid, dim3(256), 0, e->stream, d_plane, d_flags, B, H, W, band_lo, band_hi, ay, ax);
+      else SDM_LAUNCH((tiles_mark_kernel<false>), grid, dim3(256), 0, e->stream, d_plane, d_flags, B, H, W, band_lo, band_hi, ay, ax);
+      prof_end(e);
+      prof_begin(e, "tiles_list", 0, (double)B * (SDM_TL_WORDS * 4 + K * 20 + 4));
+      count_kernel("tiles_list");
+      SDM_LAUNCH(tiles_list_kernel, dim3((unsigned)sdm_cdiv(B, 64)), dim3(64), 0, e->stream, (const unsigned int*)d_flags, d_tiles, d_count, B, K, ay, ax);
+      prof_end(e);
+    }
+    tfree(e, flags);
+    return 0;
+  });
+}
+
+/* sdm_apply_matte_boxes with the weighted blend of k_tiles.h in the place of the maximum, and a base for the pixels outside every tile.  N = 0 runs the blend
+ * and the tail only: no list, no model input, no model pass. */
+int sdm_apply_matte_tiles(sdm_ctx* e, const float* image, const float* trimap, int B, int H, int W, int S, int is_transparent, const int32_t* tiles, int N,
+                          int feather_px, const float* base, int output_mode, int mask_refine, double trimap_constraint, float* alpha, float* matted,
+                          int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !trimap || !alpha || !matted) return SDM_ERR_INVALID;
+  if (!e->finalized) SDM_FAIL(e, SDM_ERR_STATE, "weights not finalised: call sdm_load_tensor(...) and sdm_finalize_weights first");
+  if (output_mode < 0 || output_mode > 2) SDM_FAIL(e, SDM_ERR_INVALID, "unknown output mode %d", output_mode);
+  if (N < 0 || N > SDM_TILES_MAX) SDM_FAIL(e, SDM_ERR_INVALID, "apply matte tiles: N = %d outside 0 .. %d", N, SDM_TILES_MAX);
+  if (N > 0 && !tiles) SDM_FAIL(e, SDM_ERR_INVALID, "apply matte tiles: tiles_n5 is NULL with N = %d", N);
+  if (feather_px < 0 || feather_px > SDM_TILES_MAX_FEATHER)
+    SDM_FAIL(e, SDM_ERR_INVALID, "apply matte tiles: feather_px = %d outside 0 .. %d", feather_px, SDM_TILES_MAX_FEATHER);
+  if (S <= 0 || S % 64) SDM_FAIL(e, SDM_ERR_INVALID, "inference size must be a positive multiple of 64 (got %dx%d)", S, S);
+  TRY(roi_check(e, "apply matte tiles", B, H, W, 0.0f, 0, 0, 0));
+  std::vector<int32_t> it((size_t)std::max(N, 1), is_transparent ? 1 : 0);
+  NodeTail tail; tail.output_mode = output_mode; tail.mask_refine = mask_refine ? 1 : 0; tail.c = trimap_constraint;
+  const size_t px = (size_t)B * H * W;
+  // (an empty list and an absent base: no bytes behind a valid address)
+  IoSpan in[] = {{(void*)image, px * 12}, {(void*)trimap, px * 4}, {(void*)(N ? (const void*)tiles : (const void*)image), (size_t)N * 20},
+                 {(void*)(base ? base : image), base ? px * 4 : 0}};
+  IoSpan outs[] = {{alpha, px * 4}, {matted, px * 4 * tail.channels()}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_img = (const float*)in[0].p; const float* d_tri = (const float*)in[1].p; const int* d_tiles = (const int*)in[2].p;
+    const float* d_base = base ? (const float*)in[3].p : nullptr;
+    float* d_out = (float*)outs[0].p; float* d_matted = (float*)outs[1].p;
+    T list, x16, plane, a;
+    if (N) {
+      if (e->dry) TRY(prepare_variants(e, N, it.data(), nullptr, 4, 0));
+      list = talloc(e, N, 1, 1, 5, 1);
+      x16 = talloc(e, 2 * N, S, S, 16, e->act_f32);
+      plane = talloc(e, N, S, S, 1, 1);
+      if (!e->dry) {
+        const unsigned nb = (unsigned)(((long)N * S * S + 255) / 256);
+        void* img16 = x16.p;
+        void* tri16 = (unsigned char*)x16.p + (size_t)N * S * S * 16 * fmt_bytes(x16.f32);
+        prof_begin(e, "boxes_sanitize", 0, (double)N * 40);
+        count_kernel("boxes_sanitize");
+        SDM_LAUNCH(boxes_sanitize_kernel, dim3(1), dim3(64), 0, e->stream, d_tiles, (int*)list.p, N, B, H, W);
+        prof_end(e);
+        // (an upper bound of the bytes: what is read depends on the tiles)
+        prof_begin(e, "boxes_prep_image", 0, (double)N * H * W * 12 + (double)N * S * S * 16 * fmt_bytes(x16.f32));
+        count_kernel("boxes_prep_image");
+        SDM_LAUNCH(boxes_prep_image_kernel, dim3(nb), dim3(256), 0, e->stream, d_img, (const int*)list.p, img16, x16.f32, N, H, W, S);
+        prof_end(e);
+        prof_begin(e, "boxes_prep_trimap", 0, (double)N * H * W * 4 + (double)N * S * S * (16 * fmt_bytes(x16.f32) + 4));
+        count_kernel("boxes_prep_trimap");
+        SDM_LAUNCH(boxes_prep_trimap_kernel, dim3(nb), dim3(256), 0, e->stream, d_tri, (const int*)list.p, tri16, x16.f32, (float*)plane.p, N, H, W, S);
+        prof_end(e);
+      }
+      TRY(run_model(e, x16, plane, N, S, S, true, &a));
+    }
+    if (!e->dry) {
+      const dim3 bgrid((unsigned)(B * sdm_cdiv(H, SDM_TL_BH) * sdm_cdiv(W, SDM_TL_BW))), fgrid((unsigned)(((long)B * H * W + 255) / 256));
+      // (an upper bound of the bytes: the write, a base or trimap value per pixel, the slots once)
+      prof_begin(e, "tiles_blend", 0, (double)px * 8 + (double)N * S * S * 4);
+      count_kernel("tiles_blend");
+      SDM_LAUNCH(tiles_blend_kernel, bgrid, dim3(256), 0, e->stream, N ? (const float*)a.p : (const float*)nullptr, N ? (const int*)list.p : (const int*)nullptr,
+                 d_tri, d_base, d_out, N, B, H, W, S, feather_px);
+      prof_end(e);
+      SDM_LAUNCH(refine_compose_kernel, fgrid, dim3(256), 0, e->stream, d_img, d_tri, d_out, d_matted, (long)B * H * W, tail.output_mode, tail.mask_refine,
+                 (float)tail.c, (float)(1.0 - tail.c));
+    }
+    if (N) { tfree(e, a); tfree(e, plane); tfree(e, x16); tfree(e, list); }
     return 0;
   });
 }

@@ -82,7 +82,7 @@ EXPORTS = [
     "sdm_default_config", "sdm_create", "sdm_destroy", "sdm_last_error", "sdm_load_tensor", "sdm_finalize_weights",
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
-    "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
+    "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_band_tiles", "sdm_apply_matte_tiles", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
     "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background", "sdm_harmonize", "sdm_matte_metrics",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_stats", "sdm_op_gn_partials", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
@@ -125,6 +125,8 @@ class Bindings:
             "sdm_apply_matte_roi": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, f32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, i32, vp]),
             "sdm_subject_boxes": (i32, [vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
             "sdm_apply_matte_boxes": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, C.c_double, vp, vp, i32, vp]),
+            "sdm_band_tiles": (i32, [vp, vp, i32, i32, i32, f32, f32, i32, i32, i32, vp, vp, i32, vp]),
+            "sdm_apply_matte_tiles": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, C.c_double, vp, vp, i32, vp]),
             "sdm_estimate_foreground": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
             "sdm_refine_alpha_guided": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp]),
             "sdm_compose_canvas": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, i32, i32, vp, i32, vp, i32, vp]),
@@ -655,6 +657,100 @@ class Engine:
         self._check(self.lib.sdm_apply_matte_boxes(self.h, _ptr(image_bhwc), _ptr(trimap_bhw), B, H, W, int(S), 1 if is_transparent else 0, _ptr(boxes),
                                                    int(boxes.shape[0]), mode, 1 if mask_refine else 0, float(trimap_constraint), _ptr(alpha), _ptr(matted),
                                                    self._kind(image_bhwc), stream), "sdm_apply_matte_boxes")
+        if sync:
+            self.synchronize()
+        return alpha, matted
+
+    TILES_MAX = 16               # SDM_TILES_MAX (include/sdmatte.h)
+    TILES_MAX_GRID = 256         # SDM_TILES_MAX_GRID
+    TILES_MAX_FEATHER = 1024     # SDM_TILES_MAX_FEATHER
+
+    @classmethod
+    def _check_tiles_params(cls, what, band_lo, band_hi, tile, overlap, max_tiles):
+        band_lo, band_hi = float(band_lo), float(band_hi)
+        lo32, hi32 = float(np.float32(band_lo)), float(np.float32(band_hi))      # what the C ABI's floats will hold
+        if not (0.0 <= band_lo < band_hi <= 1.0) or not (0.0 <= lo32 < hi32 <= 1.0):
+            raise ValueError(f"{what}: band_lo and band_hi must satisfy 0 <= band_lo < band_hi <= 1, got {band_lo!r}, {band_hi!r}")
+        if int(tile) != tile or not 16 <= int(tile) <= cls.FG_MAX_SIDE:
+            raise ValueError(f"{what}: tile must be an integer in 16 .. {cls.FG_MAX_SIDE}, got {tile!r}")
+        if int(overlap) != overlap or not 0 <= int(overlap) <= int(tile) // 2:
+            raise ValueError(f"{what}: overlap must be an integer in 0 .. tile / 2 = {int(tile) // 2}, got {overlap!r}")
+        if int(max_tiles) != max_tiles or not 1 <= int(max_tiles) <= cls.TILES_MAX:
+            raise ValueError(f"{what}: max_tiles must be an integer in 1 .. {cls.TILES_MAX}, got {max_tiles!r}")
+        return band_lo, band_hi, int(tile), int(overlap), int(max_tiles)
+
+    @classmethod
+    def _check_tiles_grid(cls, what, H, W, tile, overlap):
+        ny, nx = (1 if L <= tile else -(-(L - overlap) // (tile - overlap)) for L in (H, W))
+        if ny * nx > cls.TILES_MAX_GRID:
+            raise ValueError(f"{what}: a grid of {ny} x {nx} cells is more than {cls.TILES_MAX_GRID} (tile = {tile} is too small for {(H, W)})")
+
+    def band_tiles(self, trimap, band_lo=0.25, band_hi=0.75, tile=1024, overlap=128, max_tiles=16, out=None, sync=True, return_count=False):
+        """The tiles of a frame that need the model, on the GPU (sdm_band_tiles, defined in include/sdmatte.h): trimap [B,H,W] -> int32 [B,max_tiles,5] =
+        per image the entries {b, y0, x0, h, w} of the grid tiles (`tile` pixels a side, neighbours overlapping by at least `overlap`) that hold a pixel
+        with band_lo < trimap < band_hi, in row-major grid order; {-1, 0, 0, 0, 0} in every further entry.  return_count: also int32 [B], the number of
+        such tiles per image, also where it exceeds max_tiles.  Needs no loaded weights.  `sdmatte_nodes.band_tiles` is the same function on CPU
+        tensors, exactly."""
+        if trimap.dim() != 3 or trimap.numel() == 0:
+            raise ValueError(f"band_tiles: trimap must be a non-empty [B,H,W], got {tuple(trimap.shape)}")
+        band_lo, band_hi, tile, overlap, max_tiles = self._check_tiles_params("band_tiles", band_lo, band_hi, tile, overlap, max_tiles)
+        B, H, W = (int(v) for v in trimap.shape)
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"band_tiles: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        self._check_tiles_grid("band_tiles", H, W, tile, overlap)
+        trimap = trimap.float().contiguous()
+        if out is None:
+            out = torch.empty(B, max_tiles, 5, dtype=torch.int32, device=trimap.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (B, max_tiles, 5):
+            raise ValueError("band_tiles: out must be a contiguous int32 tensor [B,max_tiles,5]")
+        count = torch.empty(B, dtype=torch.int32, device=trimap.device) if return_count else None
+        stream = self._check_io("band_tiles", trimap, out, count)
+        self._check(self.lib.sdm_band_tiles(self.h, _ptr(trimap), B, H, W, band_lo, band_hi, tile, overlap, max_tiles, _ptr(out), _ptr(count),
+                                            self._kind(trimap), stream), "sdm_band_tiles")
+        if sync:
+            self.synchronize()
+        return (out, count) if return_count else out
+
+    def apply_matte_tiles(self, image_bhwc, trimap_bhw, tiles, S, is_transparent, output_mode, mask_refine, trimap_constraint, feather_px=None, base=None,
+                          sync=True):
+        """`apply_matte_node` over a list of tiles in one C-ABI call (sdm_apply_matte_tiles): tiles int32 [N,5] = {b, y0, x0, h, w}, N in 0 .. 16, on the
+        device of the planes; the model runs with batch N, one tile per slot at S x S, and each frame pixel gets the weighted mean of the tiles that contain
+        it - weights that ramp over feather_px pixels (None = 0) towards a tile's edges inside the frame - or, outside all of them, `base` [B,H,W] (None:
+        1 where trimap > 0.5, else 0); mask_refine and the composition run on the whole frame.  A void entry is skipped but costs a model pass
+        (`sdmatte_nodes.compact_boxes` drops them on the host); N = 0 runs no model pass.  Returns (alpha [B,H,W], matted [B,H,W,3|4])."""
+        if output_mode not in self.OUTPUT_MODES:
+            raise ValueError(f"unknown output_mode {output_mode!r}")
+        if image_bhwc.dim() != 4 or image_bhwc.shape[-1] != 3 or image_bhwc.numel() == 0:
+            raise ValueError(f"apply_matte_tiles: image must be a non-empty [B,H,W,3], got {tuple(image_bhwc.shape)}")
+        B, H, W, _ = (int(v) for v in image_bhwc.shape)
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"apply_matte_tiles: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        if trimap_bhw.dim() != 3 or trimap_bhw.shape[0] != B:
+            raise ValueError(f"apply_matte_tiles: trimap must be [B,H,W] with B = {B}, got {tuple(trimap_bhw.shape)}")
+        if tuple(trimap_bhw.shape) != (B, H, W):
+            # the tiles are tiles of the image: there is no trimap of another size here
+            raise IndexError(f"apply_matte_tiles: trimap {tuple(trimap_bhw.shape[1:])} must match the image {(H, W)}")
+        if tiles.dim() != 2 or tiles.shape[1] != 5 or tiles.dtype != torch.int32 or not 0 <= tiles.shape[0] <= self.TILES_MAX:
+            raise ValueError(f"apply_matte_tiles: tiles must be int32 [N,5] with N in 0 .. {self.TILES_MAX}, got {tiles.dtype} {tuple(tiles.shape)}")
+        feather_px = 0 if feather_px is None else feather_px
+        if int(feather_px) != feather_px or not 0 <= int(feather_px) <= self.TILES_MAX_FEATHER:
+            raise ValueError(f"apply_matte_tiles: feather_px must be an integer in 0 .. {self.TILES_MAX_FEATHER}, got {feather_px!r}")
+        if base is not None and tuple(base.shape) != (B, H, W):
+            raise ValueError(f"apply_matte_tiles: base must be [B,H,W] = {(B, H, W)}, got {tuple(base.shape)}")
+        image_bhwc = image_bhwc.float().contiguous()
+        trimap_bhw = trimap_bhw.float().contiguous()
+        tiles = tiles.contiguous()
+        base = base.float().contiguous() if base is not None else None
+        mode = self.OUTPUT_MODES[output_mode]
+        dev = image_bhwc.device
+        alpha = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+        matted = torch.empty(B, H, W, 4 if mode == 1 else 3, dtype=torch.float32, device=dev)
+        N = int(tiles.shape[0])
+        stream = self._check_io("apply_matte_tiles", image_bhwc, trimap_bhw, tiles, base, alpha, matted)
+        self._check(self.lib.sdm_apply_matte_tiles(self.h, _ptr(image_bhwc), _ptr(trimap_bhw), B, H, W, int(S), 1 if is_transparent else 0,
+                                                   _ptr(tiles) if N else None, N, int(feather_px), _ptr(base), mode, 1 if mask_refine else 0,
+                                                   float(trimap_constraint), _ptr(alpha), _ptr(matted), self._kind(image_bhwc), stream),
+                    "sdm_apply_matte_tiles")
         if sync:
             self.synchronize()
         return alpha, matted

@@ -576,6 +576,117 @@ def paste_boxes(crops, boxes, B, H, W):
     return out
 
 
+def tile_axis(L, tile, overlap):
+    """The grid rule of `Engine.band_tiles` for one axis of length L, in Python integers (the definition is in include/sdmatte.h, sdm_band_tiles):
+    (origins, size) - one tile of size L at 0 if L <= tile, otherwise n = ceil((L - overlap) / (tile - overlap)) tiles of size `tile` at
+    (i * (L - tile)) // (n - 1)."""
+    L, tile, overlap = int(L), int(tile), int(overlap)
+    if L < 1 or tile < 1 or not 0 <= overlap <= tile // 2:
+        raise ValueError(f"tile_axis: L = {L}, tile = {tile}, overlap = {overlap}: need L >= 1, tile >= 1 and overlap in 0 .. tile / 2")
+    if L <= tile:
+        return [0], L
+    n = -(-(L - overlap) // (tile - overlap))
+    return [(i * (L - tile)) // (n - 1) for i in range(n)], tile
+
+
+def band_tiles(trimap, band_lo=0.25, band_hi=0.75, tile=1024, overlap=128, max_tiles=16, return_count=False):
+    """`Engine.band_tiles` on CPU tensors, exactly (integers only): trimap [B,H,W] -> int32 [B,max_tiles,5] = per image the entries {b, y0, x0, h, w} of
+    the grid tiles that hold a pixel with band_lo < trimap < band_hi (compared in fp32), row-major, void entries {-1, 0, 0, 0, 0} behind them; with
+    return_count also int32 [B], the number of such tiles (also beyond max_tiles).  A tile's band pixels are counted through a summed-area table."""
+    import numpy as np
+    from .engine import Engine
+    if trimap.dim() != 3 or trimap.numel() == 0:
+        raise ValueError(f"band_tiles: trimap must be a non-empty [B,H,W], got {tuple(trimap.shape)}")
+    band_lo, band_hi, tile, overlap, max_tiles = Engine._check_tiles_params("band_tiles", band_lo, band_hi, tile, overlap, max_tiles)
+    p = trimap.detach().cpu().float().contiguous().numpy()
+    B, H, W = p.shape
+    Engine._check_tiles_grid("band_tiles", H, W, tile, overlap)
+    (oy, sy), (ox, sx) = tile_axis(H, tile, overlap), tile_axis(W, tile, overlap)
+    out = np.zeros((B, max_tiles, 5), np.int32)
+    out[:, :, 0] = -1
+    count = np.zeros(B, np.int32)
+    for b in range(B):
+        with np.errstate(invalid="ignore"):
+            band = (p[b] > np.float32(band_lo)) & (p[b] < np.float32(band_hi))
+        sat = np.zeros((H + 1, W + 1), np.int64)
+        sat[1:, 1:] = band.astype(np.int64).cumsum(0).cumsum(1)
+        n = 0
+        for y0 in oy:
+            for x0 in ox:
+                if sat[y0 + sy, x0 + sx] - sat[y0, x0 + sx] - sat[y0 + sy, x0] + sat[y0, x0] > 0:
+                    if n < max_tiles:
+                        out[b, n] = (b, y0, x0, sy, sx)
+                    n += 1
+        count[b] = n
+    out = torch.from_numpy(out)
+    return (out, torch.from_numpy(count)) if return_count else out
+
+
+def _tile_axis_weight(start, ext, L, feather_px):
+    """fp32 [ext]: min(1, (d + 1) / (feather_px + 1)) with d the distance to the nearer edge pixel among the tile's sides that are not on the frame's
+    border (1.0 without such a side)."""
+    o = torch.arange(ext, dtype=torch.int64)
+    d = torch.full((ext, ), 1 << 40, dtype=torch.int64)
+    if start != 0:
+        d = torch.minimum(d, o)
+    if start + ext != L:
+        d = torch.minimum(d, ext - 1 - o)
+    ramp = (d.clamp(max=feather_px) + 1).to(torch.float32) / torch.tensor(float(feather_px + 1), dtype=torch.float32)
+    return torch.where(d >= feather_px, torch.ones(ext, dtype=torch.float32), ramp)
+
+
+def blend_tiles(crops, tiles, B, H, W, feather_px=0, base=None):
+    """The way back of `Engine.apply_matte_tiles` on CPU tensors, in fp32 and in list order (the definition is in include/sdmatte.h,
+    sdm_apply_matte_tiles): crops[n] ([h,w] of tiles[n] = {b, y0, x0, h, w}, values in [0, 1]) -> fp32 [B,H,W], per pixel
+    clamp(sum (w_n / Wsum) * crops[n]) over the tiles that contain it, w_n = wy * wx ramping over feather_px pixels towards a tile's edges inside the
+    frame; a pixel in no tile gets `base` [B,H,W] (NaN -> 0, clamped; None: 0.0).  A void entry (b < 0) is skipped."""
+    tiles = torch.as_tensor(tiles).reshape(-1, 5)
+    B, H, W, feather_px = int(B), int(H), int(W), int(feather_px)
+    if len(crops) != tiles.shape[0]:
+        raise ValueError(f"blend_tiles: {len(crops)} crops for {tiles.shape[0]} tiles")
+    if feather_px < 0:
+        raise ValueError(f"blend_tiles: feather_px must be >= 0, got {feather_px}")
+    if base is None:
+        out = torch.zeros(B, H, W, dtype=torch.float32)
+    else:
+        if tuple(base.shape) != (B, H, W):
+            raise ValueError(f"blend_tiles: base must be [B,H,W] = {(B, H, W)}, got {tuple(base.shape)}")
+        out = torch.nan_to_num(base.detach().cpu().float(), nan=0.0).clamp(0.0, 1.0)
+    wsum = torch.zeros(B, H, W, dtype=torch.float32)
+    acc = torch.zeros(B, H, W, dtype=torch.float32)
+    weights = []
+    for n, crop in enumerate(crops):
+        b, y0, x0, h, w = (int(v) for v in tiles[n])
+        if b < 0:
+            weights.append(None)
+            continue
+        if b >= B or tuple(crop.shape) != (h, w) or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+            raise ValueError(f"blend_tiles: crop {tuple(crop.shape)} does not fit the tile {(b, y0, x0, h, w)} of {B} frames of {(H, W)}")
+        wn = _tile_axis_weight(y0, h, H, feather_px)[:, None] * _tile_axis_weight(x0, w, W, feather_px)[None, :]
+        weights.append(wn)
+        wsum[b, y0:y0 + h, x0:x0 + w] += wn
+    for n, crop in enumerate(crops):
+        if weights[n] is None:
+            continue
+        b, y0, x0, h, w = (int(v) for v in tiles[n])
+        acc[b, y0:y0 + h, x0:x0 + w] += (weights[n] / wsum[b, y0:y0 + h, x0:x0 + w]) * crop.detach().cpu().float()
+    covered = wsum > 0
+    out[covered] = acc.clamp(0.0, 1.0)[covered]
+    return out
+
+
+def auto_tile(H, W, inference_size, overlap=128, limit=16):
+    """The tile size of the tiled node: the smallest multiple of 64 that is >= inference_size and whose grid (the rule of `tile_axis`) has at most `limit`
+    cells on an H x W frame.  No data is read, so the result bounds the tile count of every image of that size."""
+    H, W, overlap, limit = int(H), int(W), int(overlap), int(limit)
+    if H < 1 or W < 1 or limit < 1 or int(inference_size) < 1 or overlap < 0:
+        raise ValueError(f"auto_tile: bad arguments H = {H}, W = {W}, inference_size = {inference_size}, overlap = {overlap}, limit = {limit}")
+    tile = -(-int(inference_size) // 64) * 64
+    while tile // 2 < overlap or len(tile_axis(H, tile, overlap)[0]) * len(tile_axis(W, tile, overlap)[0]) > limit:
+        tile += 64
+    return tile
+
+
 def canvas_fit(roi, canvas_h, canvas_w, fill_pct=80, valign="center"):
     """The placements of `Engine.compose_canvas` in exact integers (the definition is in include/sdmatte.h, sdm_compose_canvas): roi int [B,4] = {y0, x0, h, w}
     -> int32 [B,8] = {y0, x0, h, w, dy0, dx0, dh, dw}, the box scaled to fill `fill_pct` % of the canvas and aligned in it."""
@@ -1521,6 +1632,85 @@ class SDMatteApplySubjects:
         return (torch.cat(alphas), torch.cat(matteds), trimap.detach().cpu(), out)
 
 
+_TILED_INPUTS = {
+    "tile_size": ("INT", {"default": 0, "min": 0, "max": 8192, "step": 64, "tooltip": "side of a tile in frame pixels; 0 = the smallest multiple of 64 >= inference_size whose grid has at most 16 tiles"}),
+    "overlap": ("INT", {"default": 128, "min": 0, "max": 4096, "step": 1, "tooltip": "neighbouring tiles share at least this many pixels (at most half a tile)"}),
+    "feather": ("INT", {"default": -1, "min": -1, "max": 1024, "step": 1, "tooltip": "width of the ramp that blends overlapping tiles; -1 = the overlap"}),
+    "band_lo": ("FLOAT", {"default": 0.25, "min": 0.0, "max": 0.99, "step": 0.01, "tooltip": "a tile needs the model if it holds a trimap value above this ..."}),
+    "band_hi": ("FLOAT", {"default": 0.75, "min": 0.01, "max": 1.0, "step": 0.01, "tooltip": "... and below this"}),
+}
+
+
+class SDMatteApplyTiled:
+    """`Apply SDMatte (Mask)` at the photo's own resolution: the frame is cut into overlapping tiles, every tile that holds a pixel of the trimap's unknown
+    band is matted in a model pass of its own at `inference_size`, and the passes are blended with weights that ramp down towards a tile's edges.
+    The definite parts of the trimap cost no pass.  Returns the tiles as well: a list of (x, y, width, height) per image."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        base = SDMatteApplyMask.INPUT_TYPES()
+        required = {}
+        for key, spec in base["required"].items():
+            required[key] = spec
+            if key == "dilate_px":
+                required.update(_TILED_INPUTS)
+        optional = dict(base["optional"])
+        optional["base_alpha"] = ("MASK", {"tooltip": "alpha for the pixels outside every tile (default: the trimap's definite values)"})
+        return {"required": required, "optional": optional}
+
+    RETURN_TYPES = ("MASK", "IMAGE", "MASK", "BBOX")
+    RETURN_NAMES = ("alpha_mask", "matted_image", "trimap", "tiles")
+    FUNCTION = "apply_matte"
+    CATEGORY = "Matting/SDMatte"
+
+    def apply_matte(self, ckpt_name, image, mask, threshold, erode_px, dilate_px, tile_size, overlap, feather, band_lo, band_hi, inference_size,
+                    is_transparent, output_mode, mask_refine, trimap_constraint, force_cpu=False, base_alpha=None):
+        from .engine import Engine
+        if force_cpu:
+            raise RuntimeError("[SDMatte] force_cpu=True is not available: this node runs hand-written gfx950 kernels only "
+                               "(no CPU path).  Use the reference plugin for CPU inference.")
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        if mask.dim() != 3 or tuple(mask.shape) != tuple(image.shape[:3]):
+            raise ValueError(f"[SDMatte] mask must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(mask.shape)}")
+        if base_alpha is not None and tuple(base_alpha.shape) != tuple(image.shape[:3]):
+            raise ValueError(f"[SDMatte] base_alpha must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(base_alpha.shape)}")
+        H, W = int(image.shape[1]), int(image.shape[2])
+        overlap = int(overlap)
+        tile = int(tile_size) if int(tile_size) > 0 else auto_tile(H, W, int(inference_size), overlap, Engine.TILES_MAX)
+        feather = overlap if int(feather) < 0 else int(feather)
+        Engine._check_tiles_params("[SDMatte] apply_matte", band_lo, band_hi, tile, overlap, Engine.TILES_MAX)
+        Engine._check_tiles_grid("[SDMatte] apply_matte", H, W, tile, overlap)
+        if not 0 <= feather <= Engine.TILES_MAX_FEATHER:
+            raise ValueError(f"[SDMatte] feather must be in 0 .. {Engine.TILES_MAX_FEATHER}, got {feather}")
+        return self._run(get_model(ckpt_name, _torch_device()), image, mask, float(threshold), int(erode_px), int(dilate_px), tile, overlap, feather,
+                         float(band_lo), float(band_hi), int(inference_size), bool(is_transparent), output_mode, bool(mask_refine), float(trimap_constraint),
+                         base_alpha)
+
+    @staticmethod
+    def _run(model, image, mask, threshold, erode_px, dilate_px, tile, overlap, feather, band_lo, band_hi, inference_size, is_transparent, output_mode,
+             mask_refine, trimap_constraint, base_alpha=None):
+        """Trimap, tiles, a readback of the few hundred bytes of the list, then one apply_matte_tiles call per range of images with at most SDM_TILES_MAX
+        entries; a range without an entry (no unknown pixel) is called with N = 0."""
+        from .engine import Engine
+        eng = model.engine
+        B = int(image.shape[0])
+        trimap = eng.make_trimap(mask, threshold, erode_px, dilate_px)
+        tiles, count = eng.band_tiles(trimap, band_lo, band_hi, tile, overlap, Engine.TILES_MAX, return_count=True)
+        if int(count.max()) > Engine.TILES_MAX:
+            raise ValueError(f"[SDMatte] an image needs {int(count.max())} tiles of {tile} pixels, more than {Engine.TILES_MAX}: use a larger tile_size (0 chooses one)")
+        tiles = compact_boxes(tiles)
+        alphas, matteds = [], []
+        for lo, hi, part in split_boxes(tiles, B, Engine.TILES_MAX):
+            a, m = eng.apply_matte_tiles(image[lo:hi], trimap[lo:hi], part.to(trimap.device), inference_size, is_transparent, output_mode, mask_refine,
+                                         trimap_constraint, feather, None if base_alpha is None else base_alpha[lo:hi].to(trimap.device))
+            alphas.append(a.detach().cpu())
+            matteds.append(m.detach().cpu())
+        out = [[(int(x0), int(y0), int(w), int(h)) for bb, y0, x0, h, w in tiles.tolist() if bb == b] for b in range(B)]
+        _trim_engine_memory(model)
+        return (torch.cat(alphas), torch.cat(matteds), trimap.detach().cpu(), out)
+
+
 _FOREGROUND_INPUTS = {
     "regularization": ("FLOAT", {"default": 1e-5, "min": 1e-9, "max": 1.0, "step": 1e-6, "tooltip": "smoothness weight between all neighbours (must be above 0)"}),
     "gradient_weight": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 100.0, "step": 0.01, "tooltip": "extra smoothness weight across alpha edges"}),
@@ -1992,9 +2182,18 @@ def with_metrics_node(mappings, metrics: bool = True):
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1, SDMATTE_HARMONIZE_NODE=1, SDMATTE_METRICS_NODE=1), like the multi-GPU fan-out
+def with_tiled_node(mappings, tiled: bool = True):
+    """(classes, names) of `mappings` plus `SDMatteApplyTiled` when `tiled`; the argument is not modified (as `with_harmonize_node`)."""
+    classes, names = dict(mappings[0]), dict(mappings[1])
+    if tiled:
+        classes["SDMatteApplyTiled"] = SDMatteApplyTiled
+        names["SDMatteApplyTiled"] = "Apply SDMatte (Tiled)"
+    return classes, names
+
+
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1, SDMATTE_HARMONIZE_NODE=1, SDMATTE_METRICS_NODE=1, SDMATTE_TILED_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
-NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_metrics_node(with_harmonize_node(node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
+NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_tiled_node(with_metrics_node(with_harmonize_node(node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
                                                                 os.environ.get("SDMATTE_REFINE_NODE") == "1",
                                                                 os.environ.get("SDMATTE_CLEAN_NODE") == "1",
@@ -2006,4 +2205,5 @@ NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_metrics_node(with_harmoni
                                                                 os.environ.get("SDMATTE_MOTION_NODE") == "1",
                                                                 os.environ.get("SDMATTE_DEFOCUS_NODE") == "1"),
                                                                       os.environ.get("SDMATTE_HARMONIZE_NODE") == "1"),
-                                                                      os.environ.get("SDMATTE_METRICS_NODE") == "1")
+                                                                      os.environ.get("SDMATTE_METRICS_NODE") == "1"),
+                                                                      os.environ.get("SDMATTE_TILED_NODE") == "1")

@@ -292,6 +292,61 @@ int sdm_apply_matte_boxes(sdm_ctx* ctx, const float* image_bhwc, const float* tr
                           const int32_t* boxes_n5, int N, int output_mode, int mask_refine, double trimap_constraint, float* alpha_bhw,
                           float* matted_bhwc, int ptr_kind, void* stream);
 
+/* Which tiles of a frame need the model, on the GPU (beyond the reference): a portrait that fills a 4K frame has the frame as its box, so the box calls
+ * above still show the model its hair at a quarter of the resolution.  The frame is cut into overlapping tiles of `tile` pixels, and only the tiles that
+ * hold a pixel of the trimap's unknown band are listed.  trimap fp32 [B,H,W] -> tiles_bk5 int32 [B][max_tiles][5] = {b, y0, x0, h, w} and count_b (may be
+ * NULL) int32 [B], both of the same pointer kind as the plane.  Per image:
+ *   band     pixel p is unknown iff band_lo < trimap[p] and trimap[p] < band_hi (two fp32 compares, so NaN is not in the band, nor is a value equal to
+ *            either bound).  0.25 and 0.75 are the band of sdm_matte_metrics.
+ *   grid     per axis of length L, with T = tile and O = overlap, in integers (64-bit products, truncating division): one tile of size L at 0 if L <= T;
+ *            otherwise n = ceil((L - O) / (T - O)) tiles of size T at the origins o_i = (i * (L - T)) / (n - 1), i = 0 .. n-1.  The origins increase
+ *            strictly, the first tile starts at 0 and the last ends at L, neighbours overlap by at least O, every pixel is covered - by at most three
+ *            tiles per axis (three, not two: up to nine tiles meet in a pixel).  A grid tile is the product of a y-interval and an x-interval.
+ *   active   a grid tile is active iff its rectangle holds at least one band pixel.  Hence every band pixel lies in every active tile that contains it,
+ *            and in at least one.
+ *   list     the active tiles in row-major grid order (iy, then ix) are entries 0, 1, ..; every further entry is void: {-1, 0, 0, 0, 0}.  count_b[b] is
+ *            the number of active tiles, also when it exceeds max_tiles: then the first max_tiles are listed and the caller sees the overflow.  An image
+ *            without a band pixel has count 0 and void entries only.
+ * Integer and bitwise operations only: GPU, emulator and sdmatte_nodes.band_tiles agree exactly.  band_lo and band_hi finite with 0 <= band_lo < band_hi
+ * <= 1, tile in 16 .. SDM_FG_MAX_SIDE, overlap in 0 .. tile / 2, max_tiles in 1 .. SDM_TILES_MAX, n_y * n_x <= SDM_TILES_MAX_GRID grid cells per image,
+ * B, H, W as in sdm_subject_roi: SDM_ERR_INVALID otherwise, and then nothing is queued or written.  Stream contract and pointer kinds as
+ * sdm_make_trimap; sdm_last_forward_ms covers the launches.  Needs no weights.  Three kernel launches (csrc/k_tiles.h: tiles_init, tiles_mark,
+ * tiles_list), whatever B, H, W and the content: one read of the plane, no global atomic per pixel (at most SDM_TILES_MAX_GRID / 32 per block), no host
+ * readback.  The flag words are part of the activation arena, host pointers go through the I/O staging (sdm_resident_bytes counts both,
+ * sdm_release_memory frees them). */
+#define SDM_TILES_MAX 16 /* = SDM_BOXES_MAX_TOTAL */
+#define SDM_TILES_MAX_GRID 256
+int sdm_band_tiles(sdm_ctx* ctx, const float* trimap_bhw, int B, int H, int W, float band_lo, float band_hi, int tile, int overlap, int max_tiles,
+                   int32_t* tiles_bk5, int32_t* count_b, int ptr_kind, void* stream);
+/* sdm_apply_matte_node over a list of tiles that cut through one subject: the model runs with batch N, slot n on the tile of entry n = {b, y0, x0, h, w}
+ * of tiles_n5 (int32 [N][5], of the same pointer kind as the planes; N in 0 .. SDM_TILES_MAX is known to the host, the list's content stays on the
+ * device), and the alphas are blended into the frames.  The trimap [B,H,W] has the image's size.
+ *   sanitise, prepare  exactly as in sdm_apply_matte_boxes (the same kernels under the same names): an entry that does not lie inside the planes is void, a
+ *            void entry is not an error and costs a model pass, and no kernel of this call reads outside the planes whatever the list holds.
+ *   blend    each frame pixel is written once.  For image b and pixel p, over the valid entries i of image b whose rectangle contains p, in list order:
+ *            a_i   = the clamped value of that slot at p as in sdm_apply_matte_roi: the plain copy when (h, w) == (S, S), else the resize from S x S;
+ *            w_i   = wy * wx.  Per axis, a side of the tile that lies on the frame's border does not ramp; any other side ramps as
+ *                    min(1, (d + 1) / (feather_px + 1)), d being the distance in pixels to that side's edge pixel (0 on it), a true fp32 division; the
+ *                    axis weight is the minimum of its two sides (1 if both lie on the border).  feather_px = 0 gives weight 1 everywhere;
+ *            Wsum  = the sum of the w_i in list order;
+ *            out   = clamp(sum of (w_i / Wsum) * a_i in list order, 0, 1), true fp32 divisions.
+ *            Hence a pixel inside exactly one tile gets that tile's value unchanged, bit for bit (w / w == 1), and with one tile equal to the frame the
+ *            call is bit-identical to sdm_apply_matte_node.  The weights are normalised before the multiply, so that a constant slot value stays
+ *            that constant.
+ *   base     a pixel in no valid tile gets base_bhw[b][p] (NaN -> 0, then clamped to [0, 1]) if base_bhw (fp32 [B,H,W], may be NULL) is given, otherwise
+ *            1.0 if trimap[p] > 0.5, else 0.0.  For a list from sdm_band_tiles on the same trimap every such pixel is definite, so this is exact; for
+ *            a caller's own list it is the caller's statement.
+ *   mask_refine and the output composition then run over the whole frame as in sdm_apply_matte_node.  The box conditioning stays [0, 0, 1, 1] and
+ *   is_transparent is one flag.
+ * N = 0 (tiles_n5 may be NULL then) runs no preparation and no model pass: the blend gives every pixel the base, and the tail follows.
+ * N or feather_px (0 .. SDM_TILES_MAX_FEATHER) outside its range, a bad output_mode, S or plane size: SDM_ERR_INVALID, and then nothing is queued or
+ * written.  The arena is that of sdm_apply_matte_boxes.  Four launches beyond the model's, each once per call: boxes_sanitize, boxes_prep_image,
+ * boxes_prep_trimap, tiles_blend in sdm_kernel_counts and the per-launch profile (tiles_blend alone with N = 0). */
+#define SDM_TILES_MAX_FEATHER 1024
+int sdm_apply_matte_tiles(sdm_ctx* ctx, const float* image_bhwc, const float* trimap_bhw, int B, int H, int W, int S, int is_transparent,
+                          const int32_t* tiles_n5, int N, int feather_px, const float* base_bhw, int output_mode, int mask_refine,
+                          double trimap_constraint, float* alpha_bhw, float* matted_bhwc, int ptr_kind, void* stream);
+
 /* Foreground / background colours from an image and its alpha, on the GPU (beyond the reference: its matted_rgba keeps the composite
  * a*F + (1-a)*B in every semi-transparent pixel, and with it a halo of the old background).  A multi-level estimator in the style of Germer et al.,
  * "Fast Multi-Level Foreground Estimation"; it uses the image and the alpha only.
