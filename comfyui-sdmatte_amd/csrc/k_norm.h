@@ -4,8 +4,8 @@
 // ResnetBlock2D / Transformer2DModel / VAE Attention / conv_norm_out (SURVEY.md Appendix A.3,A.5-A.7;
 // eps 1e-6 VAE + Transformer2D, 1e-5 U-Net ResBlocks), and F.layer_norm(eps 1e-5) x3 per
 // BasicTransformerBlock.  Statistics are per (image, group) over (C/32 channels x H*W pixels), biased
-// variance, computed in fp32 per thread, fp32 LDS atomics per block and fp64 global atomics across
-// blocks; the affine transform is applied in fp32 and rounded once to fp16 (the MFMA operand type).
+// variance, from sums about a pivot (gn_pivot) computed in fp32 per thread, fp32 LDS atomics per block and fp64
+// global atomics across blocks; the affine transform is applied in fp32 and rounded once to fp16 (the MFMA operand type).
 //
 // Work decomposition (both kernels): a thread owns ONE fixed 8-channel vector (16 B fp16 / 32 B fp32)
 // and strides over pixels, so gamma/beta/scale/shift live in registers and all global accesses are
@@ -20,7 +20,17 @@ struct GnSrc {
   int HW;                            // pixels per image
 };
 
-// sums[n][g][2] (double) += {sum x, sum x^2}
+// The pivot of group g of image n: the group's first value (pixel 0, first channel of the group).  The stand-alone statistics are sums of x - pivot:
+// E[x^2] - mean^2 on the raw values loses accuracy as (mean / std)^2 (a channel offset of 100 std leaves 1e-3 of the normalised value), the shifted
+// sums lose it as ((mean - pivot) / std)^2 - and the pivot is a value of the group, a few std from its mean.
+SDM_DEV_INLINE float gn_pivot(const GnSrc& s, int n, int c) {
+  const void* src = s.in0; int Cs = s.C0, cc = c;
+  if (c >= s.C0) { src = s.in1; Cs = s.C1; cc = c - s.C0; }
+  const size_t i = (size_t)n * s.HW * Cs + cc;
+  return s.in_f32 ? ((const float*)src)[i] : (float)((const half_t*)src)[i];
+}
+
+// sums[n][g][2] (double) += {sum d, sum d^2}, d = x - pivot of the group
 __global__ void __launch_bounds__(512) gn_stats_kernel(GnSrc s, double* __restrict__ sums, int groups, int pix_per_block) {
   SDM_DYN_SMEM(smem);
   const int C = s.C0 + s.C1;
@@ -33,26 +43,26 @@ __global__ void __launch_bounds__(512) gn_stats_kernel(GnSrc s, double* __restri
   __syncthreads();
   const int n = blockIdx.y;
   const int cv = tid % CV, slot = tid / CV;
+  const int cpg = C / groups;
   if (slot < slots) {
     const int c = cv * 8;
     const void* src = s.in0; int Cs = s.C0, cc = c;
     if (c >= s.C0) { src = s.in1; Cs = s.C1; cc = c - s.C0; }
-    float a[8], q[8];
+    float a[8], q[8], piv[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { a[e] = 0.0f; q[e] = 0.0f; }
+    for (int e = 0; e < 8; ++e) { a[e] = 0.0f; q[e] = 0.0f; piv[e] = gn_pivot(s, n, (c + e) / cpg * cpg); }      // (an 8-channel vector may lie across groups)
     const int p0 = blockIdx.x * pix_per_block;
     const int p1 = min(p0 + pix_per_block, s.HW);
     for (int p = p0 + slot; p < p1; p += slots) {
       float v[8];
       sdm_load8_as_f32(src, ((size_t)n * s.HW + p) * Cs + cc, s.in_f32, v);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { a[e] += v[e]; q[e] += v[e] * v[e]; }
+      for (int e = 0; e < 8; ++e) { const float d = v[e] - piv[e]; a[e] += d; q[e] += d * d; }
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) { atomicAdd(&lsum[c + e], a[e]); atomicAdd(&lsq[c + e], q[e]); }
   }
   __syncthreads();
-  const int cpg = C / groups;
   if (tid < groups) {
     double ss = 0.0, qq = 0.0;
     for (int j = 0; j < cpg; ++j) { ss += (double)lsum[tid * cpg + j]; qq += (double)lsq[tid * cpg + j]; }
@@ -61,16 +71,18 @@ __global__ void __launch_bounds__(512) gn_stats_kernel(GnSrc s, double* __restri
   }
 }
 
-// scale[n][c] = rstd*gamma, shift[n][c] = beta - mean*rstd*gamma
-__global__ void gn_finalize_kernel(const double* __restrict__ sums, const float* __restrict__ gamma,
+// scale[n][c] = rstd*gamma, shift[n][c] = beta - mean*rstd*gamma, from the shifted sums: mean = pivot + sum d / count, var = sum d^2 / count - (sum d / count)^2
+__global__ void gn_finalize_kernel(GnSrc s, const double* __restrict__ sums, const float* __restrict__ gamma,
                                    const float* __restrict__ beta, float* __restrict__ scale, float* __restrict__ shift,
                                    int N, int C, int groups, long count, float eps) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N * C) return;
-  const int n = i / C, c = i % C, g = c / (C / groups);
-  const double mean = sums[((size_t)n * groups + g) * 2] / (double)count;
-  double var = sums[((size_t)n * groups + g) * 2 + 1] / (double)count - mean * mean;
+  const int cpg = C / groups;
+  const int n = i / C, c = i % C, g = c / cpg;
+  const double md = sums[((size_t)n * groups + g) * 2] / (double)count;
+  double var = sums[((size_t)n * groups + g) * 2 + 1] / (double)count - md * md;
   if (var < 0.0) var = 0.0;
+  const double mean = (double)gn_pivot(s, n, g * cpg) + md;
   const float rstd = (float)(1.0 / sqrt(var + (double)eps));
   const float a = rstd * gamma[c];
   scale[i] = a;

@@ -1487,7 +1487,7 @@ static int gn_scale_shift(sdm_ctx* e, const void* in0, const void* in1, int C0, 
     prof_begin(e, "gn_stats", 0, (double)N * HW * C * (in_f32 ? 4 : 2));
     SDM_LAUNCH(gn_stats_kernel, dim3(g.nb, N), dim3(g.threads), (size_t)2 * C * 4, e->stream, s, sums, groups, g.ppb);
     prof_end(e);
-    SDM_LAUNCH(gn_finalize_kernel, dim3(sdm_cdiv(N * C, 256)), dim3(256), 0, e->stream, (const double*)sums, gamma, beta, scale, shift, N, C,
+    SDM_LAUNCH(gn_finalize_kernel, dim3(sdm_cdiv(N * C, 256)), dim3(256), 0, e->stream, s, (const double*)sums, gamma, beta, scale, shift, N, C,
                groups, (long)HW * (C / groups), eps);
   }
   return 0;
@@ -2878,6 +2878,16 @@ static void pack_layer_weight(sdm_ctx* e, const ConvL& L, const float* src, int 
   SDM_LAUNCH(pack_conv_weight_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, e->stream, src, L.w, O, I, L.ntaps,
              L.Cin_pad, L.Cout_pad, ci_off, co_off, L.geglu, w_scale * ldexpf(1.0f, L.w_exp), L.w_lo);
 }
+// A weight the K16 format cannot hold: |w| * w_scale * 2^w_exp beyond fp16's largest finite value would be packed as inf and every output of the layer
+// would be inf / nan with return code 0.  The load fails instead and names the tensor ("weights outside the split format").
+static const float kK16Max = 65504.0f;
+static int check_weight_range(sdm_ctx* e, const ConvL& L, const char* tensor, float amax, float w_scale) {
+  const float packed = amax * fabsf(w_scale) * ldexpf(1.0f, L.w_exp);
+  if (packed > kK16Max)
+    SDM_FAIL(e, SDM_ERR_INVALID, "%s: max|w| = %g does not fit the packed fp16 weight format of layer %s (|w| * %g <= %g)", tensor, (double)amax, L.name.c_str(),
+             (double)(fabsf(w_scale) * ldexpf(1.0f, L.w_exp)), (double)kK16Max);
+  return 0;
+}
 static void pack_layer_bias(sdm_ctx* e, const ConvL& L, const float* src, int n, int co_off) {
   SDM_LAUNCH(pack_bias_kernel, dim3(sdm_cdiv(L.Cout_pad, 256)), dim3(256), 0, e->stream, src, L.b, n, L.Cout_pad, co_off, L.geglu);
 }
@@ -2901,6 +2911,11 @@ int sdm_load_tensor(sdm_ctx* e, const char* name, int dtype, int ndim, const int
     ok = ndim >= 2 && shape[0] == s.shape[0] && shape[1] == s.shape[1];
   }
   if (!ok) SDM_FAIL(e, SDM_ERR_INVALID, "size mismatch for %s: checkpoint has %zu elements, model expects %zu", name, n, nexp);
+  if (s.kind == SLOT_CONV_W) {
+    float amax = 0.0f;
+    for (size_t i = 0; i < n; ++i) amax = std::max(amax, fabsf(to_f32(host_ptr, dtype, i)));
+    TRY(check_weight_range(e, e->convs[s.layer], name, amax, s.w_scale));
+  }
   e->finalized = false;
   if (s.kind == SLOT_HOST) {
     float* dst = e->hostblob.data() + s.host_off;
@@ -3020,6 +3035,9 @@ static void fold_cross_block(const sdm_ctx* e, const TfB& t, const std::vector<d
 }
 static int upload_folded(sdm_ctx* e, ConvL& L, const std::vector<float>& w, int O, int I, int ci_off, const std::vector<float>* bias) {
   if (ensure_buf(e, &e->stage, &e->stage_bytes, std::max(w.size() * 4, (size_t)1 << 20)) != 0) return SDM_ERR_NOMEM;
+  float amax = 0.0f;
+  for (float v : w) amax = std::max(amax, fabsf(v));
+  TRY(check_weight_range(e, L, (L.name + " (folded cross-attention weight)").c_str(), amax, 1.0f));
   SDM_CHECK_DEV(e, dev_memset(L.w, 0, L.w_bytes(), e->stream));
   if (L.w_lo) SDM_CHECK_DEV(e, dev_memset(L.w_lo, 0, L.w_bytes(), e->stream));
   SDM_CHECK_DEV(e, dev_memcpy_h2d(e->stage, w.data(), w.size() * 4, e->stream));

@@ -34,6 +34,20 @@ struct TempLayer {
     L.wup = (unsigned char*)wup.p;
     L.w = (half_t*)w.p; L.b = (float*)b.p; L.w_lo = (half_t*)w_lo.p; L.w_dma = (half_t*)w_dma.p; L.w3 = (unsigned char*)w3.p;
     pack_layer_weight(e, L, wsrc, O, I, 0, 0, 1.0f);
+    {   // The caller's weights are on the device, so this is a second form of sdm_load_tensor's range check (check_weight_range works on the host copy of a
+        // checkpoint tensor and reports max|w|): a max over the packed high parts, where a weight beyond fp16 reads inf - it can say that one does not fit,
+        // not which value.  One small launch, a 4-byte copy and a stream sync per hook call (the bench helpers that build a TempLayer pay it in front of
+        // their timed launches, not inside them); derive_layers takes its own max only for the layers with an fp8 copy, after this point.
+      DevBuf mx;
+      SDM_CHECK_DEV(e, mx.alloc0(4, e->stream));
+      const size_t n = L.w_bytes() / 2;
+      unsigned int* mp = (unsigned int*)mx.p;
+      SDM_LAUNCH(absmax_f16_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, e->stream, (const half_t*)L.w, n, mp);
+      float m = 0.0f;
+      SDM_CHECK_DEV(e, dev_memcpy_d2h(&m, mp, 4, e->stream));
+      SDM_CHECK_DEV(e, dev_sync(e->stream));
+      if (!std::isfinite(m)) SDM_FAIL(e, SDM_ERR_INVALID, "%s: a weight does not fit the packed fp16 weight format (|w| * %g <= %g)", name, (double)ldexpf(1.0f, L.w_exp), (double)kK16Max);
+    }
     if (bias) pack_layer_bias(e, L, bias, O, 0);
     std::vector<ConvL*> one{&L};
     return derive_layers(e, one);
@@ -154,6 +168,24 @@ int sdm_op_gn_partials(sdm_ctx* e, const float* st0, int rows0, const float* st1
     T scratch; float* scale; float* shift;
     TRY(gn_scale_shift(e, nullptr, nullptr, C0, C1, 1, N, HW, groups, gamma, beta, eps, st0, rows0, C1 > 0 ? st1 : nullptr, C1 > 0 ? rows1 : 0, true,
                        &scratch, &scale, &shift));
+    if (!e->dry) {
+      SDM_CHECK_DEV(e, dev_memcpy_d2d(scale_out, scale, (size_t)N * (C0 + C1) * 4, e->stream));
+      SDM_CHECK_DEV(e, dev_memcpy_d2d(shift_out, shift, (size_t)N * (C0 + C1) * 4, e->stream));
+    }
+    tfree(e, scratch);
+    return 0;
+  });
+}
+
+/* The stand-alone statistics alone: x0 [N][HW][C0] (+ x1 [N][HW][C1], the second source of a channel concat; C1 = 0: none), fp32 or fp16 -> the scale | shift
+ * tables of sdm_op_gn_partials, by gn_stats_kernel + gn_finalize_kernel as gn_scale_shift launches them for an input without partial rows. */
+int sdm_op_gn_tables(sdm_ctx* e, const void* x0, const void* x1, int C0, int C1, int in_f32, int N, int HW, int groups, const float* gamma,
+                     const float* beta, float eps, float* scale_out, float* shift_out) {
+  if (e) dev_use(e->device);
+  if (!e || !x0 || (C1 > 0 && !x1) || !gamma || !beta || !scale_out || !shift_out || N < 1 || HW < 1 || groups < 1) return SDM_ERR_INVALID;
+  return run_two_pass(e, [&]() -> int {
+    T scratch; float* scale; float* shift;
+    TRY(gn_scale_shift(e, x0, C1 > 0 ? x1 : nullptr, C0, C1, in_f32, N, HW, groups, gamma, beta, eps, nullptr, 0, nullptr, 0, false, &scratch, &scale, &shift));
     if (!e->dry) {
       SDM_CHECK_DEV(e, dev_memcpy_d2d(scale_out, scale, (size_t)N * (C0 + C1) * 4, e->stream));
       SDM_CHECK_DEV(e, dev_memcpy_d2d(shift_out, shift, (size_t)N * (C0 + C1) * 4, e->stream));

@@ -85,7 +85,7 @@ EXPORTS = [
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_band_tiles", "sdm_apply_matte_tiles", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
     "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background", "sdm_harmonize", "sdm_matte_metrics",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
-    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_stats", "sdm_op_gn_partials", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
+    "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_stats", "sdm_op_gn_partials", "sdm_op_gn_tables", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias", "sdm_debug_patch_token_map", "sdm_op_groupnorm_p3", "sdm_op_gemm_p3_tokens", "sdm_op_mask_bias_tokens", "sdm_op_active_tiles",
     "sdm_op_cross_patch_planes", "sdm_op_cross_patch_planes_ex", "sdm_op_attention_shared", "sdm_debug_cross_attention", "sdm_op_cross_core",
     "sdm_set_option", "sdm_get_option", "sdm_reset_options", "sdm_option_name", "sdm_option_help", "sdm_kernel_counts", "sdm_kernel_counts_reset",
@@ -155,6 +155,7 @@ class Bindings:
             "sdm_op_conv_stats": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32,
                                         f32, i32, i32, vp, vp, f32, i32, i32, vp, i32, vp, i32, vp, i32, C.POINTER(i32)]),
             "sdm_op_gn_partials": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp]),
+            "sdm_op_gn_tables": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp]),
             "sdm_op_gemm_p3": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, f32, i32, vp, vp, C.POINTER(i32)]),
             "sdm_op_conv_up_stats": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, C.POINTER(i32)]),
             "sdm_debug_run_layer": (i32, [vp, C.c_char_p, vp, i32, i32, i32, vp, i32]),
@@ -1360,6 +1361,20 @@ class Engine:
         shift = torch.empty(N, C0 + C1, dtype=torch.float32, device=st0.device)
         self._check(self.lib.sdm_op_gn_partials(self.h, _ptr(st0), rows0, _ptr(st1), rows1, C0, C1, N, int(HW), groups, _ptr(gamma), _ptr(beta), float(eps),
                                                 _ptr(scale), _ptr(shift)), "sdm_op_gn_partials")
+        return scale, shift
+
+    def op_gn_tables(self, x0, gamma, beta, eps, groups=32, x1=None):
+        """Test hook: the stand-alone GroupNorm statistics alone (gn_stats_kernel + gn_finalize_kernel) on x0 [N,H,W,C0] (+ x1, the second concat source),
+        fp32 or fp16 -> (scale [N,C0+C1], shift [N,C0+C1])."""
+        x0 = x0.contiguous()
+        x1 = x1.contiguous() if x1 is not None else None
+        N, H, W_, C0 = x0.shape
+        C1 = x1.shape[-1] if x1 is not None else 0
+        gamma, beta = gamma.float().contiguous(), beta.float().contiguous()
+        scale = torch.empty(N, C0 + C1, dtype=torch.float32, device=x0.device)
+        shift = torch.empty(N, C0 + C1, dtype=torch.float32, device=x0.device)
+        self._check(self.lib.sdm_op_gn_tables(self.h, _ptr(x0), _ptr(x1), C0, C1, int(x0.dtype == torch.float32), N, H * W_, groups, _ptr(gamma), _ptr(beta),
+                                              float(eps), _ptr(scale), _ptr(shift)), "sdm_op_gn_tables")
         return scale, shift
 
     def op_conv_up_stats(self, x, w, bias=None):

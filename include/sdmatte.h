@@ -787,6 +787,10 @@ int sdm_op_conv_stats(sdm_ctx* ctx, const void* in0, const void* in1, int C0, in
  * rows of images of HW pixels -> scale [N][C0 + C1] = rstd * gamma, shift [N][C0 + C1] = beta - mean * rstd * gamma.  C0 % 8 == 0, (C0 + C1) % 8 == 0. */
 int sdm_op_gn_partials(sdm_ctx* ctx, const float* st0, int rows0, const float* st1, int rows1, int C0, int C1, int N, int HW, int groups,
                        const float* gamma, const float* beta, float eps, float* scale, float* shift);
+/* Test hook: the stand-alone GroupNorm statistics (gn_stats_kernel + gn_finalize_kernel) alone.  x0 [N][HW][C0] (+ x1 [N][HW][C1], C1 = 0 for none), fp32
+ * (in_f32) or fp16 -> the same tables as sdm_op_gn_partials.  C0 % 8 == 0, (C0 + C1) % 8 == 0. */
+int sdm_op_gn_tables(sdm_ctx* ctx, const void* x0, const void* x1, int C0, int C1, int in_f32, int N, int HW, int groups, const float* gamma,
+                     const float* beta, float eps, float* scale, float* shift);
 /* bench only (tools/gemm_p3_bench.py): ms per launch of the plane-fed GEMM on random operands; epi_flags = epilogue (0 fp32, 1 GEGLU, 2 q|k|v planes, 3 planes,
  * 4 fp32 + statistics) | 256 for an fp32 residual */
 float sdm_bench_gemm_p3(sdm_ctx* ctx, long M, int K, int O, int epi_flags, int iters);
