@@ -24,6 +24,7 @@
 #include "k_temporal.h"
 #include "k_motion.h"
 #include "k_defocus.h"
+#include "k_plate.h"
 #include "k_harmonize.h"
 #include "k_metrics.h"
 #include "k_roi.h"
@@ -2587,7 +2588,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background, sdm_harmonize, sdm_matte_metrics, sdm_band_tiles, sdm_apply_matte_tiles) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background, sdm_fill_background, sdm_harmonize, sdm_matte_metrics, sdm_band_tiles, sdm_apply_matte_tiles) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -3670,6 +3671,76 @@ int sdm_defocus_background(sdm_ctx* e, const float* image, const float* alpha, c
       prof_end(e);
     }
     tfree(e, plane);
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// the photo without its subject: push-pull fill (k_plate.h)
+// ------------------------------------------------------------------------------------------------
+/* The pyramid (levels 1 .. S, 16 bytes per pixel, about a third of a level-0 plane of that width) lives in the activation arena.  1 + 2 ceil(S / 3)
+ * launches, S = the number of levels with max(h_l, w_l) > 32: a function of H and W only. */
+int sdm_fill_background(sdm_ctx* e, const float* image, const float* alpha, const float* bg, const float* hole, int B, int H, int W, float alpha_cut,
+                        float* out, int ptr_kind, void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !alpha || !out) return SDM_ERR_INVALID;
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "fill background: bad image size %dx%dx%d", B, H, W);
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "fill background: %dx%dx%d is too large (sides up to %d, %d pixels in all)", B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  if (!std::isfinite(alpha_cut) || !(alpha_cut >= SDM_PLATE_MIN_CUT) || !(alpha_cut <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "fill background: alpha_cut = %g must be a finite number in [%g, 1]", (double)alpha_cut, (double)SDM_PLATE_MIN_CUT);
+  static_assert(SDM_PLATE_SMALL_PX == SDM_PLATE_SMALL * SDM_PLATE_SMALL && SDM_PLATE_GROUP == 3 && SDM_PLATE_TW == 64 && SDM_PLATE_TH == 32,
+                "k_plate.h is written for these");
+  int S = 0;
+  while (std::max(plate_dim(H, S), plate_dim(W, S)) > SDM_PLATE_SMALL) ++S;
+  size_t off[17] = {0}, pyr_px = 0;                                     // off[l]: first pixel of level l's plane, l = 1 .. S (SDM_FG_MAX_SIDE = 2^15: S <= 10)
+  for (int l = 1; l <= S; ++l) { off[l] = pyr_px; pyr_px += (size_t)B * plate_dim(H, l) * plate_dim(W, l); }
+  const size_t px = (size_t)B * H * W;
+  // (an absent plane is an empty span behind a valid pointer: the staging copies 0 bytes of it; with bg the image is not read)
+  IoSpan in[] = {{(void*)image, bg ? 0 : px * 12}, {(void*)alpha, px * 4}, {(void*)(bg ? bg : image), bg ? px * 12 : 0},
+                 {(void*)(hole ? hole : alpha), hole ? px * 4 : 0}};
+  IoSpan outs[] = {{out, px * 12}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_alpha = (const float*)in[1].p; float* d_out = (float*)outs[0].p;
+    const float* d_C = bg ? (const float*)in[2].p : (const float*)in[0].p; const float* d_hole = hole ? (const float*)in[3].p : nullptr;
+    T pyr;
+    if (S > 0) pyr = talloc(e, 1, 1, (int)pyr_px, 4, 1);
+    if (!e->dry) {
+      PlateIn pin;
+      pin.C = d_C; pin.alpha = d_alpha; pin.hole = d_hole; pin.cut = alpha_cut;
+      pin.vec = W % 4 == 0 && aligned16(d_C) && aligned16(d_alpha) && (!d_hole || aligned16(d_hole)) && aligned16(d_out) ? 1 : 0;
+      auto plane = [&](int l) -> f32x4* { return (l >= 1 && l <= S) ? (f32x4*)pyr.p + off[l] : nullptr; };
+      auto lpx = [&](int l) -> double { return (double)B * plate_dim(H, l) * plate_dim(W, l); };
+      const double in_bpp = 16.0 + (d_hole ? 4.0 : 0.0);
+      auto tiles = [&](int l) -> unsigned { return (unsigned)(B * sdm_cdiv(plate_dim(H, l), SDM_PLATE_TH) * sdm_cdiv(plate_dim(W, l), SDM_PLATE_TW)); };
+      for (int l = 0; l < S; l += SDM_PLATE_GROUP) {
+        const int n = std::min(SDM_PLATE_GROUP, S - l);
+        double bytes = lpx(l) * (l ? 16.0 : in_bpp);
+        for (int k = 1; k <= n; ++k) bytes += 16.0 * lpx(l + k);
+        prof_begin(e, "plate_pull", 0, bytes);
+        count_kernel("plate_pull");
+        SDM_LAUNCH(plate_pull_kernel, dim3(tiles(l)), dim3(256), 0, e->stream, pin, (const f32x4*)plane(l), B, H, W, l, n, plane(l + 1), plane(l + 2),
+                   plane(l + 3));
+        prof_end(e);
+      }
+      prof_begin(e, "plate_small", 0, S ? 32.0 * lpx(S) : (double)px * (in_bpp + 12.0));
+      count_kernel("plate_small");
+      SDM_LAUNCH(plate_small_kernel, dim3((unsigned)B), dim3(SDM_PLATE_SMALL_PX), 0, e->stream, pin, plane(S), B, H, W, S, d_out);
+      prof_end(e);
+      for (int top = S; top > 0;) {                                     // the first push takes what three do not divide
+        const int n = top % SDM_PLATE_GROUP ? top % SDM_PLATE_GROUP : SDM_PLATE_GROUP, lf = top - n;
+        // bytes: the tile's own level in and out; the levels above it with their halo (counted without it: a ring of one pixel)
+        double bytes = lf ? 32.0 * lpx(lf) : (double)px * (in_bpp + 12.0);
+        for (int k = 1; k <= n; ++k) bytes += 16.0 * lpx(lf + k);
+        prof_begin(e, "plate_push", 0, bytes);
+        count_kernel("plate_push");
+        SDM_LAUNCH(plate_push_kernel, dim3(tiles(lf)), dim3(256), 0, e->stream, pin, (const f32x4*)plane(top), (const f32x4*)(n == 3 ? plane(lf + 2) : nullptr),
+                   (const f32x4*)(n >= 2 ? plane(lf + 1) : nullptr), plane(lf), B, H, W, lf, n, d_out);
+        prof_end(e);
+        top = lf;
+      }
+    }
+    if (S > 0) tfree(e, pyr);
     return 0;
   });
 }

@@ -83,7 +83,7 @@ EXPORTS = [
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_band_tiles", "sdm_apply_matte_tiles", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
-    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background", "sdm_harmonize", "sdm_matte_metrics",
+    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background", "sdm_fill_background", "sdm_harmonize", "sdm_matte_metrics",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_stats", "sdm_op_gn_partials", "sdm_op_gn_tables", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias", "sdm_debug_patch_token_map", "sdm_op_groupnorm_p3", "sdm_op_gemm_p3_tokens", "sdm_op_mask_bias_tokens", "sdm_op_active_tiles",
@@ -136,6 +136,7 @@ class Bindings:
             "sdm_smooth_alpha_temporal": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, i32, vp]),
             "sdm_smooth_alpha_motion": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, vp, i32, vp]),
             "sdm_defocus_background": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, vp]),
+            "sdm_fill_background": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, i32, vp]),
             "sdm_harmonize": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
             "sdm_matte_metrics": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
@@ -1144,6 +1145,49 @@ class Engine:
         stream = self._check_io("defocus_background", image_bhwc, alpha_bhw, fg, bg, out)
         self._check(self.lib.sdm_defocus_background(self.h, _ptr(image_bhwc), _ptr(alpha_bhw), _ptr(fg), _ptr(bg), B, H, W, radius_px, highlight_gain,
                                                     highlight_threshold, _ptr(out), self._kind(image_bhwc), stream), "sdm_defocus_background")
+        if sync:
+            self.synchronize()
+        return out
+
+    # SDM_PLATE_* (include/sdmatte.h)
+    PLATE_ALPHA_CUT = 0.0625
+    PLATE_MIN_CUT = 2.0 ** -10
+
+    @staticmethod
+    def plate_launches(H, W):
+        """(launches of plate_pull, plate_small, plate_push) of a fill_background call on H x W: the formula of include/sdmatte.h."""
+        S = 0
+        while max(-(-int(H) >> S), -(-int(W) >> S)) > 32:
+            S += 1
+        return (S + 2) // 3, 1, (S + 2) // 3
+
+    def fill_background(self, image_bhwc, alpha_bhw, bg=None, hole=None, alpha_cut=PLATE_ALPHA_CUT, sync=True):
+        """The photo without its subject (sdm_fill_background, defined in include/sdmatte.h): the background colours (`bg` if given, else the image)
+        count with the weight clamp(1 - a / alpha_cut, 0, 1), a the alpha (or the larger of alpha and `hole`), and the rest is filled by push-pull:
+        weighted averages down a pyramid, bilinear interpolation back up.  Pixels of weight 1 come back bit for bit, and the subject's colour never
+        enters the plate.  `bg` is the background plane of `estimate_foreground`; with it alpha_cut = 1 is the natural value, without it the default
+        1/16 keeps contaminated soft pixels out.  Returns fp32 [B,H,W,3] on the inputs' device.  `sum(plate_launches(H, W))` kernel launches.  Needs no
+        loaded weights.  `sdmatte_nodes.clean_plate` is the same function in torch, equal to fp32 rounding."""
+        if image_bhwc.dim() != 4 or image_bhwc.shape[-1] != 3 or image_bhwc.numel() == 0:
+            raise ValueError(f"fill_background: image must be a non-empty [B,H,W,3], got {tuple(image_bhwc.shape)}")
+        B, H, W, _ = (int(v) for v in image_bhwc.shape)
+        if tuple(alpha_bhw.shape) != (B, H, W):
+            raise ValueError(f"fill_background: alpha must be [B,H,W] = {(B, H, W)}, got {tuple(alpha_bhw.shape)}")
+        if bg is not None and tuple(bg.shape) != (B, H, W, 3):
+            raise ValueError(f"fill_background: bg must be [B,H,W,3] = {(B, H, W, 3)}, got {tuple(bg.shape)}")
+        if hole is not None and tuple(hole.shape) != (B, H, W):
+            raise ValueError(f"fill_background: hole must be [B,H,W] = {(B, H, W)}, got {tuple(hole.shape)}")
+        if max(H, W) > self.FG_MAX_SIDE or B * H * W > self.FG_MAX_PIXELS:
+            raise ValueError(f"fill_background: {(B, H, W)} is too large (sides up to {self.FG_MAX_SIDE}, {self.FG_MAX_PIXELS} pixels in all)")
+        alpha_cut = self._check_f32_range("fill_background", "alpha_cut", alpha_cut, self.PLATE_MIN_CUT, 1)
+        image_bhwc = image_bhwc.float().contiguous()
+        alpha_bhw = alpha_bhw.float().contiguous()
+        bg = bg.float().contiguous() if bg is not None else None
+        hole = hole.float().contiguous() if hole is not None else None
+        out = torch.empty(B, H, W, 3, dtype=torch.float32, device=image_bhwc.device)
+        stream = self._check_io("fill_background", image_bhwc, alpha_bhw, bg, hole, out)
+        self._check(self.lib.sdm_fill_background(self.h, _ptr(image_bhwc), _ptr(alpha_bhw), _ptr(bg), _ptr(hole), B, H, W, alpha_cut, _ptr(out),
+                                                 self._kind(image_bhwc), stream), "sdm_fill_background")
         if sync:
             self.synchronize()
         return out

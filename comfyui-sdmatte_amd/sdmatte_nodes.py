@@ -35,6 +35,9 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
     light wrap along the edge, then "over"), in one to four kernel launches; `harmonize_map` / `harmonize_cutout` below are its torch restatement;
   * and one registered only with SDMATTE_METRICS_NODE=1: `SDMatteMetrics` scores an alpha against a ground truth with the matting literature's SAD, MSE,
     Grad and Conn over the trimap's unknown band, on the GPU; `matte_metrics` below is its torch restatement;
+  * and one registered only with SDMATTE_PLATE_NODE=1: `SDMatteCleanPlate` gives back the photo without its subject (the hole filled by push-pull from
+    the background around it; background pixels come back bit for bit), in 1 + 2 ceil(S / 3) kernel launches; `clean_plate` below is its torch
+    restatement;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -1146,6 +1149,57 @@ def defocus_background(image, alpha, fg=None, bg=None, radius_px=16, highlight_g
     return a.unsqueeze(-1) * Fg + (1.0 - a).unsqueeze(-1) * blur
 
 
+def clean_plate(image, alpha, bg=None, hole=None, alpha_cut=0.0625, dtype=torch.float32):
+    """`Engine.fill_background` in torch, on the tensors' own device (the function defined in include/sdmatte.h): image [B,H,W,3], alpha [B,H,W],
+    optional background colours [B,H,W,3] and hole plane [B,H,W] -> [B,H,W,3] in `dtype` (fp32 or fp64), the photo without its subject.  Equal to the
+    kernels to fp32 rounding; the identities of the header hold here too.  w_0 is formed in fp32 whatever the dtype, as the contract has it.  The pull
+    is four strided slices of a level padded to even sides with zero weights (a missing child adds 0), the push four gathers."""
+    import torch.nn.functional as F
+    from .engine import Engine
+    if image.dim() != 4 or image.shape[-1] != 3 or image.numel() == 0:
+        raise ValueError(f"clean_plate: image must be a non-empty [B,H,W,3], got {tuple(image.shape)}")
+    if tuple(alpha.shape) != tuple(image.shape[:3]):
+        raise ValueError(f"clean_plate: alpha must be [B,H,W] = {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+    if bg is not None and tuple(bg.shape) != tuple(image.shape):
+        raise ValueError(f"clean_plate: bg must be [B,H,W,3] = {tuple(image.shape)}, got {tuple(bg.shape)}")
+    if hole is not None and tuple(hole.shape) != tuple(alpha.shape):
+        raise ValueError(f"clean_plate: hole must be [B,H,W] = {tuple(alpha.shape)}, got {tuple(hole.shape)}")
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"clean_plate: dtype must be torch.float32 or torch.float64, got {dtype}")
+    cut = Engine._check_f32_range("clean_plate", "alpha_cut", alpha_cut, Engine.PLATE_MIN_CUT, 1)
+    dev = image.device
+    clean = lambda t: torch.nan_to_num(t.detach().float(), nan=0.0).clamp(0.0, 1.0)
+    a = clean(alpha)
+    if hole is not None:
+        a = torch.maximum(a, clean(hole))
+    w = (1.0 - a / torch.tensor(cut, dtype=torch.float32, device=dev)).clamp(0.0, 1.0).to(dtype).unsqueeze(-1)
+    C = (bg if bg is not None else image).detach().float().to(dtype)
+    levels = [(C, w)]
+    while C.shape[1] > 1 or C.shape[2] > 1:
+        h, ww = C.shape[1:3]
+        pad = (0, 0, 0, ww % 2, 0, h % 2)
+        Cp, wp = F.pad(C, pad), F.pad(w, pad)
+        kids = [(wp[:, dy::2, dx::2], Cp[:, dy::2, dx::2]) for dy, dx in ((0, 0), (0, 1), (1, 0), (1, 1))]
+        Sw = ((kids[0][0] + kids[1][0]) + kids[2][0]) + kids[3][0]
+        Sc = ((kids[0][0] * kids[0][1] + kids[1][0] * kids[1][1]) + kids[2][0] * kids[2][1]) + kids[3][0] * kids[3][1]
+        some = Sw > 0
+        C = torch.where(some, Sc / torch.where(some, Sw, torch.ones_like(Sw)), torch.zeros_like(Sc))
+        w = Sw.clamp(max=1.0)
+        levels.append((C, w))
+    Fl = levels[-1][0]
+    for C, w in reversed(levels[:-1]):
+        h, ww = C.shape[1:3]
+        hc, wc = Fl.shape[1:3]
+        y, x = torch.arange(h, device=dev), torch.arange(ww, device=dev)
+        ny, nx = y >> 1, x >> 1
+        fy = (ny + (y & 1) * 2 - 1).clamp(0, hc - 1)
+        fx = (nx + (x & 1) * 2 - 1).clamp(0, wc - 1)
+        Fn, Ff = Fl[:, ny], Fl[:, fy]
+        U = 0.75 * (0.75 * Fn[:, :, nx] + 0.25 * Fn[:, :, fx]) + 0.25 * (0.75 * Ff[:, :, nx] + 0.25 * Ff[:, :, fx])
+        Fl = w * C + (1.0 - w) * U
+    return Fl
+
+
 def _harmonize_opponent(c):
     return torch.stack([((c[..., 0] + c[..., 1]) + c[..., 2]) / 3.0, c[..., 0] - c[..., 1], (c[..., 0] + c[..., 1]) / 2.0 - c[..., 2]], -1)
 
@@ -2041,6 +2095,62 @@ class SDMatteDefocus:
         return (eng.defocus_background(image, alpha, fg, bg, *params, sync=False).cpu(), )
 
 
+class SDMatteCleanPlate:
+    """Image + alpha -> the photo without its subject (the "clean plate"): the hole is filled by push-pull from the background around it, the background
+    itself comes back bit for bit, and the subject's colour never enters.  For moving the subject inside its own photo, a two-layer parallax split, a
+    background for the defocus / harmonize nodes, or the pre-fill in front of an inpainting model.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE", {"tooltip": "the photo"}),
+                             "alpha": ("MASK", {"tooltip": "alpha matte of the photo (alpha_mask of Apply SDMatte)"})},
+                "optional": {"hole": ("MASK", {"tooltip": "more to take out (a shadow, a second object): combined with the alpha by max"}),
+                             "background": ("IMAGE", {"tooltip": "background colours (SDMatte Foreground Colours); default: the photo"}),
+                             "alpha_cut": ("FLOAT", {"default": 0.0625, "min": 2.0 ** -10, "max": 1.0, "step": 0.0001,
+                                                     "tooltip": "pixels count as background with the weight 1 - alpha / alpha_cut; 1 with clean background "
+                                                                "colours, small without"}),
+                             "decontaminate": ("BOOLEAN", {"default": False,
+                                                           "tooltip": "with no background connected: estimate the background colours from the photo first"}),
+                             "force_cpu": ("BOOLEAN", {"default": False, "tooltip": "evaluate the torch restatement on the CPU instead of the GPU call"})}}
+
+    RETURN_TYPES = ("IMAGE", )
+    RETURN_NAMES = ("plate", )
+    FUNCTION = "fill"
+    CATEGORY = "Matting/SDMatte"
+
+    def fill(self, image, alpha, hole=None, background=None, alpha_cut=0.0625, decontaminate=False, force_cpu=False):
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        if alpha.dim() == 2:
+            alpha = alpha.unsqueeze(0)
+        if tuple(alpha.shape) != tuple(image.shape[:3]):
+            raise ValueError(f"[SDMatte] alpha must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(alpha.shape)}")
+        if hole is not None:
+            if hole.dim() == 2:
+                hole = hole.unsqueeze(0)
+            if tuple(hole.shape) != tuple(image.shape[:3]):
+                raise ValueError(f"[SDMatte] hole must be [B,H,W] of the image {tuple(image.shape[:3])}, got {tuple(hole.shape)}")
+        if background is not None and tuple(background.shape) != tuple(image.shape):
+            raise ValueError(f"[SDMatte] background must be [B,H,W,3] of the image {tuple(image.shape)}, got {tuple(background.shape)}")
+        alpha_cut = float(alpha_cut)
+        estimate = bool(decontaminate) and background is None
+        if force_cpu:      # an explicit request, never a silent substitute: the same functions in torch
+            image, alpha = image.detach().cpu(), alpha.detach().cpu()
+            hole = hole.detach().cpu() if hole is not None else None
+            bg = background.detach().cpu() if background is not None else None
+            if estimate:
+                _, bg, _ = estimate_foreground(image, alpha)
+            return (clean_plate(image, alpha, bg, hole, alpha_cut), )
+        device = _torch_device()
+        eng = _trimap_engine(device)
+        image, alpha = image.detach().to(device), alpha.detach().to(device)
+        hole = hole.detach().to(device) if hole is not None else None
+        bg = background.detach().to(device) if background is not None else None
+        if estimate:       # the plane stays on the device: the two calls are ordered on torch's current stream
+            _, bg = eng.estimate_foreground(image, alpha, sync=False)
+        return (eng.fill_background(image, alpha, bg, hole, alpha_cut, sync=False).cpu(), )
+
+
 class SDMatteHarmonize:
     """Foreground + alpha + a new background -> the cut-out sitting in that scene on the GPU: its colours matched to the scene's light (mean and spread of
     brightness and of the two colour axes), the scene's light wrapped around its edge, then composed.  One to four kernel launches.  Needs no checkpoint."""
@@ -2191,9 +2301,18 @@ def with_tiled_node(mappings, tiled: bool = True):
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1, SDMATTE_HARMONIZE_NODE=1, SDMATTE_METRICS_NODE=1, SDMATTE_TILED_NODE=1), like the multi-GPU fan-out
+def with_plate_node(mappings, plate: bool = True):
+    """(classes, names) of `mappings` plus `SDMatteCleanPlate` when `plate`; the argument is not modified (as `with_harmonize_node`)."""
+    classes, names = dict(mappings[0]), dict(mappings[1])
+    if plate:
+        classes["SDMatteCleanPlate"] = SDMatteCleanPlate
+        names["SDMatteCleanPlate"] = "SDMatte Clean Plate (Fill Background)"
+    return classes, names
+
+
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1, SDMATTE_HARMONIZE_NODE=1, SDMATTE_METRICS_NODE=1, SDMATTE_TILED_NODE=1, SDMATTE_PLATE_NODE=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
-NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_tiled_node(with_metrics_node(with_harmonize_node(node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
+NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_plate_node(with_tiled_node(with_metrics_node(with_harmonize_node(node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
                                                                 os.environ.get("SDMATTE_REFINE_NODE") == "1",
                                                                 os.environ.get("SDMATTE_CLEAN_NODE") == "1",
@@ -2206,4 +2325,5 @@ NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_tiled_node(with_metrics_n
                                                                 os.environ.get("SDMATTE_DEFOCUS_NODE") == "1"),
                                                                       os.environ.get("SDMATTE_HARMONIZE_NODE") == "1"),
                                                                       os.environ.get("SDMATTE_METRICS_NODE") == "1"),
-                                                                      os.environ.get("SDMATTE_TILED_NODE") == "1")
+                                                                      os.environ.get("SDMATTE_TILED_NODE") == "1"),
+                                                                      os.environ.get("SDMATTE_PLATE_NODE") == "1")

@@ -614,6 +614,45 @@ int sdm_smooth_alpha_motion(sdm_ctx* ctx, const float* image_bhwc, const float* 
 int sdm_defocus_background(sdm_ctx* ctx, const float* image_bhwc, const float* alpha_bhw, const float* fg_bhwc, const float* bg_bhwc, int B, int H, int W,
                            int radius_px, float highlight_gain, float highlight_threshold, float* out_bhwc, int ptr_kind, void* stream);
 
+/* The photo without its subject (beyond the reference): the clean plate.  Every other call keeps the subject; this one gives back the background behind it,
+ * for moving or rescaling the subject inside its own photo (sdm_compose_canvas over the plate), for a two-layer parallax split, as a background without a
+ * subject-shaped hole for sdm_harmonize / sdm_defocus_background, or as the pre-fill in front of a generative inpainting model.  The hole is filled by
+ * push-pull: weighted averages down a pyramid, then bilinear interpolation back up that keeps every pixel the pyramid knows.  Deterministic, no weights.
+ * image, bg and out are fp32 [B,H,W,3]; alpha and hole are fp32 [B,H,W]; bg_bhwc and hole_bhw may each be NULL; all of one pointer kind.  Colours are
+ * used as they are.  They must be finite: a non-finite colour gives unspecified values, never an out-of-bounds access.
+ *   a       the alpha with NaN -> 0, then clamped to [0, 1].  With a hole plane, sanitised the same way, a = max(a, hole): a shadow, or a second object
+ *           to take out.
+ *   C       bg if given, else image (the image is then not read).  With the background plane of sdm_estimate_foreground the soft pixels carry clean
+ *           colours.
+ *   w_0     clamp(1 - a / alpha_cut, 0, 1), in fp32 with a true division: a == 0 gives exactly 1, a >= alpha_cut exactly 0.  alpha_cut is finite in
+ *           [SDM_PLATE_MIN_CUT, 1] = [2^-10, 1]; the default SDM_PLATE_ALPHA_CUT = 1/16 suits a call WITHOUT bg: a soft pixel of the image is contaminated
+ *           by the subject's colour, so only nearly pure background may count.  WITH bg the natural value is 1: w_0 = 1 - a.
+ *   levels  (h_0, w_0) = (H, W), (h_{l+1}, w_{l+1}) = (ceil(h_l / 2), ceil(w_l / 2)), down to (1, 1).
+ *   pull    pixel (i, j) of level l + 1 has the children (2 i + dy, 2 j + dx), dy, dx in {0, 1}, that exist at level l, taken in the order (0,0) (0,1)
+ *           (1,0) (1,1) and summed as ((t0 + t1) + t2) + t3, missing children left out:  Sw = sum of w_l,  Sc = sum of w_l * C_l per channel;
+ *           C_{l+1} = Sc / Sw if Sw > 0, else 0 (a true fp32 division);  w_{l+1} = min(1, Sw).
+ *   push    F_top = C_top.  For pixel (y, x) of level l:  ny = y >> 1, fy = clamp(ny + (y odd ? 1 : -1), 0, h_{l+1} - 1), and nx, fx from x likewise;
+ *           U = 0.75 * (0.75 * F[ny,nx] + 0.25 * F[ny,fx]) + 0.25 * (0.75 * F[fy,nx] + 0.25 * F[fy,fx])   (bilinear at half-pixel centres, integer addresses);
+ *           F_l = w_l * C_l + (1 - w_l) * U;   out = F_0.
+ * Everything is fp32, no FMA contraction, in the order written.  An image with no pixel of w_0 > 0 (all subject) gets an all-zero plate: there is no
+ * colour to fill with.  These hold bit for bit:
+ *   1. where w_0 == 1, out == C: background pixels are not touched, so there is no seam to hide;
+ *   2. a channel of C that is 0 wherever w_0 > 0 is 0 in the whole plate: the subject's colour never enters;
+ *   3. with an alpha of 0 and 1 only and C == 0.5 wherever a == 0, the plate is exactly 0.5 everywhere;
+ *   4. an image's result does not depend on the batch it is in; two calls, host and device pointers, and pointers 4 bytes off a 16-byte boundary all give
+ *      the same bits.
+ * sdmatte_nodes.clean_plate is the same function in torch (equal to fp32 rounding).
+ * Limits: B, H, W >= 1 within SDM_FG_MAX_SIDE / SDM_FG_MAX_PIXELS; alpha_cut as above: SDM_ERR_INVALID otherwise, with a message that names the argument,
+ * and then nothing is queued or written.  Stream contract and pointer kinds as sdm_make_trimap; sdm_last_forward_ms covers the launches.  Needs no
+ * weights.  Kernel launches (csrc/k_plate.h): with S = the number of levels l with max(h_l, w_l) > 32 (0 for a photo of at most 32 x 32, else
+ * ceil(log2(max(H, W) / 32))), ceil(S / 3) of `plate_pull`, one of `plate_small`, then ceil(S / 3) of `plate_push` in sdm_kernel_counts and the per-launch
+ * profile: 1 + 2 * ceil(S / 3) in all, a function of H and W only (7 at 2160 x 3840, where S = 7); no host readback, no atomics.  The pyramid (levels 1 .. S at
+ * 16 bytes per pixel, about a third of 16 bytes per pixel of the photo) lives in the activation arena; host pointers go through the I/O staging. */
+#define SDM_PLATE_ALPHA_CUT 0.0625f
+#define SDM_PLATE_MIN_CUT 0.0009765625f
+int sdm_fill_background(sdm_ctx* ctx, const float* image_bhwc, const float* alpha_bhw, const float* bg_bhwc, const float* hole_bhw, int B, int H, int W,
+                        float alpha_cut, float* out_bhwc, int ptr_kind, void* stream);
+
 /* The cut-out in its new scene (beyond the reference): colour match and light wrap.  A subject shot under one light and placed over a scene under another
  * looks pasted on with a plain "over": its colours do not match the scene's light, and its edge carries none of it.  This call moves the subject's colour
  * statistics towards the scene's, lets the scene's light spill over the subject's edge, and composes.  No weights.
@@ -741,7 +780,7 @@ void sdm_kernel_counts_reset(void);
 /* Block until everything queued on the engine stream has finished. */
 int sdm_synchronize(sdm_ctx* ctx);
 
-/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal / sdm_smooth_alpha_motion / sdm_defocus_background / sdm_harmonize / sdm_matte_metrics: their launches), measured with HIP events on the
+/* Time (ms) spent by the GPU in the last sdm_forward/sdm_apply_matte (or sdm_make_trimap / sdm_clean_mask / sdm_subject_roi / sdm_estimate_foreground / sdm_refine_alpha_guided / sdm_compose_canvas / sdm_smooth_alpha_temporal / sdm_smooth_alpha_motion / sdm_defocus_background / sdm_fill_background / sdm_harmonize / sdm_matte_metrics: their launches), measured with HIP events on the
  * stream the kernels were launched on.  Valid after sdm_synchronize. */
 float sdm_last_forward_ms(sdm_ctx* ctx);
 
