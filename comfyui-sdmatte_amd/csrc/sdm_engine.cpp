@@ -26,6 +26,7 @@
 #include "k_defocus.h"
 #include "k_plate.h"
 #include "k_harmonize.h"
+#include "k_key.h"
 #include "k_metrics.h"
 #include "k_roi.h"
 #include "k_canvas.h"
@@ -2588,7 +2589,7 @@ struct NodeTail {
 // for DEVICE pointers, its place in the I/O staging for HOST pointers - before the body runs.  An absent optional output has bytes == 0.
 struct IoSpan { void* p; size_t bytes; };
 
-// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background, sdm_fill_background, sdm_harmonize, sdm_matte_metrics, sdm_band_tiles, sdm_apply_matte_tiles) around its body, the
+// The scaffold of every product call (forward_impl, sdm_make_trimap, sdm_clean_mask, sdm_subject_roi, sdm_estimate_foreground, sdm_refine_alpha_guided, sdm_compose_canvas, sdm_distance_field, sdm_offset_mask, sdm_outline, sdm_smooth_alpha_temporal, sdm_smooth_alpha_motion, sdm_defocus_background, sdm_fill_background, sdm_harmonize, sdm_screen_colour, sdm_chroma_key, sdm_matte_metrics, sdm_band_tiles, sdm_apply_matte_tiles) around its body, the
 // talloc / launch / tfree sequence that arena_two_pass runs twice.  The caller has checked its arguments.
 // Stream contract (include/sdmatte.h): kernels run on the engine's own stream.  For DEVICE pointers the caller names the stream on which it
 // produced the inputs and will consume the outputs (NULL = the device's default stream): the engine stream waits for everything queued there
@@ -3823,6 +3824,129 @@ int sdm_harmonize(sdm_ctx* e, const float* fg, const float* alpha, const float* 
     }
     if (wrap) tfree(e, tplane);
     if (match) { tfree(e, map); tfree(e, partials); }
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// green-screen shots: screen colour, key, trimap from the key, despill (k_key.h)
+// ------------------------------------------------------------------------------------------------
+static int key_size_check(sdm_ctx* e, const char* what, int B, int H, int W) {
+  if (B <= 0 || H < 1 || W < 1) SDM_FAIL(e, SDM_ERR_INVALID, "%s: bad image size %dx%dx%d", what, B, H, W);
+  if (H > SDM_FG_MAX_SIDE || W > SDM_FG_MAX_SIDE || (double)B * H * W > (double)SDM_FG_MAX_PIXELS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "%s: %dx%dx%d is too large (sides up to %d, %d pixels in all)", what, B, H, W, SDM_FG_MAX_SIDE, SDM_FG_MAX_PIXELS);
+  return 0;
+}
+
+/* The histograms (one per slot), {eligible, mode} per slot and the partial sums (16 bytes per run of 4096 pixels) live in the activation arena.  Five
+ * launches, whatever the arguments. */
+int sdm_screen_colour(sdm_ctx* e, const float* image, int B, int H, int W, int hint, int share, float* screen, int32_t* info, int ptr_kind,
+                      void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !screen) return SDM_ERR_INVALID;
+  TRY(key_size_check(e, "screen colour", B, H, W));
+  if (hint < 0 || hint > 2) SDM_FAIL(e, SDM_ERR_INVALID, "screen colour: hint = %d must be 0 (any), 1 (green) or 2 (blue)", hint);
+  if (share != 0 && share != 1) SDM_FAIL(e, SDM_ERR_INVALID, "screen colour: share = %d must be 0 or 1", share);
+  // a histogram of 4096 ints per slot, cleared and indexed with ints
+  if (!share && B > SDM_KEY_MAX_SLOTS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "screen colour: B = %d is too large without share (at most %d images, one histogram each)", B, SDM_KEY_MAX_SLOTS);
+  static_assert(SDM_KEY_RUN_PX == SDM_KEY_RUN && SDM_KEY_HIST_PX % SDM_KEY_RUN_PX == 0 && SDM_KEY_NBIN == 4096 && (long long)SDM_KEY_MAX_SLOTS * SDM_KEY_NBIN < 2147483647LL,
+                "k_key.h is written for these");
+  const int slots = share ? 1 : B, per = share ? B : 1, P = per * H * W;             // P <= SDM_FG_MAX_PIXELS
+  const int runs = sdm_cdiv(P, SDM_KEY_RUN_PX), hblocks = sdm_cdiv(P, SDM_KEY_HIST_PX);
+  const CkColourParams prm = {SDM_KEY_MIN_SUM, SDM_KEY_MIN_SAT, hint};
+  const size_t px = (size_t)B * H * W;
+  IoSpan in[] = {{(void*)image, px * 12}};
+  IoSpan outs[] = {{screen, (size_t)B * 12}, {info, info ? (size_t)B * 16 : 0}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_image = (const float*)in[0].p;
+    float* d_screen = (float*)outs[0].p; int* d_info = info ? (int*)outs[1].p : nullptr;
+    T hist = talloc(e, slots, 1, SDM_KEY_NBIN, 1, 1), mode = talloc(e, slots, 1, 1, 2, 1), partials = talloc(e, slots, runs, 1, 4, 1);
+    if (!e->dry) {
+      const int vec = P % 4 == 0 && aligned16(d_image) ? 1 : 0;
+      const int nh = slots * SDM_KEY_NBIN;
+      prof_begin(e, "ck_clear", 0, (double)nh * 4);
+      count_kernel("ck_clear");
+      SDM_LAUNCH(ck_clear_kernel, dim3((unsigned)sdm_cdiv(nh, 256)), dim3(256), 0, e->stream, (int*)hist.p, nh);
+      prof_end(e);
+      prof_begin(e, "ck_hist", 0, (double)px * 12);
+      count_kernel("ck_hist");
+      SDM_LAUNCH(ck_hist_kernel, dim3((unsigned)(slots * hblocks)), dim3(256), 0, e->stream, d_image, slots, P, prm, vec, (int*)hist.p);
+      prof_end(e);
+      prof_begin(e, "ck_mode", 0, (double)nh * 4);
+      count_kernel("ck_mode");
+      SDM_LAUNCH(ck_mode_kernel, dim3((unsigned)slots), dim3(256), 0, e->stream, (const int*)hist.p, (int*)mode.p);
+      prof_end(e);
+      prof_begin(e, "ck_mean", 0, (double)px * 12 + (double)slots * runs * 16);
+      count_kernel("ck_mean");
+      SDM_LAUNCH(ck_mean_kernel, dim3((unsigned)(slots * runs)), dim3(256), 0, e->stream, d_image, slots, P, prm, vec, (const int*)mode.p,
+                 (CkPartial*)partials.p);
+      prof_end(e);
+      prof_begin(e, "ck_finalize", 0, (double)slots * runs * 16);
+      count_kernel("ck_finalize");
+      SDM_LAUNCH(ck_finalize_kernel, dim3((unsigned)slots), dim3(64), 0, e->stream, (const CkPartial*)partials.p, (const int*)mode.p, runs, per, d_screen,
+                 d_info);
+      prof_end(e);
+    }
+    tfree(e, partials); tfree(e, mode); tfree(e, hist);
+    return 0;
+  });
+}
+
+/* With trimap_bhw: the class bytes, the int16 plane of op_trimap and, without key_bhw, the key live in the activation arena (4 launches); 1 launch
+ * otherwise. */
+int sdm_chroma_key(sdm_ctx* e, const float* image, const float* screen, int screen_is_plane, int B, int H, int W, float clip_fg, float clip_bg,
+                   float sure_fg, float sure_bg, int erode_px, int dilate_px, float despill, float* key, float* trimap, float* despilled, int ptr_kind,
+                   void* stream_arg) {
+  if (e) dev_use(e->device);
+  if (!e || !image || !screen) return SDM_ERR_INVALID;
+  TRY(key_size_check(e, "chroma key", B, H, W));
+  if (!key && !trimap && !despilled) SDM_FAIL(e, SDM_ERR_INVALID, "chroma key: at least one of key_bhw, trimap_bhw, despilled_bhwc must be given");
+  if (screen_is_plane != 0 && screen_is_plane != 1) SDM_FAIL(e, SDM_ERR_INVALID, "chroma key: screen_is_plane = %d must be 0 or 1", screen_is_plane);
+  if (!std::isfinite(clip_fg) || !(clip_fg >= 0.0f) || !(clip_fg < 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "chroma key: clip_fg = %g must be a finite number in [0, 1)", (double)clip_fg);
+  if (!(clip_bg > clip_fg) || !(clip_bg <= 1.0f)) SDM_FAIL(e, SDM_ERR_INVALID, "chroma key: clip_bg = %g must lie in (clip_fg = %g, 1]", (double)clip_bg, (double)clip_fg);
+  if (!std::isfinite(sure_fg) || !(sure_fg >= -1.0f) || !(sure_fg <= 1.0f))
+    SDM_FAIL(e, SDM_ERR_INVALID, "chroma key: sure_fg = %g must be a finite number in [-1, 1]", (double)sure_fg);
+  if (!(sure_bg >= sure_fg) || !(sure_bg <= 2.0f)) SDM_FAIL(e, SDM_ERR_INVALID, "chroma key: sure_bg = %g must lie in [sure_fg = %g, 2]", (double)sure_bg, (double)sure_fg);
+  if (!(despill >= 0.0f) || !(despill <= 1.0f)) SDM_FAIL(e, SDM_ERR_INVALID, "chroma key: despill = %g must lie in [0, 1]", (double)despill);
+  if (erode_px < 0 || erode_px > SDM_TRIMAP_MAX_RADIUS || dilate_px < 0 || dilate_px > SDM_TRIMAP_MAX_RADIUS)
+    SDM_FAIL(e, SDM_ERR_INVALID, "chroma key: erode_px = %d, dilate_px = %d outside 0 .. %d", erode_px, dilate_px, SDM_TRIMAP_MAX_RADIUS);
+  if (trimap) TRY(trimap_check(e, B, H, W, erode_px, dilate_px));      // (the row kernel's grid; cannot fail within SDM_FG_MAX_PIXELS)
+  const CkKeyParams prm = {clip_fg, clip_bg, sure_fg, sure_bg, despill, SDM_KEY_MIN_SEP};
+  const size_t px = (size_t)B * H * W;
+  IoSpan in[] = {{(void*)image, px * 12}, {(void*)screen, screen_is_plane ? px * 12 : (size_t)B * 12}};
+  IoSpan outs[] = {{key, key ? px * 4 : 0}, {trimap, trimap ? px * 4 : 0}, {despilled, despilled ? px * 12 : 0}};
+  return product_call(e, ptr_kind, stream_arg, in, outs, [&]() -> int {
+    const float* d_image = (const float*)in[0].p; const float* d_screen = (const float*)in[1].p;
+    float* d_key = key ? (float*)outs[0].p : nullptr; float* d_trimap = trimap ? (float*)outs[1].p : nullptr;
+    float* d_desp = despilled ? (float*)outs[2].p : nullptr;
+    T cls, dist, keyplane;
+    if (trimap) {
+      cls = talloc(e, 1, 1, (int)((px + 1) / 2), 1, 0);                 // one byte per pixel
+      dist = talloc(e, B, H, W, 1, 0);
+      if (!key) keyplane = talloc(e, B, H, W, 1, 1);
+    }
+    if (!e->dry) {
+      float* k_out = d_key ? d_key : (trimap ? (float*)keyplane.p : nullptr);
+      const int vec = aligned16(d_image) && (!screen_is_plane || aligned16(d_screen)) && (!k_out || aligned16(k_out)) && (!d_desp || aligned16(d_desp)) ? 1 : 0;
+      prof_begin(e, "ck_key", 0, (double)px * ((screen_is_plane ? 24 : 12) + (k_out ? 4 : 0) + (trimap ? 1 : 0) + (d_desp ? 12 : 0)));
+      count_kernel("ck_key");
+      SDM_LAUNCH(ck_key_kernel, dim3((unsigned)sdm_cdiv(sdm_cdiv((int)px, 4), 256)), dim3(256), 0, e->stream, d_image, d_screen,
+                 screen_is_plane, B, H * W, prm, vec, k_out, trimap ? (unsigned char*)cls.p : (unsigned char*)nullptr, d_desp);
+      prof_end(e);
+      if (trimap) {
+        op_trimap(e, k_out, B, H, W, 0.5f, erode_px, dilate_px, (short*)dist.p, d_trimap);
+        prof_begin(e, "ck_veto", 0, (double)px * 9);
+        count_kernel("ck_veto");
+        SDM_LAUNCH(ck_veto_kernel, dim3((unsigned)sdm_cdiv((int)px, 256)), dim3(256), 0, e->stream, d_trimap, (const unsigned char*)cls.p, (long long)px);
+        prof_end(e);
+      }
+    }
+    if (trimap) {
+      if (!key) tfree(e, keyplane);
+      tfree(e, dist); tfree(e, cls);
+    }
     return 0;
   });
 }

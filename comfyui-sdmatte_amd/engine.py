@@ -83,7 +83,7 @@ EXPORTS = [
     "sdm_weight_stats", "sdm_missing_key", "sdm_weight_blob_bytes", "sdm_export_weight_blob", "sdm_import_weight_blob",
     "sdm_host_blob_bytes", "sdm_export_host_blob", "sdm_import_host_blob", "sdm_forward", "sdm_forward_ex", "sdm_forward_rect", "sdm_apply_matte", "sdm_apply_matte_node",
     "sdm_make_trimap", "sdm_clean_mask", "sdm_apply_matte_mask", "sdm_subject_roi", "sdm_apply_matte_roi", "sdm_subject_boxes", "sdm_apply_matte_boxes", "sdm_band_tiles", "sdm_apply_matte_tiles", "sdm_estimate_foreground", "sdm_refine_alpha_guided", "sdm_compose_canvas",
-    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background", "sdm_fill_background", "sdm_harmonize", "sdm_matte_metrics",
+    "sdm_distance_field", "sdm_offset_mask", "sdm_outline", "sdm_smooth_alpha_temporal", "sdm_smooth_alpha_motion", "sdm_defocus_background", "sdm_fill_background", "sdm_harmonize", "sdm_screen_colour", "sdm_chroma_key", "sdm_matte_metrics",
     "sdm_synchronize", "sdm_release_memory", "sdm_resident_bytes", "sdm_weight_bytes", "sdm_last_forward_ms", "sdm_profile_enable", "sdm_profile_count", "sdm_profile_get", "sdm_profile_dump",
     "sdm_op_conv", "sdm_op_conv_ex", "sdm_op_conv_stats", "sdm_op_gn_partials", "sdm_op_gn_tables", "sdm_op_conv_up_stats", "sdm_op_gemm_p3", "sdm_debug_run_layer", "sdm_debug_set_input_cmask", "sdm_debug_temb_row", "sdm_conv_num_cfgs", "sdm_bench_conv", "sdm_bench_attn", "sdm_bench_gemm_p3", "sdm_op_groupnorm", "sdm_op_layernorm", "sdm_op_attention", "sdm_op_attention_ex", "sdm_op_attention_split", "sdm_op_attention_split_ex", "sdm_debug_attn_plan", "sdm_op_resize_aa",
     "sdm_op_mask_bias", "sdm_debug_patch_token_map", "sdm_op_groupnorm_p3", "sdm_op_gemm_p3_tokens", "sdm_op_mask_bias_tokens", "sdm_op_active_tiles",
@@ -138,6 +138,8 @@ class Bindings:
             "sdm_defocus_background": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, vp]),
             "sdm_fill_background": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, i32, vp]),
             "sdm_harmonize": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
+            "sdm_screen_colour": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
+            "sdm_chroma_key": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, i32, i32, f32, vp, vp, vp, i32, vp]),
             "sdm_matte_metrics": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, i32, vp]),
             "sdm_synchronize": (i32, [vp]),
             "sdm_release_memory": (i32, [vp]),
@@ -1247,6 +1249,138 @@ class Engine:
             self.synchronize()
         res = (out, ) + ((fg_out, ) if return_fg else ()) + ((map_out, ) if return_map else ())
         return res[0] if len(res) == 1 else res
+
+    # SDM_KEY_* (include/sdmatte.h)
+    KEY_HINTS = {"any": 0, "green": 1, "blue": 2}
+    KEY_DEFAULTS = {"clip_fg": 0.15, "clip_bg": 0.85, "sure_fg": 0.05, "sure_bg": 0.95, "erode_px": 10, "dilate_px": 10, "despill": 1.0}
+    KEY_OUTPUTS = ("key", "trimap", "despilled")
+    KEY_MIN_SUM, KEY_MIN_SAT, KEY_MIN_SEP, KEY_RUN = 0.15, 0.25, 1.0 / 64, 4096
+    KEY_SCREEN_CUT = 0.25
+    KEY_MAX_SLOTS = 65536
+
+    @staticmethod
+    def key_launches(want=KEY_OUTPUTS):
+        """{launch name: count} of a chroma_key call that returns `want`: the counts of include/sdmatte.h."""
+        return {"ck_key": 1, "trimap_cols": 1, "trimap_rows": 1, "ck_veto": 1} if "trimap" in want else {"ck_key": 1}
+
+    SCREEN_COLOUR_LAUNCHES = {"ck_clear": 1, "ck_hist": 1, "ck_mode": 1, "ck_mean": 1, "ck_finalize": 1}
+
+    @classmethod
+    def _check_key_image(cls, what, image):
+        if image.dim() != 4 or image.shape[-1] != 3 or image.numel() == 0:
+            raise ValueError(f"{what}: image must be a non-empty [B,H,W,3], got {tuple(image.shape)}")
+        B, H, W, _ = (int(v) for v in image.shape)
+        if max(H, W) > cls.FG_MAX_SIDE or B * H * W > cls.FG_MAX_PIXELS:
+            raise ValueError(f"{what}: {(B, H, W)} is too large (sides up to {cls.FG_MAX_SIDE}, {cls.FG_MAX_PIXELS} pixels in all)")
+        return B, H, W
+
+    @classmethod
+    def _check_key_hint(cls, what, hint):
+        if hint in cls.KEY_HINTS:
+            return cls.KEY_HINTS[hint]
+        if isinstance(hint, int) and not isinstance(hint, bool) and hint in cls.KEY_HINTS.values():
+            return hint
+        raise ValueError(f"{what}: hint must be one of {sorted(cls.KEY_HINTS)} (or 0, 1, 2), got {hint!r}")
+
+    @classmethod
+    def _check_key_params(cls, what, clip_fg, clip_bg, sure_fg, sure_bg, erode_px, dilate_px, despill):
+        """The argument limits of sdm_chroma_key; returns the values that cross the C ABI (floats rounded to fp32)."""
+        clip_fg = cls._check_f32_range(what, "clip_fg", clip_fg, 0, 1)
+        if clip_fg >= 1:
+            raise ValueError(f"{what}: clip_fg must be a finite number in [0, 1), got {clip_fg!r}")
+        clip_bg = cls._check_f32_range(what, "clip_bg", clip_bg, clip_fg, 1, lo_open=True)
+        sure_fg = cls._check_f32_range(what, "sure_fg", sure_fg, -1, 1)
+        sure_bg = cls._check_f32_range(what, "sure_bg", sure_bg, sure_fg, 2)
+        despill = cls._check_f32_range(what, "despill", despill, 0, 1)
+        erode_px, dilate_px = cls._check_radii(what, erode_px, dilate_px)
+        return clip_fg, clip_bg, sure_fg, sure_bg, erode_px, dilate_px, despill
+
+    @classmethod
+    def _check_key_want(cls, what, want):
+        want = (want, ) if isinstance(want, str) else tuple(want)
+        if not want or len(set(want)) != len(want) or any(w not in cls.KEY_OUTPUTS for w in want):
+            raise ValueError(f"{what}: want must name one to three different outputs of {cls.KEY_OUTPUTS}, got {want!r}")
+        return want
+
+    @staticmethod
+    def _check_key_screen(what, screen, B, H, W):
+        """(screen as [B,3] or [B,H,W,3], is_plane): a colour per image ([B,3] or [B,1,1,3]) or a colour per pixel."""
+        if screen.dim() == 2 and tuple(screen.shape) == (B, 3):
+            return screen, 0
+        if screen.dim() == 4 and tuple(screen.shape) == (B, 1, 1, 3):
+            return screen.reshape(B, 3), 0
+        if screen.dim() == 4 and tuple(screen.shape) == (B, H, W, 3):
+            return screen, 1
+        raise ValueError(f"{what}: screen must be [B,3], [B,1,1,3] or [B,H,W,3] with (B, H, W) = {(B, H, W)}, got {tuple(screen.shape)}")
+
+    def screen_colour(self, image_bhwc, hint="green", share=False, return_info=False, sync=True):
+        """The colour of the green or blue screen behind a subject (sdm_screen_colour, defined in include/sdmatte.h): the mode of a 64 x 64 histogram
+        of the chromaticities of the saturated pixels (`hint`: "green", "blue" or "any"), then the mean colour of the pixels around the mode.  One screen
+        per image, or one for the whole batch with `share` (a clip).  Returns fp32 [B,3] on the input's device; with return_info also int32 [B,4] =
+        {eligible pixels, selected pixels, iu, iv} (no eligible pixel: colour 0 and {0, 0, -1, -1}).  Five kernel launches.  Needs no loaded weights.
+        `sdmatte_nodes.screen_colour` is the same function in torch: the integers exactly, the colour to fp32 rounding."""
+        B, H, W = self._check_key_image("screen_colour", image_bhwc)
+        hint = self._check_key_hint("screen_colour", hint)
+        if not share and B > self.KEY_MAX_SLOTS:
+            raise ValueError(f"screen_colour: B = {B} is too large without share (at most {self.KEY_MAX_SLOTS} images, one histogram each)")
+        image_bhwc = image_bhwc.float().contiguous()
+        dev = image_bhwc.device
+        screen = torch.empty(B, 3, dtype=torch.float32, device=dev)
+        info = torch.empty(B, 4, dtype=torch.int32, device=dev) if return_info else None
+        stream = self._check_io("screen_colour", image_bhwc, screen)
+        self._check(self.lib.sdm_screen_colour(self.h, _ptr(image_bhwc), B, H, W, hint, 1 if share else 0, _ptr(screen), _ptr(info),
+                                               self._kind(image_bhwc), stream), "sdm_screen_colour")
+        if sync:
+            self.synchronize()
+        return (screen, info) if return_info else screen
+
+    def chroma_key(self, image_bhwc, screen, clip_fg=0.15, clip_bg=0.85, sure_fg=0.05, sure_bg=0.95, erode_px=10, dilate_px=10, despill=1.0,
+                   want=KEY_OUTPUTS, sync=True):
+        """The colour-difference key of an image against its screen (sdm_chroma_key, defined in include/sdmatte.h).  `screen` is a colour per image
+        ([B,3] or [B,1,1,3], from `screen_colour`) or a colour per pixel ([B,H,W,3], the plate of `fill_background`).  Outputs, those named in `want`
+        in that order (one name: the tensor itself): "key" fp32 [B,H,W], 0 on the screen and 1 on the subject, linear between the clips; "trimap" fp32
+        [B,H,W], the trimap of `make_trimap(key, 0.5, erode_px, dilate_px)` with every definite pixel whose own colour does not agree (`sure_fg`,
+        `sure_bg`) set to 0.5; "despilled" fp32 [B,H,W,3], the image with the screen's excess taken out of its channel.  One kernel launch without the
+        trimap, four with it.  Needs no loaded weights.  `sdmatte_nodes.chroma_key` is the same function in torch, bit for bit."""
+        B, H, W = self._check_key_image("chroma_key", image_bhwc)
+        screen, is_plane = self._check_key_screen("chroma_key", screen, B, H, W)
+        params = self._check_key_params("chroma_key", clip_fg, clip_bg, sure_fg, sure_bg, erode_px, dilate_px, despill)
+        want = self._check_key_want("chroma_key", want)
+        image_bhwc = image_bhwc.float().contiguous()
+        screen = screen.float().contiguous()
+        dev = image_bhwc.device
+        outs = {"key": torch.empty(B, H, W, dtype=torch.float32, device=dev) if "key" in want else None,
+                "trimap": torch.empty(B, H, W, dtype=torch.float32, device=dev) if "trimap" in want else None,
+                "despilled": torch.empty(B, H, W, 3, dtype=torch.float32, device=dev) if "despilled" in want else None}
+        stream = self._check_io("chroma_key", image_bhwc, screen, *outs.values())
+        self._check(self.lib.sdm_chroma_key(self.h, _ptr(image_bhwc), _ptr(screen), is_plane, B, H, W, *params, _ptr(outs["key"]), _ptr(outs["trimap"]),
+                                            _ptr(outs["despilled"]), self._kind(image_bhwc), stream), "sdm_chroma_key")
+        if sync:
+            self.synchronize()
+        res = tuple(outs[w] for w in want)
+        return res[0] if len(res) == 1 else res
+
+    def key_screen(self, image_bhwc, hint="green", share=False, screen_correction=True, screen_cut=KEY_SCREEN_CUT, clip_fg=0.15, clip_bg=0.85,
+                   sure_fg=0.05, sure_bg=0.95, erode_px=10, dilate_px=10, despill=1.0, want=KEY_OUTPUTS, sync=True):
+        """A green-screen shot in one call: `screen_colour`, then `chroma_key`.  With `screen_correction` (the "screen correction" pass of a keyer) a
+        first key marks the subject, `fill_background(image, key, alpha_cut=screen_cut)` fills its hole with the screen around it, and the key is made
+        again against the screen's colour at each pixel, so that uneven lighting and shadows on the screen key out.  Returns the outputs named in
+        `want`, in that order, and then the screen: [B,3], or the plate [B,H,W,3] with screen_correction.  With device tensors the chain is queued
+        without a host sync between the calls, and no tensor leaves the device."""
+        self._check_key_image("key_screen", image_bhwc)
+        params = self._check_key_params("key_screen", clip_fg, clip_bg, sure_fg, sure_bg, erode_px, dilate_px, despill)
+        want = self._check_key_want("key_screen", want)
+        screen_cut = self._check_f32_range("key_screen", "screen_cut", screen_cut, self.PLATE_MIN_CUT, 1)
+        image_bhwc = image_bhwc.float().contiguous()
+        chain_sync = image_bhwc.device.type != "cuda"       # host pointers are synchronous anyway
+        screen = self.screen_colour(image_bhwc, hint, share, sync=chain_sync)
+        if screen_correction:
+            key = self.chroma_key(image_bhwc, screen, *params, want=("key", ), sync=chain_sync)
+            screen = self.fill_background(image_bhwc, key, alpha_cut=screen_cut, sync=chain_sync)
+        res = self.chroma_key(image_bhwc, screen, *params, want=want, sync=chain_sync)
+        if sync:
+            self.synchronize()
+        return (res if isinstance(res, tuple) else (res, )) + (screen, )
 
     # SDM_MM_* (include/sdmatte.h)
     METRICS_GRAD_SIGMA = 1.4

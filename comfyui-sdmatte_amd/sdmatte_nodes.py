@@ -38,6 +38,10 @@ signature (sdmatte_nodes.py:217-257), same `NODE_CLASS_MAPPINGS` / `NODE_DISPLAY
   * and one registered only with SDMATTE_PLATE_NODE=1: `SDMatteCleanPlate` gives back the photo without its subject (the hole filled by push-pull from
     the background around it; background pixels come back bit for bit), in 1 + 2 ceil(S / 3) kernel launches; `clean_plate` below is its torch
     restatement;
+  * and two registered only with SDMATTE_KEY_NODES=1, for green- and blue-screen shots: `SDMatteChromaKey` finds the screen's colour, keys the image
+    against it (optionally against the screen's colour at each pixel, the clean plate of a first key) and returns the trimap for the model, the key,
+    the despilled image and the screen; `SDMatteDespill` takes the screen's reflected light out of an image or a foreground; `screen_colour`,
+    `chroma_key` and `key_screen` below are their torch restatements;
   * `force_cpu=True` is rejected: this node has no CPU path (the reference's own force_cpu branch cannot run either:
     meta_arch.py hard-codes `.cuda()`).
 """
@@ -1274,6 +1278,133 @@ def harmonize_cutout(fg, alpha, bg, luma_strength=0.6, chroma_strength=0.8, cont
     return res[0] if len(res) == 1 else res
 
 
+def _key_dtype(what, dtype):
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: dtype must be torch.float32 or torch.float64, got {dtype}")
+    return dtype
+
+
+def _key_bins(image, hint):
+    """(eligible [B,H,W] bool, iu, iv int64 [B,H,W]) of sdm_screen_colour: fp32 whatever comes after, as the contract has it."""
+    r, g, b = image.detach().float().unbind(-1)
+    f = lambda v: torch.tensor(v, dtype=torch.float32, device=image.device)
+    s = (r + g) + b
+    mx = torch.where(g > r, g, r)
+    mx = torch.where(b > mx, b, mx)
+    mn = torch.where(g < r, g, r)
+    mn = torch.where(b < mn, b, mn)
+    ok = (s >= f(0.15)) & ((mx - mn) >= f(0.25) * s)
+    if hint == 1:
+        ok = ok & (g > r) & (g > b)
+    if hint == 2:
+        ok = ok & (b > r) & (b > g)
+
+    def index(c):
+        u = (c / s) * f(64.0)
+        return torch.where(u >= 0, torch.where(u < 64, u, f(63.0)), f(0.0)).to(torch.int64)
+    return ok, index(r), index(g)
+
+
+def screen_colour(image, hint="green", share=False, return_info=False, dtype=torch.float32):
+    """`Engine.screen_colour` in torch, on the tensor's own device (the function defined in include/sdmatte.h): image [B,H,W,3] -> the screen's colour
+    [B,3] in `dtype` (fp32 or fp64), with return_info also int32 [B,4] = {eligible pixels, selected pixels, iu, iv}.  The histogram, the mode and the
+    info are exact; the colour is equal to the kernels' to fp32 rounding (fp32: sums per run of 4096 pixels, then fp64, as the contract has it)."""
+    import torch.nn.functional as F
+    from .engine import Engine
+    B, H, W = Engine._check_key_image("screen_colour", image)
+    hint = Engine._check_key_hint("screen_colour", hint)
+    dtype = _key_dtype("screen_colour", dtype)
+    dev = image.device
+    ok, iu, iv = _key_bins(image, hint)
+    slots = 1 if share else B
+    c = image.detach().float().reshape(slots, -1, 3)
+    ok, iu, iv = ok.reshape(slots, -1), iu.reshape(slots, -1), iv.reshape(slots, -1)
+    P = c.shape[1]
+    colour = torch.zeros(slots, 3, dtype=dtype, device=dev)
+    info = torch.zeros(slots, 4, dtype=torch.int32, device=dev)
+    for s in range(slots):
+        idx = (iu[s] * 64 + iv[s])[ok[s]]
+        if idx.numel() == 0:
+            info[s, 2:] = -1
+            continue
+        hist = torch.bincount(idx, minlength=4096).view(64, 64)
+        pad = F.pad(hist, (1, 1, 1, 1))
+        C = sum(pad[dy:dy + 64, dx:dx + 64] for dy in range(3) for dx in range(3)).flatten()
+        mode = int((C == C.max()).nonzero()[0])
+        mu, mv = mode // 64, mode % 64
+        sel = ok[s] & ((iu[s] - mu).abs() <= 1) & ((iv[s] - mv).abs() <= 1)
+        n = int(sel.sum())
+        vals = torch.where(sel.unsqueeze(-1), c[s], torch.zeros_like(c[s])).to(dtype)
+        runs = -(-P // 4096)
+        vals = F.pad(vals, (0, 0, 0, runs * 4096 - P)).view(runs, 4096, 3)
+        colour[s] = (vals.sum(dim=1).double().sum(dim=0) / n).to(dtype)
+        info[s] = torch.tensor([int(ok[s].sum()), n, mu, mv], dtype=torch.int32, device=dev)
+    if share:
+        colour, info = colour.expand(B, 3).contiguous(), info.expand(B, 4).contiguous()
+    return (colour, info) if return_info else colour
+
+
+def chroma_key(image, screen, clip_fg=0.15, clip_bg=0.85, sure_fg=0.05, sure_bg=0.95, erode_px=10, dilate_px=10, despill=1.0,
+               want=("key", "trimap", "despilled"), dtype=torch.float32):
+    """`Engine.chroma_key` in torch, on the tensors' own device (the function defined in include/sdmatte.h): image [B,H,W,3] and its screen ([B,3],
+    [B,1,1,3] or a colour per pixel [B,H,W,3]) -> the outputs named in `want`, in that order (one name: the tensor itself): key [B,H,W], trimap
+    [B,H,W] (through `trimap_from_mask`), despilled [B,H,W,3].  In fp32 equal to the kernels bit for bit; fp64 evaluates the same formulas on the fp32
+    inputs and parameters in double."""
+    from .engine import Engine
+    B, H, W = Engine._check_key_image("chroma_key", image)
+    screen, _ = Engine._check_key_screen("chroma_key", screen, B, H, W)
+    cf, cb, sf, sb, erode_px, dilate_px, ds = Engine._check_key_params("chroma_key", clip_fg, clip_bg, sure_fg, sure_bg, erode_px, dilate_px, despill)
+    want = Engine._check_key_want("chroma_key", want)
+    dtype = _key_dtype("chroma_key", dtype)
+    dev = image.device
+    f = lambda v: torch.tensor(v, dtype=torch.float32, device=dev).to(dtype)
+    img = image.detach().float().to(dtype)
+    S = screen.detach().float().to(dtype)
+    S = (S.view(B, 1, 1, 3) if S.dim() == 2 else S).expand(B, H, W, 3)
+    k = torch.where(S[..., 1] > S[..., 0], 1, 0)
+    k = torch.where(S[..., 2] > torch.where(k == 1, S[..., 1], S[..., 0]), 2, k)
+
+    def split(v):
+        r, g, b = v.unbind(-1)
+        top = torch.where(k == 0, r, torch.where(k == 1, g, b))
+        other = torch.where(k == 0, torch.where(g > b, g, b), torch.where(k == 1, torch.where(r > b, r, b), torch.where(r > g, r, g)))
+        return top, other
+    ck, yc = split(img)
+    Sk, yS = split(S)
+    m, mS = ck - yc, Sk - yS
+    valid = (mS >= f(Engine.KEY_MIN_SEP)) & torch.isfinite(m)
+    q = (f(cb) * mS - m) / ((f(cb) - f(cf)) * mS)
+    one, zero = torch.ones_like(q), torch.zeros_like(q)
+    key = torch.where(valid, torch.where(q > 0, torch.where(q < 1, q, one), zero), one)
+    cls_f = valid & (m <= f(sf) * mS)
+    cls_b = valid & ~cls_f & (m >= f(sb) * mS)
+    outs = {"key": key}
+    if "trimap" in want:
+        t0 = trimap_from_mask(key, 0.5, erode_px, dilate_px).to(dev)
+        keep = ((t0 == 1.0) & cls_f) | ((t0 == 0.0) & cls_b) | (t0 == 0.5)
+        outs["trimap"] = torch.where(keep, t0, torch.full_like(t0, 0.5)).to(dtype)
+    if "despilled" in want:
+        d = ck - f(ds) * m
+        spill = valid & (m > 0)
+        outs["despilled"] = torch.stack([torch.where(spill & (k == c), d, img[..., c]) for c in range(3)], dim=-1)
+    res = tuple(outs[w] for w in want)
+    return res[0] if len(res) == 1 else res
+
+
+def key_screen(image, hint="green", share=False, screen_correction=True, screen_cut=0.25, clip_fg=0.15, clip_bg=0.85, sure_fg=0.05, sure_bg=0.95,
+               erode_px=10, dilate_px=10, despill=1.0, want=("key", "trimap", "despilled"), dtype=torch.float32):
+    """`Engine.key_screen` in torch: `screen_colour`, then `chroma_key`; with screen_correction a first key, `clean_plate(image, key, alpha_cut =
+    screen_cut)` as the screen's colour at each pixel, and the key against that plane.  Returns the outputs named in `want`, then the screen ([B,3]
+    or the plate [B,H,W,3])."""
+    params = (clip_fg, clip_bg, sure_fg, sure_bg, erode_px, dilate_px, despill)
+    screen = screen_colour(image, hint, share, dtype=dtype)
+    if screen_correction:
+        key = chroma_key(image, screen.float(), *params, want=("key", ), dtype=dtype)
+        screen = clean_plate(image, key.float(), alpha_cut=screen_cut, dtype=dtype)
+    res = chroma_key(image, screen.float(), *params, want=want, dtype=dtype)
+    return (res if isinstance(res, tuple) else (res, )) + (screen, )
+
+
 def matte_metric_weights(grad_sigma=1.4):
     """(r, G, D) of sdm_matte_metrics: the Gaussian and its derivative for offsets -r .. r, computed in double from the fp32 sigma, scaled so that G (x) D
     has unit L2 norm, rounded to fp32 (numpy arrays)."""
@@ -2194,6 +2325,86 @@ class SDMatteHarmonize:
         return (out.cpu(), fg_out.cpu())
 
 
+_KEY_INPUTS = {
+    "clip_fg": ("FLOAT", {"default": 0.15, "min": 0.0, "max": 0.99, "step": 0.01,
+                          "tooltip": "screen excess (as a share of the screen's own) at and below which a pixel is all subject"}),
+    "clip_bg": ("FLOAT", {"default": 0.85, "min": 0.01, "max": 1.0, "step": 0.01, "tooltip": "screen excess at and above which a pixel is all screen"}),
+    "sure_fg": ("FLOAT", {"default": 0.05, "min": -1.0, "max": 1.0, "step": 0.01,
+                          "tooltip": "the trimap calls a pixel certain subject only with a screen excess up to this"}),
+    "sure_bg": ("FLOAT", {"default": 0.95, "min": -1.0, "max": 2.0, "step": 0.01,
+                          "tooltip": "the trimap calls a pixel certain screen only with a screen excess of at least this"}),
+    "erode_px": ("INT", {"default": 10, "min": 0, "max": 255, "tooltip": "unknown band inside the key's 0.5 contour, in pixels"}),
+    "dilate_px": ("INT", {"default": 10, "min": 0, "max": 255, "tooltip": "unknown band outside the key's 0.5 contour, in pixels"}),
+    "despill": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 1.0, "step": 0.05, "tooltip": "how much of the screen's excess is taken out of the image"}),
+}
+
+
+class SDMatteChromaKey:
+    """A green- or blue-screen shot -> the trimap for Apply SDMatte, the classical key, the despilled image and the screen, on the GPU.  The screen's
+    colour is found in the image (or the batch, for a clip); with screen_correction the key is made a second time against the screen's colour at each
+    pixel (the clean plate of the first key), so uneven lighting and shadows on the screen key out.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE", {"tooltip": "the shot in front of the screen"})},
+                "optional": dict({"hint": (["green", "blue", "any"], {"default": "green", "tooltip": "which saturated colour counts as a screen"}),
+                                  "share": ("BOOLEAN", {"default": False, "tooltip": "one screen colour for the whole batch (a clip)"}),
+                                  "screen_correction": ("BOOLEAN", {"default": True,
+                                                                    "tooltip": "key against the screen's colour at each pixel (the clean plate of a first key)"}),
+                                  "screen_cut": ("FLOAT", {"default": 0.25, "min": 2.0 ** -10, "max": 1.0, "step": 0.01,
+                                                           "tooltip": "first-key value from which a pixel no longer counts as screen for the plate"})},
+                                 **_KEY_INPUTS,
+                                 force_cpu=("BOOLEAN", {"default": False, "tooltip": "evaluate the torch restatement on the CPU instead of the GPU calls"}))}
+
+    RETURN_TYPES = ("MASK", "MASK", "IMAGE", "IMAGE")
+    RETURN_NAMES = ("trimap", "key", "despilled", "screen")
+    FUNCTION = "key"
+    CATEGORY = "Matting/SDMatte"
+
+    def key(self, image, hint="green", share=False, screen_correction=True, screen_cut=0.25, clip_fg=0.15, clip_bg=0.85, sure_fg=0.05, sure_bg=0.95,
+            erode_px=10, dilate_px=10, despill=1.0, force_cpu=False):
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        args = (hint, bool(share), bool(screen_correction), float(screen_cut), float(clip_fg), float(clip_bg), float(sure_fg), float(sure_bg),
+                int(erode_px), int(dilate_px), float(despill), ("trimap", "key", "despilled"))
+        if force_cpu:      # an explicit request, never a silent substitute: the same functions in torch
+            trimap, key, despilled, screen = key_screen(image.detach().cpu(), *args)
+        else:
+            device = _torch_device()
+            trimap, key, despilled, screen = (t.cpu() for t in _trimap_engine(device).key_screen(image.detach().to(device), *args, sync=False))
+        return (trimap, key, despilled, screen if screen.dim() == 4 else screen.view(-1, 1, 1, 3))
+
+
+class SDMatteDespill:
+    """An image (or the foreground colours of SDMatte Foreground Colours) + the screen of SDMatte Chroma Key -> the image without the screen's
+    reflected light: the excess of the screen's channel over the larger of the other two is taken out.  One kernel launch.  Needs no checkpoint."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {"required": {"image": ("IMAGE", {"tooltip": "the shot, or foreground colours estimated from it"}),
+                             "screen": ("IMAGE", {"tooltip": "the screen of SDMatte Chroma Key: one colour per image [B,1,1,3], or a colour per pixel"})},
+                "optional": {"despill": _KEY_INPUTS["despill"],
+                             "force_cpu": ("BOOLEAN", {"default": False, "tooltip": "evaluate the torch restatement on the CPU instead of the GPU call"})}}
+
+    RETURN_TYPES = ("IMAGE", )
+    RETURN_NAMES = ("image", )
+    FUNCTION = "despill"
+    CATEGORY = "Matting/SDMatte"
+
+    def despill(self, image, screen, despill=1.0, force_cpu=False):
+        if image.dim() != 4 or image.shape[-1] != 3:
+            raise ValueError(f"[SDMatte] image must be [B,H,W,3], got {tuple(image.shape)}")
+        B, H, W = (int(v) for v in image.shape[:3])
+        if screen.dim() != 4 or tuple(screen.shape) not in ((B, 1, 1, 3), (B, H, W, 3)):
+            raise ValueError(f"[SDMatte] screen must be [B,1,1,3] or [B,H,W,3] of the image {(B, H, W)}, got {tuple(screen.shape)}")
+        if force_cpu:      # an explicit request, never a silent substitute: the same function in torch
+            return (chroma_key(image.detach().cpu(), screen.detach().cpu(), despill=float(despill), want=("despilled", )), )
+        device = _torch_device()
+        out = _trimap_engine(device).chroma_key(image.detach().to(device), screen.detach().to(device), despill=float(despill), want=("despilled", ),
+                                                sync=False)
+        return (out.cpu(), )
+
+
 class SDMatteMetrics:
     """Alpha + ground truth (+ trimap) -> the matting literature's SAD, MSE, Grad and Conn over the trimap's unknown band (the whole frame without a
     trimap), on the GPU: 2 kernel launches, 63 with connectivity.  Needs no checkpoint."""
@@ -2310,9 +2521,20 @@ def with_plate_node(mappings, plate: bool = True):
     return classes, names
 
 
-# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1, SDMATTE_HARMONIZE_NODE=1, SDMATTE_METRICS_NODE=1, SDMATTE_TILED_NODE=1, SDMATTE_PLATE_NODE=1), like the multi-GPU fan-out
+def with_key_nodes(mappings, on: bool = True):
+    """(classes, names) of `mappings` plus `SDMatteChromaKey` and `SDMatteDespill` when `on`; the argument is not modified (as `with_harmonize_node`)."""
+    classes, names = dict(mappings[0]), dict(mappings[1])
+    if on:
+        classes["SDMatteChromaKey"] = SDMatteChromaKey
+        names["SDMatteChromaKey"] = "SDMatte Chroma Key (Green Screen)"
+        classes["SDMatteDespill"] = SDMatteDespill
+        names["SDMatteDespill"] = "SDMatte Despill"
+    return classes, names
+
+
+# the nodes beyond the reference are opt-in (SDMATTE_EXTRA_NODES=1, SDMATTE_FOREGROUND_NODE=1, SDMATTE_REFINE_NODE=1, SDMATTE_CLEAN_NODE=1, SDMATTE_ROI_NODE=1, SDMATTE_CANVAS_NODE=1, SDMATTE_SUBJECTS_NODE=1, SDMATTE_EDGE_NODES=1, SDMATTE_VIDEO_NODE=1, SDMATTE_MOTION_NODE=1, SDMATTE_DEFOCUS_NODE=1, SDMATTE_HARMONIZE_NODE=1, SDMATTE_METRICS_NODE=1, SDMATTE_TILED_NODE=1, SDMATTE_PLATE_NODE=1, SDMATTE_KEY_NODES=1), like the multi-GPU fan-out
 # (SDMATTE_MULTI_GPU)
-NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_plate_node(with_tiled_node(with_metrics_node(with_harmonize_node(node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
+NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_key_nodes(with_plate_node(with_tiled_node(with_metrics_node(with_harmonize_node(node_mappings(os.environ.get("SDMATTE_EXTRA_NODES") == "1",
                                                                 os.environ.get("SDMATTE_FOREGROUND_NODE") == "1",
                                                                 os.environ.get("SDMATTE_REFINE_NODE") == "1",
                                                                 os.environ.get("SDMATTE_CLEAN_NODE") == "1",
@@ -2326,4 +2548,5 @@ NODE_CLASS_MAPPINGS, NODE_DISPLAY_NAME_MAPPINGS = with_plate_node(with_tiled_nod
                                                                       os.environ.get("SDMATTE_HARMONIZE_NODE") == "1"),
                                                                       os.environ.get("SDMATTE_METRICS_NODE") == "1"),
                                                                       os.environ.get("SDMATTE_TILED_NODE") == "1"),
-                                                                      os.environ.get("SDMATTE_PLATE_NODE") == "1")
+                                                                      os.environ.get("SDMATTE_PLATE_NODE") == "1"),
+                                                                      os.environ.get("SDMATTE_KEY_NODES") == "1")

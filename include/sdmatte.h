@@ -711,6 +711,76 @@ int sdm_harmonize(sdm_ctx* ctx, const float* fg_bhw3, const float* alpha_bhw, co
                   float luma_strength, float chroma_strength, float contrast_strength, float wrap_strength, float wrap_sigma, float* out_bhw3,
                   float* fg_out_bhw3, float* map_out_b12, int ptr_kind, void* stream);
 
+/* Green-screen shots (beyond the reference): the screen's colour, the colour-difference key, a trimap from the key, despill.  A subject in front of a green
+ * or blue screen carries its own mask in its colours: a classical keyer is unreliable where the model is good (hair, blur, glass) and reliable where the
+ * model needs help (which pixels are certainly screen, which certainly subject), so the keyer is the trimap source for such footage.  No weights.
+ * All arithmetic is fp32 without FMA contraction, in the order written; a compare is one fp32 compare, so a NaN fails it.
+ *
+ * sdm_screen_colour: image is fp32 [B,H,W,3], screen_b3 is fp32 [B][3], info_b4 is int32 [B][4] or NULL; all of one pointer kind.
+ *   eligible  for a pixel (r, g, b): s = (r + g) + b; mx the largest and mn the smallest of the three, formed by compares.  The pixel is eligible iff
+ *             s >= SDM_KEY_MIN_SUM (0.15) and mx - mn >= SDM_KEY_MIN_SAT (0.25) * s and, for hint = 1 (green), g > r and g > b, for hint = 2 (blue),
+ *             b > r and b > g; hint = 0 takes any saturated colour.
+ *   bin       an eligible pixel falls into bin (iu, iv), iu = min(63, (int)((r / s) * 64)), iv = min(63, (int)((g / s) * 64)), of a 64 x 64 int32 histogram
+ *             of chromaticity (normalising by s makes an unevenly lit screen one cluster).  Where the quotient times 64 is negative or a NaN (an image
+ *             with negative or infinite colours) the index is 0: the cast would be undefined.
+ *   slots     one histogram per image; with share = 1 one for the whole batch (a clip has one screen), and the slot's pixels are those of the images laid
+ *             end to end as one image of B * H rows.
+ *   mode      C(iu, iv) = the sum of the up to nine bins of the 3 x 3 neighbourhood inside the grid; the mode is the bin of the largest C, on a tie the
+ *             smallest index iu * 64 + iv.
+ *   colour    the mean of r, g, b over the slot's eligible pixels whose bin lies in the mode's 3 x 3 neighbourhood (the selected pixels): fp32 sums per
+ *             run of SDM_KEY_RUN = 4096 consecutive pixels of the slot in a fixed tree (the summation contract of sdm_harmonize), an integer count;
+ *             the runs are added in fp64 in ascending order, the division is fp64, rounded once to fp32.
+ *   outputs   screen_b3[b] = the colour of image b's slot (with share = 1 every row is the same); info_b4[b] = {eligible pixels, selected pixels, iu, iv}
+ *             of that slot.  A slot without an eligible pixel gives the colour (0, 0, 0) and {0, 0, -1, -1}.
+ * Histogram, mode and info are integers: GPU, emulator and any other evaluation agree on them exactly.
+ *
+ * sdm_chroma_key: image is fp32 [B,H,W,3]; screen is fp32 [B][3] (screen_is_plane = 0) or [B][H][W][3] (screen_is_plane = 1: a colour per pixel, for
+ * example the plate of sdm_fill_background), of the image's pointer kind; key_bhw and trimap_bhw are fp32 [B,H,W], despilled_bhwc is fp32 [B,H,W,3];
+ * each output may be NULL, but not all three.  Per pixel, c the pixel and S its screen colour:
+ *   k         the index of the largest component of S, the lowest on a tie; o1 < o2 the other two;  y(v) = (v[o1] > v[o2]) ? v[o1] : v[o2]
+ *   m = c[k] - y(c);  mS = S[k] - y(S);  the pixel is VALID iff mS >= SDM_KEY_MIN_SEP (1/64) and m is finite.
+ *   key       a valid pixel gets clamp01(q), t = clip_bg * mS, q = (t - m) / ((clip_bg - clip_fg) * mS), clamp01(q) = q > 0 ? (q < 1 ? q : 1) : 0; an
+ *             invalid pixel gets 1.  (The colour-difference key: m / mS is 1 on the screen and 0 on anything whose k-th channel does not stand out.)
+ *   class     F iff valid and m <= sure_fg * mS;  B iff valid, not F and m >= sure_bg * mS;  U otherwise.  Products, not quotients: the plane is exact.
+ *   trimap    T0 = the trimap of sdm_make_trimap(key, 0.5, erode_px, dilate_px) as that call defines it, on this call's key.  The result is T0 where
+ *             (T0 == 1 and the class is F) or (T0 == 0 and the class is B) or T0 == 0.5, and 0.5 elsewhere: the band follows the robust 0.5 contour of the
+ *             key, a pixel counts as definite only where its own colour agrees, and a stray unsure pixel stays ONE unknown pixel (it does not grow).
+ *   despilled the k-th channel becomes c[k] - despill * m where the pixel is valid and m > 0; everything else is a bit copy.
+ * These hold bit for bit:
+ *   1. despill = 0 copies the image;
+ *   2. a valid pixel equal to its screen colour has key 0 and, with sure_fg < 1 and sure_bg <= 1, class B;
+ *   3. a valid pixel with r = g = b has key 1 and, with sure_fg >= 0, class F;
+ *   4. a plane that holds one colour per image gives the bits of the colour form;
+ *   5. the trimap equals the formula above evaluated with sdm_make_trimap on the call's own key output;
+ *   6. an image's results (sdm_screen_colour with share = 0, sdm_chroma_key) do not depend on the batch it is in; two calls, host and device pointers, and
+ *      pointers 4 bytes off a 16-byte boundary all give the same bits;
+ *   7. sdm_screen_colour with share = 1 equals the call on the images laid end to end as one image of B * H rows (rows do not interact in that call).
+ * sdmatte_nodes.screen_colour and sdmatte_nodes.chroma_key are the same functions in torch (the integers and sdm_chroma_key bit for bit, the colour to fp32
+ * rounding).
+ * Limits: hint 0, 1 or 2; share 0 or 1; without share B <= SDM_KEY_MAX_SLOTS = 65536 (a histogram per image, indexed with ints); clip_fg finite in
+ * [0, 1), clip_bg in (clip_fg, 1], sure_fg finite in [-1, 1], sure_bg in [sure_fg, 2], despill in [0, 1]; the radii in 0 .. SDM_TRIMAP_MAX_RADIUS (looked
+ * at with or without trimap_bhw); B, H, W >= 1 within SDM_FG_MAX_SIDE / SDM_FG_MAX_PIXELS: SDM_ERR_INVALID otherwise, with a message that names the
+ * argument, and then nothing is queued or written.  Stream contract and pointer kinds as sdm_make_trimap; sdm_last_forward_ms covers the launches.  Kernel
+ * launches (csrc/k_key.h), by these names in sdm_kernel_counts and the per-launch profile: sdm_screen_colour makes 5 (`ck_clear`, `ck_hist`, `ck_mode`,
+ * `ck_mean`, `ck_finalize`); sdm_chroma_key makes 1 (`ck_key`) without trimap_bhw and 4 with it (`ck_key`, `trimap_cols`, `trimap_rows`, `ck_veto`); the
+ * counts depend on the arguments only; no host readback.  The histograms (16 KB per slot), the partials (16 bytes per run), the class bytes (1 per pixel),
+ * the int16 plane of sdm_make_trimap and, when trimap_bhw is given without key_bhw, the key live in the activation arena; host pointers go through the
+ * I/O staging. */
+#define SDM_KEY_MIN_SUM 0.15f
+#define SDM_KEY_MIN_SAT 0.25f
+#define SDM_KEY_MIN_SEP 0.015625f
+#define SDM_KEY_RUN 4096
+#define SDM_KEY_MAX_SLOTS 65536
+#define SDM_KEY_CLIP_FG 0.15f
+#define SDM_KEY_CLIP_BG 0.85f
+#define SDM_KEY_SURE_FG 0.05f
+#define SDM_KEY_SURE_BG 0.95f
+int sdm_screen_colour(sdm_ctx* ctx, const float* image_bhwc, int B, int H, int W, int hint, int share, float* screen_b3, int32_t* info_b4, int ptr_kind,
+                      void* stream);
+int sdm_chroma_key(sdm_ctx* ctx, const float* image_bhwc, const float* screen, int screen_is_plane, int B, int H, int W, float clip_fg, float clip_bg,
+                   float sure_fg, float sure_bg, int erode_px, int dilate_px, float despill, float* key_bhw, float* trimap_bhw, float* despilled_bhwc,
+                   int ptr_kind, void* stream);
+
 /* Score a matte (beyond the reference): SAD, MSE, Grad and Conn, the four numbers of the matting literature (Rhemann et al., "A perceptually motivated
  * online benchmark for image matting"; the SDMatte paper reports them), over the unknown band of the trimap.  No weights.
  * pred and gt are fp32 [B,H,W]; trimap is fp32 [B,H,W] in [0, 1] or NULL; stats is fp64 [B][SDM_MM_STATS]; level is int32 [B,H,W] or NULL; all of one
